@@ -139,7 +139,12 @@ def parse():
                          "launch of the real run on a one-rank RCCL communicator; the other ranks' contributions are zeros)")
     ap.add_argument("--no-shard-graph", action="store_true", help="N > 1 with --comm direct: do not capture the sharded step in a HIP graph")
     ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what their last step handed its caller (loss, forward outputs, the updated "
+                         "parameters and buffers) as DIR/<name>.npy in float32 / float64, at most 64 MB in all")
     a = ap.parse_args()
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
     if a.resample and a.hip_graph:
         a.static_step = True         # a new draw per REPLAY needs fixed shapes and device-side counts: --resample --hip-graph implies --static-step
     return a
@@ -163,6 +168,8 @@ def build_step_inputs(workload, negative, seed):
 class Step:
     """One search step on the HIP operators (reference search/mr_lp_search.py:187-245, without
     the sampler and the architect step)."""
+
+    keep_outputs = False       # --dump-outputs: hold the forward outputs of the latest step in last_out
 
     def __init__(self, args, device, inputs):
         from mr_gnas_amd import graph as G, supernet as S
@@ -228,6 +235,8 @@ class Step:
         if self.sample_size:
             self.resample(self.sample_size, self._args.negative)
         ent, rel = self.model(self.g, self.node_id, self.src_in, self.edge_type)
+        if self.keep_outputs:
+            self.last_out = {"ent": ent, "rel": rel}
         loss = self.model.get_loss(self.g, ent, rel, self.samples, self.labels)
         loss.backward()
         if not self.fused_opt:
@@ -243,6 +252,8 @@ class FixedStep:
     """BASELINE config 1 on the GPU: one mini-batch step of the fixed README genotype (reference README.md:26,
     train/mr_lp_train.py:215-266): full training graph (un-sorted halves), feature_dim = init_fea_dim = 64, num_base_r = 23,
     batch 256, DistMult [B, N] scorer + BCELoss on label-smoothed dense targets (device LabelIndex), Adam."""
+
+    keep_outputs = False       # --dump-outputs: hold the forward outputs of the latest step in last_out
 
     def __init__(self, args, device, shape="fb15k237", dim=64, init_dim=64, nbase=23):
         """shape "synthetic10m" (BASELINE config 5: 10 M edges, 1 M nodes, 512 relation ids, D = 256) is SURVEY 8(d)'s
@@ -270,6 +281,8 @@ class FixedStep:
     def __call__(self):
         labels = self.idx.labels(self.subj, self.rel, 0.1)             # TrainDataset.__getitem__ on the device (label smoothing 0.1)
         pred = self.model(self.g, self.subj, self.rel)
+        if self.keep_outputs:
+            self.last_out = {"pred": pred}
         loss = F.binary_cross_entropy(pred, labels)
         loss.backward()
         self.opt.step()
@@ -281,6 +294,8 @@ class CompGCNStep:
     """A 2-layer CompGCN forward + backward on the FB15k-237-shaped graph (reference models/compgcn.py:116-185: basis-decomposed
     relation table, CompGraphConv x 2 with BatchNorm, tanh and dropout; no driver of the reference reaches it, so the step is
     the module itself: forward, a squared-norm loss on both outputs, backward, Adam)."""
+
+    keep_outputs = False       # --dump-outputs: hold the forward outputs of the latest step in last_out
 
     def __init__(self, args, device):
         from mr_gnas_amd import compgcn as C, graph as G, synth
@@ -302,6 +317,8 @@ class CompGCNStep:
 
     def __call__(self):
         n, r = self.model(self.g)
+        if self.keep_outputs:
+            self.last_out = {"n_feats": n, "r_feats": r}
         loss = n.square().mean() + r.square().mean()
         loss.backward()
         self.opt.step()
@@ -578,6 +595,37 @@ def log(msg):
     print(f"[bench {time.strftime('%H:%M:%S')}] {msg}", file=sys.stderr, flush=True)
 
 
+DUMP_BUDGET_BYTES = 64 << 20
+
+
+def dump_outputs(step, out_dir):
+    """--dump-outputs: what the last timed step handed its caller -- the loss, the forward outputs (last_out), every parameter and
+    buffer of the model after the optimizer step -- as out_dir/<name>.npy.  Floating tensors keep float64 or become float32, integer
+    buffers become float64.  An array larger than the per-array cap is replaced by a fixed 1-D sample of its flattened elements (indices
+    drawn from a generator seeded by the array's name, sorted), the cap halved until all arrays together fit DUMP_BUDGET_BYTES.
+    Returns (files, bytes)."""
+    import zlib
+    from mr_gnas_amd import lazy as LZ
+    arrays = {"loss": step.last_loss}
+    arrays.update({"out." + k: LZ.real(v) for k, v in getattr(step, "last_out", {}).items()})
+    arrays.update({"state." + k: v for k, v in step.model.state_dict().items()})
+    arrays = {k: v.detach() for k, v in arrays.items()}
+    out_dtype = {k: np.float64 if v.dtype in (torch.float64, torch.int64, torch.int32) else np.float32 for k, v in arrays.items()}
+    cap = max(v.numel() for v in arrays.values())        # whole arrays when they fit
+    while sum(min(v.numel(), cap) * np.dtype(out_dtype[k]).itemsize for k, v in arrays.items()) > DUMP_BUDGET_BYTES:
+        cap //= 2
+    os.makedirs(out_dir, exist_ok=True)
+    total = 0
+    for k, v in arrays.items():
+        if v.numel() > cap:
+            rng = np.random.default_rng(zlib.crc32(k.encode()))
+            v = v.reshape(-1)[torch.from_numpy(np.sort(rng.integers(0, v.numel(), cap))).to(v.device)]
+        a = v.cpu().numpy().astype(out_dtype[k])
+        np.save(os.path.join(out_dir, k + ".npy"), a)
+        total += a.nbytes
+    return len(arrays), total
+
+
 def main():
     args = parse()
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -692,6 +740,7 @@ def main():
         step = Step(args, device, step_inputs)
         barrier = lambda: None
 
+    step.keep_outputs = args.dump_outputs is not None
     log(f"inputs resident: E={getattr(step, 'E_global', step.E)} world={world}")
     for i in range(args.warmup):
         step()
@@ -780,6 +829,10 @@ def main():
         t = torch.tensor([dt], dtype=torch.float64, device=("cpu" if dist.get_backend() == "gloo" else device))
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
+    if args.dump_outputs is not None and rank == 0:
+        # before any further step (eager leg, exact-f32 leg, caller legs) changes the parameters
+        files, nbytes = dump_outputs(step, args.dump_outputs)
+        log(f"last timed step's outputs: {files} arrays, {nbytes / 2**20:.1f} MB in {args.dump_outputs}")
 
     eager_ms = None
     if sharded and launch_mode != "eager":

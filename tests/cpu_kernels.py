@@ -120,3 +120,29 @@ def registry():
         "a_max": lambda a: _Agg(D(a), "max", 0.0), "a_mean": lambda a: _Agg(D(a), "mean", 0.0),
         "a_sum": lambda a: _Agg(D(a), "sum", a.get("drop_aggr", 0.0)),
     }
+
+
+def wrap_operator(inner):
+    """A CPU restatement behind this package's operator protocol (operations_lp._Operator: forward -> a lazy handle when handles are
+    enabled, run -> the value), parameters under the restatement's names (the reference's)."""
+    from mr_gnas_amd import lazy as LZ, operations_lp as OPS
+
+    class W(OPS._Operator):
+        def __init__(self):
+            super().__init__()
+            for k, m in inner.named_children():
+                setattr(self, k, m)
+            object.__setattr__(self, "_inner", inner)
+
+        def out_shape(self, g, src_emb):
+            rows = g.number_of_nodes() if type(inner).__name__ == "_Agg" else src_emb.shape[0]
+            return (rows, src_emb.shape[1])
+
+        def run(self, g, a, b, for_epilogue=False):
+            return inner(g, LZ.real(a), LZ.real(b))
+    return W()
+
+
+def wrapped_registry():
+    """registry() with every operator behind wrap_operator: what a CPU run of the reference's MixedOp / Cell can execute."""
+    return {k: (lambda ctor: lambda args: wrap_operator(ctor(args)))(v) for k, v in registry().items()}

@@ -694,6 +694,101 @@ def case_labels_and_ranking(name, N, T, R, B, seed):
     print("wrote labels_ranking_%s: train pairs=%d test rows=%d mrr=%.4f" % (name, len(tr), len(te), res["mrr"] / res["count"]))
 
 
+# --------------------------------------------------------------------------
+# drop-in contract: what the reference's callers build and compute
+# --------------------------------------------------------------------------
+DROPIN_GENOTYPE = [("pre_sub", 1, 0), ("f_sparse_comp", 2, 1), ("f_sparse_comp", 3, 2), ("a_max", 4, 2), ("a_max", 5, 3),
+                   ("f_sparse_last", 6, 5), ("f_sparse_last", 7, 5)]
+
+
+def case_dropin(seed=3):
+    """tests/test_dropin_cpu.py's fixtures.  dropin_contract.json: the state_dict key -> shape maps of the reference's Cell (1, 2, 2,
+    D = 200), search Network and README-genotype Cell (models/model_lp.py) on the reference's own operators, its architecture
+    parameter shapes, the argument names of its cell classes' __init__ / forward, and the names models/cell_lp.py,
+    models/model_search_lp.py and models/model_lp.py import from models.operations_lp / models.cell_lp.  dropin_caller.npz: one
+    search step of the reference's unchanged Network (models/model_search_lp.py) on a small seeded graph, its operators the CPU
+    restatements of tests/cpu_kernels.py behind this package's operator protocol: parameters, architecture parameters, ent, rel,
+    loss and every gradient."""
+    import ast
+    import inspect
+    import json
+    from configs.genotypes import Genotype
+    import models.cell_lp as CL
+    import models.model_lp as ML
+    import models.model_search_lp as MS
+
+    shape = lambda m: {k: list(v.shape) for k, v in m.state_dict().items()}
+    torch.manual_seed(0)
+    net = MS.Network("cpu", 60, 7, 2, 1, 2, 2, 24, 12, 15, 40.0, 0.0, 0.0)
+    ref_args = types.SimpleNamespace(feature_dim=64, drop_aggr=0.0, drop_op=0.0, dropout=0.0)   # Cell(args, genotype), models/model_lp.py:38-47
+    imports = {}
+    for mod in ("cell_lp", "model_search_lp", "model_lp"):
+        tree = ast.parse(open(os.path.join(REF, "models", mod + ".py")).read())
+        for node in tree.body:
+            if isinstance(node, ast.ImportFrom) and node.module in ("models.operations_lp", "models.cell_lp"):
+                imports.setdefault(node.module, set()).update(a.name for a in node.names)
+    contract = {
+        "cell": shape(CL.Cell(1, 2, 2, 200, 0.0)),
+        "net": shape(net),
+        "alpha": [list(a.shape) for a in net.arch_parameters()],
+        "fixed_cell": shape(ML.Cell(ref_args, Genotype(alpha_cell=DROPIN_GENOTYPE, concat_node=[4, 5, 6, 7], score_func="sf_DisMult"))),
+        "signatures": {name: {"init": list(inspect.signature(getattr(CL, name).__init__).parameters),
+                              "forward": list(inspect.signature(getattr(CL, name).forward).parameters)}
+                       for name in ("MixedOp", "Cell_Zero", "Cell_First", "Cell_Middle", "Cell_Last", "Cell")},
+        "imports": {k: sorted(v) for k, v in sorted(imports.items())},
+    }
+    with open(os.path.join(OUT, "dropin_contract.json"), "w") as f:
+        json.dump(contract, f, indent=1, sort_keys=True)
+        f.write("\n")
+
+    sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
+    import importlib
+    import cpu_kernels as CK
+    from mr_gnas_amd import graph as G, lazy as LZ, operations_lp as OPS
+    LZ.ENABLED = False
+    mod = types.ModuleType("models.operations_lp")
+    for name in ("PRE_OPS", "FIRST_OPS", "MIDDLE_OPS", "LAST_OPS", "SF_OPS", "MIXED_OPS_sf"):
+        setattr(mod, name, getattr(OPS, name))
+    mod.MIXED_OPS = CK.wrapped_registry()
+    saved = sys.modules["models.operations_lp"]
+    sys.modules["models.operations_lp"] = mod
+    try:
+        CL2 = importlib.reload(CL)
+        MS2 = importlib.reload(MS)
+        rng = np.random.default_rng(seed)
+        n, R, T, D = 40, 5, 150, 12
+        tri = np.stack([rng.integers(0, n, T), rng.integers(0, R, T), rng.integers(0, n, T)], 1)
+        samples = np.stack([rng.integers(0, n, 300), rng.integers(0, 2 * R, 300), rng.integers(0, n, 300)], 1)
+        st = {"n": n, "R": R, "D": D, "tri": tri, "samples": samples, "labels": rng.integers(0, 2, 300).astype(np.float32)}
+        g = G.build_search_graph(n, R, tri)
+        src, _, _ = g.edges(form="all")
+        torch.manual_seed(0)
+        net = MS2.Network("cpu", n, R, 2, 1, 2, 2, D, 8, 2 * R + 1, 40.0, 0.0, 0.0)
+        net.train()
+        for k, v in net.state_dict().items():
+            st["param/" + k] = v.clone()
+        for i, a in enumerate(net.arch_parameters()):
+            st[f"alpha/{i}"] = a.detach().clone()
+        ent, rel = net(g, torch.arange(n).view(-1, 1), src, g.edata["e_type"])
+        loss = net.get_loss(g, ent, rel, torch.from_numpy(samples), torch.from_numpy(st["labels"]))
+        loss.backward()
+        st.update(ent=ent.detach(), rel=rel.detach(), loss=loss.detach())
+        for k, p in net.named_parameters():
+            if p.grad is not None:
+                st["gparam/" + k] = p.grad.clone()
+        for i, a in enumerate(net.arch_parameters()):
+            if a.grad is not None:                         # the score-function alpha does not enter this step
+                st[f"galpha/{i}"] = a.grad.clone()
+        for k, v in net.named_buffers():                   # after the step: the BatchNorm running statistics it updated
+            st["state_after/" + k] = v.clone()
+    finally:
+        sys.modules["models.operations_lp"] = saved
+        importlib.reload(CL2)
+        importlib.reload(MS)
+    np.savez_compressed(os.path.join(OUT, "dropin_caller.npz"), **npify(st))
+    print("wrote dropin_contract.json, dropin_caller: loss=%.6f" % float(loss))
+
+
 def main():
     _install_standins()
     torch.set_num_threads(1)
@@ -716,6 +811,7 @@ def main():
     case_sampling_neighbor("small", 400, 3000, 7, 200, 10, 53)
     case_sampling_neighbor("dense", 60, 900, 5, 600, 2, 54)        # two thirds of all triples: long rejection runs, exhausted vertices
     case_labels_and_ranking("small", 150, 1200, 5, 64, 52)
+    case_dropin()
 
 
 if __name__ == "__main__":

@@ -184,7 +184,10 @@ def test_sharded_fixed_network_matches_reference(tmp_path, world, case):
         got = res["g/" + k]
         assert got is not None, k
         scale = max(float(v.abs().max()), 1e-8)
-        assert float((got - v).abs().max()) <= 2e-3 * scale + 1e-7, k
+        # a bias in front of a BatchNorm (linear_e, the cell's concat) has a gradient that is zero in exact arithmetic: both sides hold
+        # ~1e-7 of rounding noise whose size follows the host CPU's summation order (as in the world2_equals_world1 test below)
+        atol = 1e-6 if scale < 1e-6 else 1e-7
+        assert float((got - v).abs().max()) <= 2e-3 * scale + atol, k
 
 
 MIXED_CELL = [('pre_mult', 1, 0), ('f_identity', 2, 1), ('f_comp', 3, 1), ('f_zero', 3, 2), ('a_sum', 4, 2), ('a_mean', 5, 3),

@@ -1,233 +1,154 @@
-"""Drop-in pin: the REFERENCE's own callers -- models/cell_lp.py (MixedOp, Cell_*, Cell) and
-models/model_search_lp.py (Network) -- construct on ``mr_gnas_amd.operations_lp`` swapped in for ``models.operations_lp``,
-and what they build has the parameter names / shapes of this package's restated callers (supernet.SuperCell /
-SearchNetwork), so reference checkpoints and code paths line up.  Build-container only: skipped where /root/reference is
-absent (the GPU box).  Runs in a subprocess: the stand-in modules must not leak into the other tests' sys.modules.
+"""Drop-in pin: the reference's callers -- models/cell_lp.py (MixedOp, Cell_*, Cell), models/model_search_lp.py
+(Network) and models/model_lp.py (Cell) -- take ``mr_gnas_amd.operations_lp`` / ``mr_gnas_amd.cell_lp`` swapped in for
+``models.operations_lp`` / ``models.cell_lp``: every name they import exists here, their cell classes' argument names are a prefix of
+this package's, and what they build has the parameter names / shapes of this package's restated callers (supernet.SuperCell /
+SearchNetwork / FixedCell), so reference checkpoints and code paths line up.  The reference's side is the fixture
+tests/golden/dropin_contract.json, and one search step of the reference's unchanged Network is tests/golden/dropin_caller.npz
+(both written by tests/golden/make_golden.py, case_dropin, from the reference's own code).
 Reference: models/cell_lp.py:12-33,155-188, models/model_search_lp.py:16-129, models/model_lp.py:13-74."""
+import inspect
 import json
 import os
-import subprocess
 import sys
 
-import pytest
-
-REF = "/root/reference"
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-SCRIPT = r'''
-import inspect, json, sys, types
 import torch
-sys.path.insert(0, %(root)r)
-sys.path.insert(0, %(root)r + "/tests/golden")
-import make_golden as MG                      # its stand-ins for dgl and the missing utils.gpu_memory_log (no fixture is written)
-MG._install_standins()
-import mr_gnas_amd
-from mr_gnas_amd import operations_lp as OPS, supernet as S
-import models                                  # the reference's package (namespace)
-sys.modules["models.operations_lp"] = OPS      # the swap a maintainer makes (INTEGRATION.md)
-models.operations_lp = OPS
-import models.cell_lp as CL
-import models.model_search_lp as MS
-import models.model_lp as ML
-assert CL.MIXED_OPS is OPS.MIXED_OPS and MS.FIRST_OPS is OPS.FIRST_OPS, "the reference callers did not pick up the swapped registry"
 
-out = {}
-D = 200
-ref_cell = CL.Cell(1, 2, 2, D, 0.0)
-our_cell = S.SuperCell(1, 2, 2, D, 0.0)
-shape = lambda m: {k: list(v.shape) for k, v in m.state_dict().items()}
-out["cell_ref"], out["cell_ours"] = shape(ref_cell), shape(our_cell)
+from conftest import GOLDEN, ROOT, load_golden, sub
 
-ref_net = MS.Network("cpu", 60, 7, 2, 1, 2, 2, 24, 12, 15, 40.0, 0.0, 0.0)
-our_net = S.SearchNetwork("cpu", 60, 7, 2, 1, 2, 2, 24, 12, 15, 40.0, 0.0, 0.0)
-out["net_ref"], out["net_ours"] = shape(ref_net), shape(our_net)
-out["alpha_ref"] = [list(a.shape) for a in ref_net.arch_parameters()]
-out["alpha_ours"] = [list(a.shape) for a in our_net.arch_parameters()]
-
-# a reference state_dict loads into the restated caller and back (strict)
-our_net.load_state_dict(ref_net.state_dict(), strict=True)
-ref_net.load_state_dict(our_net.state_dict(), strict=True)
-
-# fixed-genotype caller (README genotype): OpModule / Cell of models/model_lp.py on the swapped registry
-geno = S.Genotype(alpha_cell=[("pre_sub", 1, 0), ("f_sparse_comp", 2, 1), ("f_sparse_comp", 3, 2), ("a_max", 4, 2), ("a_max", 5, 3),
-                              ("f_sparse_last", 6, 5), ("f_sparse_last", 7, 5)], concat_node=[4, 5, 6, 7], score_func="sf_DisMult")
-try:
-    ref_args = types.SimpleNamespace(feature_dim=64, drop_aggr=0.0, drop_op=0.0, dropout=0.0)      # reference: Cell(args, genotype), models/model_lp.py:38-47
-    out["fixed_ref"] = shape(ML.Cell(ref_args, geno))
-    out["fixed_ours"] = shape(S.FixedCell(64, 0.0, geno))
-except (TypeError, AttributeError) as e:     # constructor contract differs from what this test assumes: report, do not hide
-    out["fixed_error"] = repr(e)
-
-# round 4: models.cell_lp swapped for mr_gnas_amd.cell_lp as well -- the reference's model_search_lp.Network then builds OUR cells
-# (same constructor arguments, same state_dict keys) and its forward runs through them (CPU: the literal formulation)
-import importlib
-from mr_gnas_amd import cell_lp as OCL
-sys.modules["models.cell_lp"] = OCL
-models.cell_lp = OCL
-MS2 = importlib.reload(MS)
-assert MS2.Cell is OCL.Cell and MS2.Cell_SF is OCL.Cell_SF, "model_search_lp did not pick up the swapped cell module"
-ref_net2 = MS2.Network("cpu", 60, 7, 2, 1, 2, 2, 24, 12, 15, 40.0, 0.0, 0.0)
-out["net_ref_swapped_cells"] = shape(ref_net2)
-out["swapped_cell_types"] = sorted({type(c).__module__ for c in ref_net2.cells})
-ref_net2.load_state_dict(ref_net.state_dict(), strict=True)
-out["cell_lp_exports"] = sorted(n for n in ("MixedOp", "MixedOp_SF", "Cell_Zero", "Cell_Final", "Cell_First", "Cell_Middle", "Cell_Last", "Cell", "Cell_SF")
-                                if hasattr(OCL, n))
-for name in ("MixedOp", "Cell_Zero", "Cell_First", "Cell_Middle", "Cell_Last", "Cell"):      # constructor / forward argument names of the reference
-    r_init = list(inspect.signature(getattr(CL, name).__init__).parameters)
-    o_init = list(inspect.signature(getattr(OCL, name).__init__).parameters)
-    r_fwd = list(inspect.signature(getattr(CL, name).forward).parameters)
-    o_fwd = list(inspect.signature(getattr(OCL, name).forward).parameters)
-    assert o_init[:len(r_init)] == r_init, (name, r_init, o_init)
-    assert o_fwd[:len(r_fwd)] == r_fwd, (name, r_fwd, o_fwd)
-# (a forward needs the HIP device -- the product has no CPU path: tests/test_nets_gpu.py::test_cell_lp_on_plain_tensors)
-
-# every operator the reference's MixedOp / OpModule would call binds (g, src_emb, src_emb_in)
-sig = {}
-for name, ctor in OPS.MIXED_OPS.items():
-    op = ctor({"feature_dim": 8, "drop_aggr": 0.0})
-    try:
-        inspect.signature(op.forward).bind("g", "h", "h_in")
-        sig[name] = True
-    except TypeError:
-        sig[name] = False
-for name, ctor in OPS.MIXED_OPS_sf.items():
-    op = ctor({"gamma": 40, "embed_dim": 200})
-    try:
-        inspect.signature(op.forward).bind("all_ent", "sub", "rel")
-        sig[name] = True
-    except TypeError:
-        sig[name] = False
-out["signatures"] = sig
-# the reference's MixedOp holds OUR operator classes
-out["mixed_op_types"] = sorted({type(op[0]).__module__ for op in ref_cell.cell_first._ops[0]._ops})
-print("RESULT " + json.dumps(out))
-'''
+GENOTYPE = [("pre_sub", 1, 0), ("f_sparse_comp", 2, 1), ("f_sparse_comp", 3, 2), ("a_max", 4, 2), ("a_max", 5, 3),
+            ("f_sparse_last", 6, 5), ("f_sparse_last", 7, 5)]
 
 
-@pytest.mark.skipif(not os.path.isdir(REF), reason="the reference is only present in the build container")
+def shape(m):
+    return {k: list(v.shape) for k, v in m.state_dict().items()}
+
+
 def test_reference_callers_construct_on_the_swapped_registry():
-    r = subprocess.run([sys.executable, "-c", SCRIPT % {"root": ROOT}], capture_output=True, text=True, timeout=600,
-                       env={**os.environ, "MRG_GOLDEN_OUT": "/tmp/mrg_dropin_unused"})
-    assert r.returncode == 0, r.stderr[-3000:]
-    line = [l for l in r.stdout.splitlines() if l.startswith("RESULT ")][-1]
-    out = json.loads(line[len("RESULT "):])
-    assert out["cell_ref"] == out["cell_ours"] and len(out["cell_ref"]) > 300          # 309 keys at (1, 2, 2, 200)
-    assert out["net_ref"] == out["net_ours"]
-    assert out["alpha_ref"] == out["alpha_ours"]
-    assert "fixed_error" not in out, out.get("fixed_error")
-    assert out["fixed_ref"] == out["fixed_ours"]
-    assert all(out["signatures"].values()), out["signatures"]
-    assert out["mixed_op_types"] == ["mr_gnas_amd.operations_lp"] or all("operations_lp" in t for t in out["mixed_op_types"])
-    # models.cell_lp swapped too (round 4): the reference's Network builds this package's cells under the same names
-    assert out["net_ref_swapped_cells"] == out["net_ref"]
-    assert all("cell_lp" in t and "mr_gnas_amd" in t or t.endswith("cell_lp") for t in out["swapped_cell_types"]), out["swapped_cell_types"]
-    assert len(out["cell_lp_exports"]) == 9, out["cell_lp_exports"]
+    from mr_gnas_amd import cell_lp as OCL, operations_lp as OPS, supernet as S
+    with open(os.path.join(GOLDEN, "dropin_contract.json")) as f:
+        ref = json.load(f)
+
+    # every name the reference's callers import from the two swapped modules
+    assert set(ref["imports"]) == {"models.operations_lp", "models.cell_lp"}, ref["imports"]
+    missing = [n for n in ref["imports"]["models.operations_lp"] if not hasattr(OPS, n)]
+    missing += [n for n in ref["imports"]["models.cell_lp"] if not hasattr(OCL, n)]
+    assert not missing, missing
+    assert OCL.MIXED_OPS is OPS.MIXED_OPS and OCL.FIRST_OPS is OPS.FIRST_OPS
+
+    # what the callers build: the reference's Cell / Network / README-genotype Cell on the reference's own operators
+    our_cell = S.SuperCell(1, 2, 2, 200, 0.0)
+    assert shape(our_cell) == ref["cell"] and len(ref["cell"]) > 300          # 309 keys at (1, 2, 2, 200)
+    our_net = S.SearchNetwork("cpu", 60, 7, 2, 1, 2, 2, 24, 12, 15, 40.0, 0.0, 0.0)
+    assert shape(our_net) == ref["net"]
+    assert [list(a.shape) for a in our_net.arch_parameters()] == ref["alpha"]
+    geno = S.Genotype(alpha_cell=GENOTYPE, concat_node=[4, 5, 6, 7], score_func="sf_DisMult")
+    assert shape(S.FixedCell(64, 0.0, geno)) == ref["fixed_cell"]
+    # the MixedOps of this package's cell hold this package's operator classes
+    assert sorted({type(op[0]).__module__ for op in our_cell.cell_first._ops[0]._ops}) == ["mr_gnas_amd.operations_lp"]
+
+    # constructor / forward argument names of the reference's cell classes are a prefix of this package's
+    exports = [n for n in ("MixedOp", "MixedOp_SF", "Cell_Zero", "Cell_Final", "Cell_First", "Cell_Middle", "Cell_Last", "Cell", "Cell_SF")
+               if hasattr(OCL, n)]
+    assert len(exports) == 9, exports
+    assert sorted(ref["signatures"]) == sorted(("MixedOp", "Cell_Zero", "Cell_First", "Cell_Middle", "Cell_Last", "Cell"))
+    for name, sig in ref["signatures"].items():
+        o_init = list(inspect.signature(getattr(OCL, name).__init__).parameters)
+        o_fwd = list(inspect.signature(getattr(OCL, name).forward).parameters)
+        assert o_init[:len(sig["init"])] == sig["init"], (name, sig["init"], o_init)
+        assert o_fwd[:len(sig["forward"])] == sig["forward"], (name, sig["forward"], o_fwd)
+
+    # every operator the reference's MixedOp / OpModule would call binds (g, src_emb, src_emb_in)
+    sig = {}
+    for name, ctor in OPS.MIXED_OPS.items():
+        op = ctor({"feature_dim": 8, "drop_aggr": 0.0})
+        try:
+            inspect.signature(op.forward).bind("g", "h", "h_in")
+            sig[name] = True
+        except TypeError:
+            sig[name] = False
+    for name, ctor in OPS.MIXED_OPS_sf.items():
+        op = ctor({"gamma": 40, "embed_dim": 200})
+        try:
+            inspect.signature(op.forward).bind("all_ent", "sub", "rel")
+            sig[name] = True
+        except TypeError:
+            sig[name] = False
+    assert all(sig.values()), sig
 
 
-# ---------------------------------------------------------------------------------------------------------------------------------
-# round 5: the reference's UNCHANGED cell_lp.py / model_search_lp.py drive the lazy-handle protocol (mr_gnas_amd/lazy.py)
-# ---------------------------------------------------------------------------------------------------------------------------------
-HANDLE_SCRIPT = r'''
-import json, sys, types
-import numpy as np
-import torch
-sys.path.insert(0, %(root)r)
-sys.path.insert(0, %(root)r + "/tests")
-sys.path.insert(0, %(root)r + "/tests/golden")
-import make_golden as MG
-MG._install_standins()
-import mr_gnas_amd
-from mr_gnas_amd import graph as G, lazy as LZ, operations_lp as OPS
-import cpu_kernels as CK                         # CPU restatements of the operators (test infrastructure)
-
-# the operator registry a CPU run can execute: this package's _Operator protocol (forward -> handle, run -> value) around the CPU
-# restatements, parameters under the reference's names
-def wrap(ctor):
-    def make(args):
-        inner = ctor(args)
-        class W(OPS._Operator):
-            def __init__(self):
-                super().__init__()
-                for k, m in inner.named_children():
-                    setattr(self, k, m)
-                object.__setattr__(self, "_inner", inner)
-            def out_shape(self, g, src_emb):
-                rows = g.number_of_nodes() if type(inner).__name__ == "_Agg" else src_emb.shape[0]
-                return (rows, src_emb.shape[1])
-            def run(self, g, a, b, for_epilogue=False):
-                return inner(g, LZ.real(a), LZ.real(b))
-        return W()
-    return make
-reg = {k: wrap(v) for k, v in CK.registry().items()}
-mod = types.ModuleType("models.operations_lp")
-for name in ("PRE_OPS", "FIRST_OPS", "MIDDLE_OPS", "LAST_OPS", "SF_OPS", "MIXED_OPS_sf"):
-    setattr(mod, name, getattr(OPS, name))
-mod.MIXED_OPS = reg
-import models
-sys.modules["models.operations_lp"] = mod
-models.operations_lp = mod
-import models.cell_lp as CL                      # the reference's own files, unchanged
-import models.model_search_lp as MS
-
-rng = np.random.default_rng(3)
-n, R, T, D = 40, 5, 150, 12
-tri = np.stack([rng.integers(0, n, T), rng.integers(0, R, T), rng.integers(0, n, T)], 1)
-g = G.build_search_graph(n, R, tri)
-src, dst, _ = g.edges(form="all")
-node_id = torch.arange(n).view(-1, 1)
-samples = torch.from_numpy(np.stack([rng.integers(0, n, 300), rng.integers(0, 2 * R, 300), rng.integers(0, n, 300)], 1))
-labels = torch.from_numpy(rng.integers(0, 2, 300)).float()
-
-def run(handles):
-    LZ.ENABLED, LZ.FORCE_CPU, LZ.MIN_GATHER_ROWS = handles, handles, 1
-    torch.manual_seed(0)
-    net = MS.Network("cpu", n, R, 2, 1, 2, 2, D, 8, 2 * R + 1, 40.0, 0.0, 0.0)
-    net.train()
-    ent, rel = net(g, node_id, src, g.edata["e_type"])
-    seen = {"ent_is_tensor": type(ent) is torch.Tensor}
-    loss = net.get_loss(g, ent, rel, samples, labels)
-    loss.backward()
-    grads = {k: (p.grad.clone() if p.grad is not None else None) for k, p in net.named_parameters()}
-    return ent.detach(), rel.detach(), float(loss), grads, [a.grad.clone() for a in net.arch_parameters()[:4]], net, seen
-
-counts = {"lazy": 0, "materialised": 0}
-orig_init = LZ.Lazy.__init__
-def counting_init(self, node, shape, like):
-    counts["lazy"] += 1
-    orig_init(self, node, shape, like)
-LZ.Lazy.__init__ = counting_init
-h = run(True)
-made = counts["lazy"]
-e = run(False)
-assert counts["lazy"] == made, "eager run created handles"
-out = {"handles_created": made, "ent_equal": bool(torch.equal(h[0], e[0])), "rel_equal": bool(torch.equal(h[1], e[1])), "loss": [h[2], e[2]],
-       # relative to the tensor's largest entry, floored at 1e-3 of the largest gradient entry of the step (a bias in front of a BatchNorm
-       # has a gradient that is identically zero up to rounding: no relative scale of its own)
-       "grad_rel_diff": max([0.0] + [float((a - b).abs().max() / max(float(b.abs().max()), 1e-3 * max(float(v.abs().max()) for v in e[3].values() if v is not None)))
-                                     for (k, a), (_, b) in zip(sorted(h[3].items()), sorted(e[3].items())) if a is not None and b is not None]),
-       "grad_presence_equal": all((a is None) == (b is None) for (k, a), (_, b) in zip(sorted(h[3].items()), sorted(e[3].items()))),
-       "alpha_rel_diff": max(float((a - b).abs().max() / b.abs().max().clamp(min=1e-30)) for a, b in zip(h[4], e[4])),
-       "running_stats_equal": all(torch.equal(a, b) for a, b in zip(h[5].state_dict().values(), e[5].state_dict().values()))}
-print("RESULT " + json.dumps(out))
-'''
-
-
-@pytest.mark.skipif(not os.path.isdir(REF), reason="the reference is only present in the build container")
-def test_reference_callers_unchanged_drive_the_lazy_handles():
-    """models/cell_lp.py and models/model_search_lp.py AS THEY ARE, on an operator registry that hands out lazy handles (forced for CPU
-    tensors: lazy.FORCE_CPU; CPU restatements of the operators behind this package's forward / run protocol): the reference's own
-    lines -- nh.float(), the BatchNorm and ReLU modules, w * ., Python's sum over candidates and over MixedOps, states.append(s),
+def test_reference_callers_unchanged_drive_the_lazy_handles(monkeypatch):
+    """The reference caller's lines as this package restates them (supernet.SearchNetwork._forward_reference, cell_lp's literal
+    MixedOp / Cell: models/model_search_lp.py:131-176, models/cell_lp.py:25-33,95-152), on an operator registry that hands out lazy
+    handles (forced for CPU tensors: lazy.FORCE_CPU; CPU restatements of the operators behind this package's forward / run
+    protocol): nh.float(), the BatchNorm and ReLU modules, w * ., Python's sum over candidates and over MixedOps, states.append(s),
     torch.cat of the states, all_ent_emb[src_id_final], cat((ent_emb[src_in], ent_emb)), the three gathers of calc_score -- all go
-    through Lazy.__torch_function__; on the CPU every handle is evaluated literally, in the caller's own association, so outputs,
+    through Lazy.__torch_function__.  On the CPU every handle is evaluated literally, in the caller's own association, so outputs,
     loss and the BatchNorm running statistics must equal the eager run BIT FOR BIT; the gradients agree to float32 rounding (the
     autograd nodes are created in evaluation order, which is not the eager order, so the engine accumulates the gradients of a
-    tensor with several readers in another order).  (The fused evaluation of the same handles is the GPU tests'
-    subject: tests/test_nets_gpu.py::test_reference_caller_with_and_without_lazy_handles_matches_golden.)"""
-    r = subprocess.run([sys.executable, "-c", HANDLE_SCRIPT % {"root": ROOT}], capture_output=True, text=True, timeout=600,
-                       env={**os.environ, "MRG_GOLDEN_OUT": "/tmp/mrg_dropin_unused"})
-    assert r.returncode == 0, r.stderr[-3000:]
-    out = json.loads([l for l in r.stdout.splitlines() if l.startswith("RESULT ")][-1][len("RESULT "):])
-    assert out["handles_created"] > 200, out                     # 2 layers x 22 MixedOps x (op + bn + relu + term) + sums + gathers
-    assert out["ent_equal"] and out["rel_equal"] and out["loss"][0] == out["loss"][1], out
-    assert out["running_stats_equal"] and out["grad_presence_equal"], out
-    assert out["grad_rel_diff"] <= 2e-5 and out["alpha_rel_diff"] <= 2e-5, out
+    tensor with several readers in another order).  The eager run itself is held to the reference's unchanged Network on the same
+    parameters and inputs (dropin_caller.npz).  (The fused evaluation of the same handles is the GPU tests' subject:
+    tests/test_nets_gpu.py::test_reference_caller_with_and_without_lazy_handles_matches_golden.)"""
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import cpu_kernels as CK
+    from mr_gnas_amd import graph as G, lazy as LZ, supernet as S
+
+    z = load_golden("dropin_caller")
+    n, R, D = z["n"], z["R"], z["D"]
+    g = G.build_search_graph(n, R, z["tri"].numpy())
+    src, _, _ = g.edges(form="all")
+    node_id = torch.arange(n).view(-1, 1)
+
+    def run(handles):
+        monkeypatch.setattr(LZ, "ENABLED", handles)
+        monkeypatch.setattr(LZ, "FORCE_CPU", handles)
+        monkeypatch.setattr(LZ, "MIN_GATHER_ROWS", 1)
+        net = S.SearchNetwork("cpu", n, R, 2, 1, 2, 2, D, 8, 2 * R + 1, 40.0, 0.0, 0.0, registry=CK.wrapped_registry())
+        net.load_state_dict(sub(z, "param/"), strict=True)
+        net.load_alpha([z[f"alpha/{i}"] for i in range(len(net.arch_parameters()))])
+        net.train()
+        ent, rel = net._forward_reference(g, node_id, src, g.edata["e_type"])
+        loss = net.get_loss(g, ent, rel, z["samples"], z["labels"])
+        loss.backward()
+        grads = {k: (p.grad.clone() if p.grad is not None else None) for k, p in net.named_parameters()}
+        return LZ.real(ent).detach(), LZ.real(rel).detach(), float(loss.detach()), grads, [a.grad for a in net.arch_parameters()], net
+
+    counts = {"lazy": 0}
+    orig_init = LZ.Lazy.__init__
+
+    def counting_init(self, node, shape, like):
+        counts["lazy"] += 1
+        orig_init(self, node, shape, like)
+    monkeypatch.setattr(LZ.Lazy, "__init__", counting_init)
+    h = run(True)
+    made = counts["lazy"]
+    e = run(False)
+    assert counts["lazy"] == made, "eager run created handles"
+    assert made > 200, made                     # 2 layers x 22 MixedOps x (op + bn + relu + term) + sums + gathers
+    assert torch.equal(h[0], e[0]) and torch.equal(h[1], e[1]) and h[2] == e[2]
+    assert all(torch.equal(a, b) for a, b in zip(h[5].state_dict().values(), e[5].state_dict().values()))
+    assert all((a is None) == (b is None) for (_, a), (_, b) in zip(sorted(h[3].items()), sorted(e[3].items())))
+    # relative to the tensor's largest entry, floored at 1e-3 of the largest gradient entry of the step (a bias in front of a BatchNorm
+    # has a gradient that is identically zero up to rounding: no relative scale of its own)
+    floor = 1e-3 * max(float(v.abs().max()) for v in e[3].values() if v is not None)
+    for k, a in h[3].items():
+        if a is not None:
+            b = e[3][k]
+            assert float((a - b).abs().max()) <= 2e-5 * max(float(b.abs().max()), floor), k
+    for i in range(4):
+        assert float((h[4][i] - e[4][i]).abs().max()) <= 2e-5 * float(e[4][i].abs().max()), i
+
+    # the eager run against the reference's own Network on the same parameters and inputs
+    torch.testing.assert_close(e[0], z["ent"], rtol=1e-5, atol=1e-6)
+    torch.testing.assert_close(e[1], z["rel"], rtol=1e-5, atol=1e-6)
+    assert abs(e[2] - float(z["loss"])) <= 1e-5 * abs(float(z["loss"]))
+    ref_grads = sub(z, "gparam/")
+    assert sorted(ref_grads) == sorted(k for k, v in e[3].items() if v is not None)
+    for k, b in ref_grads.items():
+        assert float((e[3][k] - b).abs().max()) <= 2e-5 * max(float(b.abs().max()), floor), k
+    ref_alpha = sub(z, "galpha/")
+    assert sorted(ref_alpha) == [str(i) for i, a in enumerate(e[4]) if a is not None]
+    for i, b in ref_alpha.items():
+        assert float((e[4][int(i)] - b).abs().max()) <= 2e-5 * float(b.abs().max()), i
+    after = dict(e[5].named_buffers())
+    for k, b in sub(z, "state_after/").items():
+        torch.testing.assert_close(after[k], b, rtol=1e-5, atol=1e-6)
