@@ -34,7 +34,7 @@
 extern "C" {
 #endif
 
-#define MRG_ABI_VERSION 15   /* 15: mrg_gated_branch.valid_rows and the valid_rows argument of mrg_mix_finalize_bwd / mrg_zero_* except colstats (the device row count of a static step graph, passed per call instead of the process-wide registry of 13), mrg_linear_bwd_weight_share (the weight gradient of one range of a grouped launch, instead of the process-wide setter of 14); 14: mrg_clip_sgd_step, mrg_optim_chunk (clip_grad_norm_ + SGD with momentum over every parameter tensor in three launches), mrg_gated_branch.act (tanh behind the BatchNorm: CompGraphConv's tail on the epilogue kernels), mrg_gemm_set_small (few-row products on two-tile column blocks), a weight-gradient share setter, mrg_segmax_bwd_input (a_max's input gradient without a dense product); 13: a registry of device-side row counts (the sampled search step as one replayable HIP graph), mrg_seg_reduce_bwd_ordered (aggregator backward walked in destination order), mrg_gemm_set_q (the 16 x 16 x 32 row GEMM at three workgroups per CU for 129..224 output columns); 12: mrg_act_grad_transpose (the [B, N] scorer's output gradient, activation folded in, as [N, B] rows); 11: mrg_gemm_set_wide8 (eight-tile column block for D = 256); 10: mrg_gemm_set_epilogue(2) (transposed accumulators: a tested comparison point); 9: mrg_gated_branch (the MixedOp epilogue recomputes f_dense_comp's output from its gate and f_sparse_comp's from its row factor), mrg_gate_row_fwd / _bwd, mrg_sum_rows_gather, mrg_wgrad_set_variant, mrg_dense_filter_fwd3 out == NULL; 8: mrg_zero_* (cell-zero MixedOp recomputed from the tables), mrg_linear_bwd_input3_pair, mrg_sample_edge_neighborhood; 7: mrg_gemm_set_epilogue (row-order stores of the split-core row GEMM), mrg_set_stream_blocks, mrg_gemm_set_mode(2); 6: fused a_mean (run-sum epilogue, heads reducer, bit-mask backward), mrg_mix_stats_coef; 5: three-segment dense filter entry points; 4: mrg_linear_relu_segmax_fwd (fused a_max); 3: device graph / plan builders, samplers, [B, N] scorers, ranking; 2: GEMM workspaces, span_gcs ext_scal */
+#define MRG_ABI_VERSION 16   /* 16: mrg_set_stream_blocks, mrg_gate_collapse and mrg_gate_param_grad removed (the streaming grid bound is fixed; the three-segment forms remain); 15: mrg_gated_branch.valid_rows and the valid_rows argument of mrg_mix_finalize_bwd / mrg_zero_* except colstats (the device row count of a static step graph, passed per call instead of the process-wide registry of 13), mrg_linear_bwd_weight_share (the weight gradient of one range of a grouped launch, instead of the process-wide setter of 14); 14: mrg_clip_sgd_step, mrg_optim_chunk (clip_grad_norm_ + SGD with momentum over every parameter tensor in three launches), mrg_gated_branch.act (tanh behind the BatchNorm: CompGraphConv's tail on the epilogue kernels), mrg_gemm_set_small (few-row products on two-tile column blocks), a weight-gradient share setter, mrg_segmax_bwd_input (a_max's input gradient without a dense product); 13: a registry of device-side row counts (the sampled search step as one replayable HIP graph), mrg_seg_reduce_bwd_ordered (aggregator backward walked in destination order), mrg_gemm_set_q (the 16 x 16 x 32 row GEMM at three workgroups per CU for 129..224 output columns); 12: mrg_act_grad_transpose (the [B, N] scorer's output gradient, activation folded in, as [N, B] rows); 11: mrg_gemm_set_wide8 (eight-tile column block for D = 256); 10: mrg_gemm_set_epilogue(2) (transposed accumulators: a tested comparison point); 9: mrg_gated_branch (the MixedOp epilogue recomputes f_dense_comp's output from its gate and f_sparse_comp's from its row factor), mrg_gate_row_fwd / _bwd, mrg_sum_rows_gather, mrg_wgrad_set_variant, mrg_dense_filter_fwd3 out == NULL; 8: mrg_zero_* (cell-zero MixedOp recomputed from the tables), mrg_linear_bwd_input3_pair, mrg_sample_edge_neighborhood; 7: mrg_gemm_set_epilogue (row-order stores of the split-core row GEMM), mrg_set_stream_blocks, mrg_gemm_set_mode(2); 6: fused a_mean (run-sum epilogue, heads reducer, bit-mask backward), mrg_mix_stats_coef; 5: three-segment dense filter entry points; 4: mrg_linear_relu_segmax_fwd (fused a_max); 3: device graph / plan builders, samplers, [B, N] scorers, ranking; 2: GEMM workspaces, span_gcs ext_scal */
 
 #define MRG_OK            0
 #define MRG_E_NULLPTR    -1   /* a required pointer is NULL */
@@ -63,12 +63,6 @@ extern "C" {
 #define MRG_ACT_SIGMOID  2   /* the [B, N] score functions: sigmoid((sub * rel) all_ent^T) */
 
 int mrg_abi_version(void);
-/* Upper bound of the grid of the FLAT HBM-streaming kernels (compose, K-way sums, the MixedOp combine / statistics /
- * gradient-reduction passes; 256-thread blocks that walk the tensors with a grid stride).  Default 512: the fastest streaming
- * grid on MI355X (tools/stream_lab.hip: 5.9 TB/s, 2048 blocks 5.3).  64 <= blocks <= 4096 (the MixedOp reductions use at most
- * 1024).  The row-per-wave kernels (gates, gathers, reducers) are not affected.  Process-wide; a tuning knob, results do not
- * depend on it except for the summation order of the column reductions. */
-int mrg_set_stream_blocks(int blocks);
 const char *mrg_error_string(int code);
 /* Name of the code object's target, e.g. "gfx950". */
 const char *mrg_target_arch(void);
@@ -102,11 +96,11 @@ int mrg_gather_compose_fwd(int op, const float *ent, const float *rel,
  * a_x(W_x [s ; s_in] + b_x) has no non-linearity inside, so it equals
  * u_x . s + v_x . s_in + c_x with  [u_x ; v_x] = W_x^T a_x,  c_x = a_x . b_x.
  *
- * mrg_gate_collapse:   uvc[0 .. in_dim) = W^T a,  uvc[in_dim] = a . b
- *   W [D, in_dim] (nn.Linear weight), b [D] or NULL, a [D] (nn.Linear(D,1).weight). */
-int mrg_gate_collapse(const float *W, const float *b, const float *a, float *uvc,
-                      int D, int in_dim, void *stream);
-/* Batched forms over the three direction segments (in, out, self) of one operator -- one launch instead of three: *_host are
+ * mrg_gate_collapse3:   uvc[0 .. in_dim) = W^T a,  uvc[in_dim] = a . b
+ *   W [D, in_dim] (nn.Linear weight), b [D] or NULL, a [D] (nn.Linear(D,1).weight).
+ * mrg_gate_param_grad3: the chain rule back to the nn.Linear parameters,  d_uvc [in_dim+1] ->
+ *   gW [D, in_dim] = a (x) d_uv,  gb [D] = a * d_c (NULL ok),  ga [D] = W d_uv + b d_c.
+ * Both cover the three direction segments (in, out, self) of one operator in one launch: *_host are
  * HOST arrays of 3 device pointers, NULL for an absent segment; uvc / d_uvc are [3][MRG_GATE_LD(D)].
  * fold != 0 (both operands of the operator are the same rows, reference models/cell_lp.py:95-104: op(g, h_in, h_in)): the
  * parameters are nn.Linear(2D, D) but the gate is u.s + v.s = (u + v).s -- uvc holds u + v at [0, D) and c at index D
@@ -143,10 +137,6 @@ int mrg_gate_row_fwd(const float *s, const float *s_in, const float *norm, const
  * ws: mrg_gate_bwd_workspace_bytes(M, D). */
 int mrg_gate_row_bwd(const float *q, const float *hvec, const float *s, const float *s_in, const float *uvc, float *gs_in, float *d_uvc,
                      void *ws, int64_t b0, int64_t b1, int64_t M, int D, void *stream);
-/* chain rule back to the nn.Linear parameters:  d_uvc [in_dim+1] ->
- * gW [D, in_dim] = a (x) d_uv,  gb [D] = a * d_c (NULL ok),  ga [D] = W d_uv + b d_c. */
-int mrg_gate_param_grad(const float *W, const float *b, const float *a, const float *d_uvc,
-                        float *gW, float *gb, float *ga, int D, int in_dim, void *stream);
 
 /* ---- a4 / a5 / a6: destination-segmented reducers --------------------------
  * block.update_all(fn.copy_edge('msg_e','m'), fn.max|sum|mean('m','h')) + residual

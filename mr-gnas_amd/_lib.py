@@ -14,7 +14,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("MRG_LIB_PATH") or os.path.join(_HERE, "lib", "libmrgnas_hip.so")     # MRG_LIB_PATH: lab builds of the same ABI
 HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "mrgnas.h")
 
-ABI_VERSION = 15
+ABI_VERSION = 16
 
 
 class MrgnasLibraryError(RuntimeError):
@@ -30,13 +30,11 @@ _P, _I, _L, _F = ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_float
 # name -> (restype, argtypes); must list every function declared in include/mrgnas.h
 SIGNATURES = {
     "mrg_abi_version": (_I, []),
-    "mrg_set_stream_blocks": (_I, [_I]),
     "mrg_error_string": (ctypes.c_char_p, [_I]),
     "mrg_target_arch": (ctypes.c_char_p, []),
     "mrg_compose_fwd": (_I, [_I, _P, _P, _P, _L, _I, _P]),
     "mrg_compose_bwd": (_I, [_I, _P, _P, _P, _P, _P, _L, _I, _P]),
     "mrg_gather_compose_fwd": (_I, [_I, _P, _P, _P, _P, _P, _L, _I, _P]),
-    "mrg_gate_collapse": (_I, [_P, _P, _P, _P, _I, _I, _P]),
     "mrg_gate_collapse3": (_I, [_P, _P, _P, _P, _I, _I, _I, _P]),
     "mrg_gate_param_grad3": (_I, [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _P]),
     "mrg_fold_halves3": (_I, [_P, _P, _I, _P]),
@@ -44,7 +42,6 @@ SIGNATURES = {
     "mrg_gate_fwd": (_I, [_P, _P, _P, _P, _P, _L, _L, _L, _I, _F, _P]),
     "mrg_gate_bwd_workspace_bytes": (_L, [_L, _I]),
     "mrg_gate_bwd": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _L, _L, _L, _I, _F, _P]),
-    "mrg_gate_param_grad": (_I, [_P, _P, _P, _P, _P, _P, _P, _I, _I, _P]),
     "mrg_seg_reduce_workspace_bytes": (_L, [_L, _I]),
     "mrg_seg_reduce_fwd": (_I, [_I, _P, _P, _P, _P, _P, _P, _P, _L, _P, _P, _P, _L, _L, _P, _P, _P, _P, _L, _I, _P]),
     "mrg_seg_reduce_bwd": (_I, [_I, _P, _P, _P, _P, _P, _P, _P, _L, _L, _I, _P]),
@@ -147,13 +144,6 @@ def load():
         fn.restype, fn.argtypes = res, args
     if lib.mrg_abi_version() != ABI_VERSION:
         raise MrgnasLibraryError(f"ABI version {lib.mrg_abi_version()} != expected {ABI_VERSION}; rebuild the library")
-    if os.environ.get("MRG_STREAM_BLOCKS"):          # lab: grid bound of the streaming kernels (mrg_set_stream_blocks)
-        if lib.mrg_set_stream_blocks(int(os.environ["MRG_STREAM_BLOCKS"])) != 0:
-            raise MrgnasLibraryError("MRG_STREAM_BLOCKS must be 64..4096")
-    if os.environ.get("MRG_WGRAD_VARIANT"):          # lab: 0 = every wave splits the fragments it multiplies (mrg_wgrad_set_variant)
-        lib.mrg_wgrad_set_variant(int(os.environ["MRG_WGRAD_VARIANT"]))
-    if os.environ.get("MRG_GEMM_EPILOGUE"):          # lab: 0 = accumulator-order stores of the row GEMM (mrg_gemm_set_epilogue)
-        lib.mrg_gemm_set_epilogue(int(os.environ["MRG_GEMM_EPILOGUE"]))
     _lib = lib
     return lib
 

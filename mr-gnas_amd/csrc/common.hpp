@@ -204,11 +204,11 @@ inline void launch_ordered_reduce_ranges(const T* ws, T* out, const int* bounds,
 // In the supernet step (profiles/r3_stream_grid.txt): mrg_sum_buffers 4.90 -> 4.50 ms, mrg_mix_fwd 3.72 -> 3.47, statistics
 // 3.10 -> 2.95.  The row-per-wave kernels (gates, gathers, reducers' backward, mrg_mix_bwd_apply with its up to 14 address
 // streams) are latency-bound per wave and LOSE with fewer blocks (gate_fwd 1.4 -> 3.1 ms at 512): they keep grid_for.
-inline int& stream_blocks() { static int b = 512; return b; }
+constexpr int STREAM_BLOCKS = 512;
 inline int stream_grid_for(int64_t work_items, int items_per_block) {
   int64_t b = (work_items + items_per_block - 1) / items_per_block;
   if (b < 1) b = 1;
-  if (b > stream_blocks()) b = stream_blocks();
+  if (b > STREAM_BLOCKS) b = STREAM_BLOCKS;
   return (int)b;
 }
 

@@ -224,17 +224,17 @@ __global__ __launch_bounds__(MRG_BLOCK) void gcs_corr_k(const float* __restrict_
 // EIGHT consecutive outputs k0 .. k0+7: the register window is twelve values (w0 | w1 | wn), one step of four i still costs two
 // ds_read_b128 but feeds THIRTY-TWO multiply-adds.  A row needs D / 8 lanes, so a wave carries two chunks (LPR = 32).  Every output's
 // sum runs over i ascending as in gcs_corr_k; the two agree to rounding (3e-7: the compiler contracts the multiply-adds differently).
-// D % 8 == 0, D <= 256; MRG_CORR8=0 keeps the four-output kernel.
-template <int MODE, int OUT>
+// D % 8 == 0, 16 <= D <= 256.
+template <int MODE>
 __global__ __launch_bounds__(MRG_BLOCK) void gcs_corr8_k(const float* __restrict__ X, const int32_t* __restrict__ xi,
                                                          const float* __restrict__ Y, const int32_t* __restrict__ yi,
                                                          const float* __restrict__ scal, const int32_t* __restrict__ eid,
                                                          const int32_t* __restrict__ chunk_node, const int32_t* __restrict__ chunk_start,
                                                          const int32_t* __restrict__ chunk_end, const int32_t* __restrict__ chunk_slot,
                                                          int64_t n_chunks, float* __restrict__ out, float* __restrict__ ws_val, int D) {
-  // OUT outputs per lane (8 or 16): LPR = 256 / OUT lanes per row cover up to 256 outputs; the last lane of a row may own outputs
+  // OUT outputs per lane: LPR = 256 / OUT lanes per row cover up to 256 outputs; the last lane of a row may own outputs
   // beyond D (computed from the zero padding behind z | z, never stored)
-  constexpr int LPR = 256 / OUT, RPB = MRG_BLOCK / LPR;
+  constexpr int OUT = 8, LPR = 256 / OUT, RPB = MRG_BLOCK / LPR;
   constexpr int XW = 256, ZW = 2 * 256 + 32;               // x | z z + the window's read-ahead / the overhang of a partial last lane
   __shared__ __align__(16) float lds[RPB * (XW + ZW)];
   const int sl = threadIdx.x % LPR, rw = threadIdx.x / LPR;
@@ -325,9 +325,6 @@ __global__ __launch_bounds__(MRG_BLOCK) void gcs_corr8_k(const float* __restrict
 
 using namespace mrg;
 
-// lab switch: MRG_CORR8=0 keeps the four-outputs-per-lane kernel
-static int corr8_on() { static const int v = [] { const char* e = getenv("MRG_CORR8"); return e ? atoi(e) : 8; }(); return v; }
-
 extern "C" int mrg_fused_gcs(int mode, const float* X, const int32_t* xi, const float* Y, const int32_t* yi,
                              const float* scal, const int32_t* eid, const int32_t* chunk_node, const int32_t* chunk_start,
                              const int32_t* chunk_end, const int32_t* chunk_slot, int64_t n_chunks, const int32_t* hub_node,
@@ -345,8 +342,8 @@ extern "C" int mrg_fused_gcs(int mode, const float* X, const int32_t* xi, const 
   RowGeom g = row_geom(D, aligned16(X) && aligned16(Y) && aligned16(out) && aligned16(ws));
   if (!g.ok) return MRG_E_SHAPE;
   (void)needs_y;
-  // eight or sixteen outputs per lane (gcs_corr8_k; MRG_CORR8 = 0 / 8 / 16)
-  const int corr8 = (corr8_on() && g.vec == 4 && D <= 256 && D >= 16) ? (corr8_on() == 16 ? 16 : (D % 8 == 0 ? 8 : 0)) : 0;
+  // eight outputs per lane (gcs_corr8_k); gcs_corr_k takes the other shapes
+  const bool corr8 = g.vec == 4 && D >= 16 && D <= 256 && D % 8 == 0;
 #define LAUNCH(KERN, V, L, K, M)                                                                                       \
   hipLaunchKernelGGL((KERN<V, L, K, M>), dim3(grid), dim3(MRG_BLOCK), 0, st, X, xi, Y, yi, scal, eid, chunk_node,       \
                      chunk_start, chunk_end, chunk_slot, n_chunks, out, ws_val, D)
@@ -359,17 +356,13 @@ extern "C" int mrg_fused_gcs(int mode, const float* X, const int32_t* xi, const 
       case MRG_GCS_COPY: LAUNCH(gcs_k, V, L, K, MRG_GCS_COPY); break;                                                  \
       case MRG_GCS_NEGS: LAUNCH(gcs_k, V, L, K, MRG_GCS_NEGS); break;                                                  \
       case MRG_GCS_CCORR:                                                                                              \
-        if (corr8) { if (corr8 == 16) hipLaunchKernelGGL((gcs_corr8_k<MRG_GCS_CCORR, 16>), dim3(grid_for(n_chunks, MRG_BLOCK / 16)), dim3(MRG_BLOCK), 0, st, X, xi, Y, yi, scal, \
-                                        eid, chunk_node, chunk_start, chunk_end, chunk_slot, n_chunks, out, ws_val, D); \
-          else hipLaunchKernelGGL((gcs_corr8_k<MRG_GCS_CCORR, 8>), dim3(grid_for(n_chunks, MRG_BLOCK / 32)), dim3(MRG_BLOCK), 0, st, X, xi, Y, yi, scal, \
-                                        eid, chunk_node, chunk_start, chunk_end, chunk_slot, n_chunks, out, ws_val, D); }  \
+        if (corr8) hipLaunchKernelGGL((gcs_corr8_k<MRG_GCS_CCORR>), dim3(grid_for(n_chunks, MRG_BLOCK / 32)), dim3(MRG_BLOCK), 0, st, X, xi, Y, yi, scal, \
+                                      eid, chunk_node, chunk_start, chunk_end, chunk_slot, n_chunks, out, ws_val, D);     \
         else LAUNCH(gcs_corr_k, V, L, K, MRG_GCS_CCORR);                                                               \
         break;                                                                                                         \
       default:                                                                                                         \
-        if (corr8) { if (corr8 == 16) hipLaunchKernelGGL((gcs_corr8_k<MRG_GCS_CCONV, 16>), dim3(grid_for(n_chunks, MRG_BLOCK / 16)), dim3(MRG_BLOCK), 0, st, X, xi, Y, yi, scal, \
-                                        eid, chunk_node, chunk_start, chunk_end, chunk_slot, n_chunks, out, ws_val, D); \
-          else hipLaunchKernelGGL((gcs_corr8_k<MRG_GCS_CCONV, 8>), dim3(grid_for(n_chunks, MRG_BLOCK / 32)), dim3(MRG_BLOCK), 0, st, X, xi, Y, yi, scal, \
-                                        eid, chunk_node, chunk_start, chunk_end, chunk_slot, n_chunks, out, ws_val, D); }  \
+        if (corr8) hipLaunchKernelGGL((gcs_corr8_k<MRG_GCS_CCONV>), dim3(grid_for(n_chunks, MRG_BLOCK / 32)), dim3(MRG_BLOCK), 0, st, X, xi, Y, yi, scal, \
+                                      eid, chunk_node, chunk_start, chunk_end, chunk_slot, n_chunks, out, ws_val, D);     \
         else LAUNCH(gcs_corr_k, V, L, K, MRG_GCS_CCONV);                                                               \
         break;                                                                                                         \
     }                                                                                                                  \

@@ -13,13 +13,6 @@ struct SegPlan {
   int blk[4];             // blocks [blk[s], blk[s+1]) work on segment s
 };
 
-// rows in flight per lane group and trip of gate_fwd_k / gate_bwd_k when a wave owns a row (D > 128): 2 (default, round 5), 1 = rounds 1-4.
-// Lab override: environment MRG_GATE_RPT (read once).
-static int gate_rows_per_trip() {
-  static int v = [] { const char* e = getenv("MRG_GATE_RPT"); return e ? atoi(e) : 2; }();
-  return v;
-}
-
 static SegPlan make_plan(int64_t b0, int64_t b1, int64_t M, int grid) {
   SegPlan p;
   p.lo[0] = 0;  p.hi[0] = b0;
@@ -36,6 +29,9 @@ static SegPlan make_plan(int64_t b0, int64_t b1, int64_t M, int grid) {
   }
   return p;                                    // blk[3] <= grid
 }
+
+// rows in flight per lane group and trip of gate_fwd_k / gate_bwd_k: 2 when a wave owns a row (LPR = 64), else 1
+constexpr int gate_rpt(int lpr) { return lpr == 64 ? 2 : 1; }
 
 // RPT rows per trip and lane group (round 5): a trip is load -> dot -> group sum -> sigmoid -> scale -> store, one dependent chain per
 // row; with ONE row in flight per wave the C5 launches (D = 256: a wave per row) ran at 0.44 of the HBM peak with 39-55 % of the wave
@@ -366,54 +362,6 @@ __global__ void gate_reduce_k(const float* __restrict__ ws, float* __restrict__ 
   d_uvc[seg * ld + t] = (float)acc;
 }
 
-// uvc[k] = sum_j W[j,k] a[j]  (k < in_dim);  uvc[in_dim] = sum_j a[j] b[j].
-// 64 x 16 threads per 64 columns: thread row ty sums j = ty, ty+16, ... (coalesced along k).
-__global__ void gate_collapse_k(const float* __restrict__ W, const float* __restrict__ b, const float* __restrict__ a,
-                                float* __restrict__ uvc, int D, int in_dim) {
-  __shared__ float part[16][64];
-  const int tx = threadIdx.x & 63, ty = threadIdx.x >> 6;
-  const int k = blockIdx.x * 64 + tx;
-  float acc = 0.f;
-  if (k < in_dim) {
-    for (int j = ty; j < D; j += 16) acc += W[(int64_t)j * in_dim + k] * a[j];
-  } else if (k == in_dim && b) {
-    for (int j = ty; j < D; j += 16) acc += a[j] * b[j];
-  }
-  part[ty][tx] = acc;
-  __syncthreads();
-  if (ty == 0 && k <= in_dim) {
-    float tot = part[0][tx];
-#pragma unroll
-    for (int i = 1; i < 16; ++i) tot += part[i][tx];
-    uvc[k] = tot;
-  }
-}
-
-// one block per output row j of W
-__global__ void gate_param_grad_k(const float* __restrict__ W, const float* __restrict__ b, const float* __restrict__ a,
-                                  const float* __restrict__ d, float* __restrict__ gW, float* __restrict__ gb,
-                                  float* __restrict__ ga, int D, int in_dim) {
-  __shared__ float part[MRG_BLOCK / MRG_WAVE];
-  const int j = blockIdx.x;
-  const float aj = a[j];
-  float acc = 0.f;
-  for (int k = threadIdx.x; k < in_dim; k += blockDim.x) {
-    float dk = d[k];
-    gW[(int64_t)j * in_dim + k] = aj * dk;
-    acc += W[(int64_t)j * in_dim + k] * dk;
-  }
-  acc = group_sum<64>(acc);
-  if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = acc;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    float tot = 0.f;
-    for (int w = 0; w < MRG_BLOCK / MRG_WAVE; ++w) tot += part[w];
-    float dc = d[in_dim];
-    ga[j] = tot + (b ? b[j] * dc : 0.f);
-    if (gb) gb[j] = aj * dc;
-  }
-}
-
 }  // namespace mrg
 
 using namespace mrg;
@@ -503,23 +451,6 @@ __global__ void unfold_halves3_k(Ptr3 gWt, MPtr3 gW, int D) {
   }
 }
 
-extern "C" int mrg_gate_collapse(const float* W, const float* b, const float* a, float* uvc, int D, int in_dim, void* stream) {
-  if (!W || !a || !uvc) return MRG_E_NULLPTR;
-  if (D <= 0 || in_dim <= 0) return MRG_E_SHAPE;
-  hipLaunchKernelGGL(gate_collapse_k, dim3((in_dim + 1 + 63) / 64), dim3(1024), 0, (hipStream_t)stream, W, b, a, uvc, D, in_dim);
-  MRG_LAUNCH_CHECK();
-  return MRG_OK;
-}
-
-extern "C" int mrg_gate_param_grad(const float* W, const float* b, const float* a, const float* d_uvc, float* gW, float* gb,
-                                   float* ga, int D, int in_dim, void* stream) {
-  if (!W || !a || !d_uvc || !gW || !ga) return MRG_E_NULLPTR;
-  if (D <= 0 || in_dim <= 0) return MRG_E_SHAPE;
-  hipLaunchKernelGGL(gate_param_grad_k, dim3(D), dim3(MRG_BLOCK), 0, (hipStream_t)stream, W, b, a, d_uvc, gW, gb, ga, D, in_dim);
-  MRG_LAUNCH_CHECK();
-  return MRG_OK;
-}
-
 static Ptr3 ptr3(const float* const* h) { Ptr3 p; for (int i = 0; i < 3; ++i) p.p[i] = h ? h[i] : nullptr; return p; }
 static MPtr3 mptr3(float* const* h) { MPtr3 p; for (int i = 0; i < 3; ++i) p.p[i] = h ? h[i] : nullptr; return p; }
 
@@ -579,13 +510,8 @@ extern "C" int mrg_gate_fwd(const float* s, const float* s_in, const float* norm
     grid = grid_for(M, (MRG_BLOCK / L) * 4);                                                                                   \
     if (grid < 3) grid = 3;                                                                                             \
     SegPlan p = make_plan(b0, b1, M, grid);                                                                             \
-    if (gate_rows_per_trip() == 2 && L == 64) {                                                                          \
-      if (s_in) hipLaunchKernelGGL((gate_fwd_k<V, L, K, true, 2>), dim3(p.blk[3]), dim3(MRG_BLOCK), 0, st, s, s_in, norm, uvc, out, p, D, scale); \
-      else hipLaunchKernelGGL((gate_fwd_k<V, L, K, false, 2>), dim3(p.blk[3]), dim3(MRG_BLOCK), 0, st, s, s_in, norm, uvc, out, p, D, scale); \
-    } else {                                                                                                            \
-      if (s_in) hipLaunchKernelGGL((gate_fwd_k<V, L, K, true, 1>), dim3(p.blk[3]), dim3(MRG_BLOCK), 0, st, s, s_in, norm, uvc, out, p, D, scale); \
-      else hipLaunchKernelGGL((gate_fwd_k<V, L, K, false, 1>), dim3(p.blk[3]), dim3(MRG_BLOCK), 0, st, s, s_in, norm, uvc, out, p, D, scale); \
-    }                                                                                                                   \
+    if (s_in) hipLaunchKernelGGL((gate_fwd_k<V, L, K, true, gate_rpt(L)>), dim3(p.blk[3]), dim3(MRG_BLOCK), 0, st, s, s_in, norm, uvc, out, p, D, scale); \
+    else hipLaunchKernelGGL((gate_fwd_k<V, L, K, false, gate_rpt(L)>), dim3(p.blk[3]), dim3(MRG_BLOCK), 0, st, s, s_in, norm, uvc, out, p, D, scale); \
   } while (0)
   MRG_DISPATCH_GEOM(g, CALL);
 #undef CALL
@@ -617,13 +543,8 @@ extern "C" int mrg_gate_bwd(const float* gout, const float* s, const float* s_in
     if (grid < 3) grid = 3;                                                                                             \
     p = make_plan(b0, b1, M, grid);                                                                                     \
     if (M > 0) {                                                                                                        \
-      if (gate_rows_per_trip() == 2 && L == 64) {                                                                        \
-        if (s_in) hipLaunchKernelGGL((gate_bwd_k<V, L, K, true, 2>), dim3(p.blk[3]), dim3(MRG_BLOCK), 0, st, gout, s, s_in, norm, uvc, gs, gs_in, (float*)ws, p, D, scale); \
-        else hipLaunchKernelGGL((gate_bwd_k<V, L, K, false, 2>), dim3(p.blk[3]), dim3(MRG_BLOCK), 0, st, gout, s, s_in, norm, uvc, gs, gs_in, (float*)ws, p, D, scale); \
-      } else {                                                                                                          \
-        if (s_in) hipLaunchKernelGGL((gate_bwd_k<V, L, K, true, 1>), dim3(p.blk[3]), dim3(MRG_BLOCK), 0, st, gout, s, s_in, norm, uvc, gs, gs_in, (float*)ws, p, D, scale); \
-        else hipLaunchKernelGGL((gate_bwd_k<V, L, K, false, 1>), dim3(p.blk[3]), dim3(MRG_BLOCK), 0, st, gout, s, s_in, norm, uvc, gs, gs_in, (float*)ws, p, D, scale); \
-      }                                                                                                                 \
+      if (s_in) hipLaunchKernelGGL((gate_bwd_k<V, L, K, true, gate_rpt(L)>), dim3(p.blk[3]), dim3(MRG_BLOCK), 0, st, gout, s, s_in, norm, uvc, gs, gs_in, (float*)ws, p, D, scale); \
+      else hipLaunchKernelGGL((gate_bwd_k<V, L, K, false, gate_rpt(L)>), dim3(p.blk[3]), dim3(MRG_BLOCK), 0, st, gout, s, s_in, norm, uvc, gs, gs_in, (float*)ws, p, D, scale); \
     }                                                                                                                   \
   } while (0)
   MRG_DISPATCH_GEOM(g, CALL);

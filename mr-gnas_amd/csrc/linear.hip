@@ -749,7 +749,7 @@ struct WgradPlan {
 // ranges of 59 row blocks x 2 column blocks were 354 workgroups = 1.4 rounds of the chip, 46 us where one round of 23-tile blocks
 // takes 33.  A caller that launches the ranges one by one passes their number as mrg_linear_bwd_weight_share's `share`, to keep the
 // same partial sums.
-static int wgrad_share_max_blocks() { static const int v = [] { const char* e = getenv("MRG_WGRAD_SHARE_MAX"); return e ? atoi(e) : 400; }(); return v; }   // lab; measured: 15 000-row ranges -13 %, 87 000-row ranges (WN18RR) -10 %, 272 000-row ranges (1 063 blocks) +20 %
+constexpr int WGRAD_SHARE_MAX_BLOCKS = 400;   // largest range (row blocks of 16 tiles) that shares the chip; see wgrad_plan
 
 static WgradPlan wgrad_plan(int64_t rows, int K, int Nout, bool dma = false, int share = 1) {
   WgradPlan p{};
@@ -780,10 +780,9 @@ static WgradPlan wgrad_plan(int64_t rows, int K, int Nout, bool dma = false, int
   const int ny = (p.TN + (p.TM <= 4 ? 16 : 8) - 1) / (p.TM <= 4 ? 16 : 8);
   // (only up to 400 row blocks of 16 tiles per range: measured -13 % at 15 000-row ranges,
   //  -10 % at 87 000-row ranges, but +20 % at 272 000-row ranges, where three rounds of 128 shorter workgroups per range beat one round of long ones)
-  const bool shared = share > 1 && (tiles + 15) / 16 <= wgrad_share_max_blocks();
+  const bool shared = share > 1 && (tiles + 15) / 16 <= WGRAD_SHARE_MAX_BLOCKS;
   const int64_t gshare = 256 / (ny * share);
-  static const int gmul = [] { const char* e = getenv("MRG_WGRAD_GMUL"); return e ? atoi(e) : 1; }();      // lab: rounds of workgroups per range
-  const int64_t gmax = !shared ? ((256 / ny > 32 ? 256 / ny : 32) * gmul) : (gshare > 16 ? gshare : 16);
+  const int64_t gmax = !shared ? (256 / ny > 32 ? 256 / ny : 32) : (gshare > 16 ? gshare : 16);
   int64_t G = (tiles + 15) / 16 < gmax ? (tiles + 15) / 16 : gmax;
   // few rows (a sampled step graph, a rank's node chunk): a workgroup walks its 16-row tiles one barrier at a time (~2 us each), so
   // one or two workgroups of 16 tiles are a 30 us latency chain on an idle chip -- up to eight workgroups of >= 4 tiles instead
@@ -799,7 +798,7 @@ static WgradPlan wgrad_plan(int64_t rows, int K, int Nout, bool dma = false, int
   return p;
 }
 
-// Share-independent: a share above 1 only lowers gmax (256 / (ny * share) < 256 / ny, 16 < 32, the lab multiplier is >= 1), so G,
+// Share-independent: a share above 1 only lowers gmax (256 / (ny * share) < 256 / ny, 16 < 32), so G,
 // and with it the number of partial tiles, is at most the share-1 plan's -- that size bounds every share.
 int64_t wgrad_workspace_bytes(int64_t rows, int K, int Nout) {
   WgradPlan p = wgrad_plan(rows, K, Nout);

@@ -929,8 +929,6 @@ __global__ __launch_bounds__(MRG_BLOCK) void zero_bwd_apply_k(const float* __res
   }
 }
 
-static int lab_env_int(const char* name, int dflt) { const char* e = getenv(name); return e ? atoi(e) : dflt; }
-
 // ---- "static step graphs" (round 5): row counts that live in device memory ------------------------------------------------------
 // The reference's search loop draws a NEW step graph every step (search/mr_lp_search.py:187-214) whose node count depends on the
 // draw; to replay that step from ONE captured HIP graph every tensor must keep its shape, so the step graph is padded to a host-known
@@ -952,31 +950,14 @@ static int64_t row_blocks(int64_t rows, int lpr, int trips) {
   }
   return b < 1 ? 1 : b;
 }
-static int mix_grid(int64_t rows, int lpr) {
-  int64_t g = row_blocks(rows, lpr, 8);
-  if (g > stream_blocks()) g = stream_blocks();
-  return (int)(g > 1024 ? 1024 : g);               // partial buffers are sized for 1024 blocks
-}
+static int capped(int64_t blocks, int cap) { return (int)(blocks < cap ? blocks : cap); }
+static_assert(STREAM_BLOCKS <= 1024, "the statistics' partial buffers are sized for 1024 blocks");
+static int mix_grid(int64_t rows, int lpr) { return capped(row_blocks(rows, lpr, 8), STREAM_BLOCKS); }
 // backward reduction / combine: since the row addressing became scalar these kernels hold 4 / 8 workgroups per CU and gain from
 // more blocks than the 512 of the flat kernels (lab: 3.0 -> 2.4 ms and 2.53 -> 2.42 ms per step at 1024)
-static int mix_reduce_grid(int64_t rows, int lpr) {
-  static const int cap = lab_env_int("MRG_MIX_REDUCE_BLOCKS", 1024);
-  int64_t b = row_blocks(rows, lpr, 8);
-  const int c = cap > 1024 ? 1024 : (cap < 1 ? 1 : cap);              // partial buffers are sized for 1024 blocks
-  return (int)(b < 1 ? 1 : (b > c ? c : b));
-}
-static int mix_apply_grid(int64_t rows, int lpr) {
-  static const int cap = lab_env_int("MRG_MIX_APPLY_BLOCKS", MRG_MAX_GRID);
-  int64_t b = row_blocks(rows, lpr, 4);
-  const int c = cap > 8192 ? 8192 : (cap < 1 ? 1 : cap);
-  return (int)(b < 1 ? 1 : (b > c ? c : b));
-}
-static int mix_fwd_grid(int64_t rows, int lpr) {
-  static const int cap = lab_env_int("MRG_MIX_FWD_BLOCKS", 1024);
-  int64_t b = row_blocks(rows, lpr, 4);
-  const int c = cap > MRG_MAX_GRID ? MRG_MAX_GRID : (cap < 1 ? 1 : cap);
-  return (int)(b < 1 ? 1 : (b > c ? c : b));
-}
+static int mix_reduce_grid(int64_t rows, int lpr) { return capped(row_blocks(rows, lpr, 8), 1024); }   // partial buffers: 1024 blocks
+static int mix_apply_grid(int64_t rows, int lpr) { return capped(row_blocks(rows, lpr, 4), MRG_MAX_GRID); }
+static int mix_fwd_grid(int64_t rows, int lpr) { return capped(row_blocks(rows, lpr, 4), 1024); }
 
 static bool pack_ok(const void* const* host, int K) { return host != nullptr && K >= 1 && K <= MRG_MIX_MAXK; }
 

@@ -147,20 +147,17 @@ __global__ __launch_bounds__(MRG_BLOCK) void seg_bwd_k(const float* __restrict__
 // N * D / E of them (5.3) -- from a copy of W in LDS (D * K * 4 bytes <= 160 KB: D = K = 200 fills the CU's LDS exactly; one
 // 1024-thread workgroup per CU).  Order of the sum per output element: the won columns c ascending within j = c % 4, j = 0..3 --
 // deterministic; exact f32 FMAs (the dense product ran on the split core at f32-equivalent accuracy).
-template <bool WLDS, int THREADS>
-__global__ __launch_bounds__(THREADS) void segmax_bwd_gx_k(const float* __restrict__ gout, const float* __restrict__ mx,
-                                                         const int32_t* __restrict__ dst, const int32_t* __restrict__ arg,
-                                                         const float* __restrict__ W, float* __restrict__ gmsg, float* __restrict__ gx,
-                                                         const int32_t* __restrict__ order, int64_t E, int D, int Kin) {
+__global__ __launch_bounds__(1024) void segmax_bwd_gx_k(const float* __restrict__ gout, const float* __restrict__ mx,
+                                                      const int32_t* __restrict__ dst, const int32_t* __restrict__ arg,
+                                                      const float* __restrict__ W, float* __restrict__ gmsg, float* __restrict__ gx,
+                                                      const int32_t* __restrict__ order, int64_t E, int D, int Kin) {
   extern __shared__ __align__(16) float wl[];
+  constexpr int THREADS = 1024, WAVES = THREADS / 64;
   const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  constexpr int WAVES = THREADS / 64;
-  if constexpr (WLDS) {
-    const int n4 = D * Kin / 4;
-    for (int i = tid; i < n4; i += THREADS) reinterpret_cast<float4*>(wl)[i] = reinterpret_cast<const float4*>(W)[i];
-    __syncthreads();
-  }
-  const float* __restrict__ wsrc = WLDS ? wl : W;          // lab (MRG_SEGMAX_BWD_LDS=0): the rows of W from L2, four waves per block, no LDS
+  const int n4 = D * Kin / 4;
+  for (int i = tid; i < n4; i += THREADS) reinterpret_cast<float4*>(wl)[i] = reinterpret_cast<const float4*>(W)[i];
+  __syncthreads();
+  const float* __restrict__ wsrc = wl;                    // (reading wl itself compiles to narrower ds_read2 loads)
   const int dv = D >> 2, kv = Kin >> 2;
   const int64_t stride = (int64_t)gridDim.x * WAVES;
   // A wave's rows are a chain edge id -> destination -> three gathered table rows -> stores: ~2 us of dependent latency per edge with
@@ -235,18 +232,11 @@ extern "C" int mrg_segmax_bwd_input(const float* gout, const float* mx, const in
   if (E == 0) return MRG_OK;
   if (!gout || !dst || !arg || !W || !gx) return MRG_E_NULLPTR;
   if (!aligned16(gout) || !aligned16(arg) || !aligned16(W) || !aligned16(gx) || !aligned16(gmsg) || !aligned16(mx)) return MRG_E_SHAPE;
-  static const int use_lds = [] { const char* e = getenv("MRG_SEGMAX_BWD_LDS"); return e ? atoi(e) : 1; }();   // lab switch
-  if (use_lds) {
-    const size_t lds = (size_t)D * Kin * sizeof(float);
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&segmax_bwd_gx_k<true, 1024>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    int64_t grid = (E + 15) / 16;
-    if (grid > 256) grid = 256;                            // one 1024-thread workgroup (the whole LDS) per CU
-    hipLaunchKernelGGL((segmax_bwd_gx_k<true, 1024>), dim3((unsigned)grid), dim3(1024), lds, (hipStream_t)stream, gout, mx, dst, arg, W, gmsg, gx, order, E, D, Kin);
-  } else {
-    int64_t grid = (E + 3) / 4;
-    if (grid > 2048) grid = 2048;
-    hipLaunchKernelGGL((segmax_bwd_gx_k<false, 256>), dim3((unsigned)grid), dim3(256), 0, (hipStream_t)stream, gout, mx, dst, arg, W, gmsg, gx, order, E, D, Kin);
-  }
+  const size_t lds = (size_t)D * Kin * sizeof(float);
+  (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&segmax_bwd_gx_k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+  int64_t grid = (E + 15) / 16;
+  if (grid > 256) grid = 256;                              // one 1024-thread workgroup (the whole LDS) per CU
+  hipLaunchKernelGGL(segmax_bwd_gx_k, dim3((unsigned)grid), dim3(1024), lds, (hipStream_t)stream, gout, mx, dst, arg, W, gmsg, gx, order, E, D, Kin);
   MRG_LAUNCH_CHECK();
   return MRG_OK;
 }

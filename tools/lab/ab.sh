@@ -8,9 +8,9 @@
 # median / min per configuration printed; otherwise the lines matching --grep (default: all) are printed under each run.
 #
 # Examples (rounds 4 / 5):
-#   gate kernels one / two rows per trip, aggregator backward in edge / destination order, at the C5 and FB shapes:
-#     tools/lab/ab.sh stragglers --rounds 1 --grep '^gate|^seg' 'MRG_GATE_RPT=1 MRG_SEG_BWD_ORDERED=0' 'MRG_GATE_RPT=2 MRG_SEG_BWD_ORDERED=1' \
-#         -- python tools/kbench.py --shape c5 --only gate,seg --reps 7
+#   aggregator backward in edge / destination order, at the C5 and FB shapes:
+#     tools/lab/ab.sh stragglers --rounds 1 --grep '^seg' 'MRG_SEG_BWD_ORDERED=0' 'MRG_SEG_BWD_ORDERED=1' \
+#         -- python tools/kbench.py --shape c5 --only seg --reps 7
 #   three-waves-per-SIMD row GEMM against the two-wave kernel in the headline step:
 #     tools/lab/ab.sh q 'MRG_GEMM_Q=0' 'MRG_GEMM_Q=1' -- --steps 10 --warmup 3 --no-cpu-baseline
 set -u
