@@ -3,15 +3,19 @@
 (forward + loss + backward + clip + SGD) per "step", FB15k-237-shaped synthetic
 KG, feature_dim = 200 (BASELINE.json config 2).
 
-    python bench.py --gpus 1 --steps 5 --warmup 2
+    python bench.py --gpus 1 --steps 5 --warmup 2 [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 Rank 0 prints ONE JSON line.  `value` = million directed edges of the step graph
 processed per second (E / t_step / 1e6), inputs resident in HBM before timing.
-`roofline` prices the libmrgnas kernel with the largest device time in the timed
-steps (HIP events on the launch stream); `kernels` lists every libmrgnas entry
-point of one instrumented step; `cpu_baseline` times the CPU oracle on a bounded
-sample of the same workload on this host's cores.
+`roofline` prices the libmrgnas kernel family with the largest device time in the
+instrumented step that runs before the timed ones (HIP events on the launch
+stream); `kernels` lists every libmrgnas entry point of that step.
+
+A plain run stops there.  `--full` adds what takes runs of its own after the timed
+steps: the eager leg of a captured sharded step, the exact-f32 and reference-caller
+legs, the north-star kernel passes and `cpu_baseline` (the CPU oracle on this
+host's cores, one full-graph step included: over a minute).
 """
 import argparse
 import json
@@ -108,21 +112,21 @@ def parse():
                          "nn.BatchNorm1d, ReLU and a scaled add per candidate; gathers materialised as models/model_search_lp.py:144-145) "
                          "on this package's operators -- what the UNCHANGED reference caller gets from the operator swap alone")
     ap.add_argument("--comp-fn", default="sub", choices=["sub", "mul", "ccorr"], help="compgcn_fb15k237: the layer's composition")
-    ap.add_argument("--no-caller-leg", action="store_true", help="skip the extra timed steps with the reference's literal caller")
+    ap.add_argument("--no-caller-leg", action="store_true", help="--full: skip the extra timed steps with the reference's literal caller")
     ap.add_argument("--dim", type=int, default=200)
     ap.add_argument("--negative", type=int, default=10)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
     ap.add_argument("--hip-graph", action="store_true",
                     help="capture one whole step in a HIP graph and time K replays (launch-bound small step graphs; "
                          "the per-kernel events of the roofline then come from the instrumented eager step)")
     ap.add_argument("--exact-f32", action="store_true",
                     help="run every GEMM on the exact-f32 MFMA core (mrg_gemm_set_mode(1)) instead of the split-bf16 core")
-    ap.add_argument("--cpu-sample", type=int, default=30000, help="graph_batch_size of the CPU-baseline sample")
+    ap.add_argument("--cpu-sample", type=int, default=30000, help="--full: graph_batch_size of the CPU-baseline sample")
     ap.add_argument("--cpu-full-graph", type=int, default=1,
-                    help="1 (default): cpu_baseline.value = ONE step of the CPU oracle on the headline (full-graph) workload itself, "
+                    help="--full, 1 (default): cpu_baseline.value = ONE step of the CPU oracle on the headline (full-graph) workload itself, "
                          "timed in this run (~75 s, ~71 GB of host memory); 0: the bounded sample only")
-    ap.add_argument("--no-c5", action="store_true", help="skip the north-star kernel pass at the C5 shape (10 M edges, D = 256)")
-    ap.add_argument("--no-exact-f32-leg", action="store_true", help="skip the extra timed steps on the exact-f32 matrix core")
+    ap.add_argument("--no-c5", action="store_true", help="--full: skip the north-star kernel pass at the C5 shape (10 M edges, D = 256)")
+    ap.add_argument("--no-exact-f32-leg", action="store_true", help="--full: skip the extra timed steps on the exact-f32 matrix core")
     ap.add_argument("--resample", action="store_true",
                     help="sampled workloads only: draw a NEW step graph inside every timed step (device sampler, negative "
                          "sampling, graph build, index plans: reference search/mr_lp_search.py:187-214), so `value` pays for it")
@@ -139,6 +143,10 @@ def parse():
                          "launch of the real run on a one-rank RCCL communicator; the other ranks' contributions are zeros)")
     ap.add_argument("--no-shard-graph", action="store_true", help="N > 1 with --comm direct: do not capture the sharded step in a HIP graph")
     ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also run the extra legs and passes (eager leg of a captured "
+                         "sharded step, exact-f32 leg, reference-caller legs, north-star kernel passes, CPU baseline); a plain run "
+                         "prints its line right after the timed steps")
     ap.add_argument("--dump-outputs", default=None, metavar="DIR",
                     help="after the timed steps, write what their last step handed its caller (loss, forward outputs, the updated "
                          "parameters and buffers) as DIR/<name>.npy in float32 / float64, at most 64 MB in all")
@@ -835,7 +843,7 @@ def main():
         log(f"last timed step's outputs: {files} arrays, {nbytes / 2**20:.1f} MB in {args.dump_outputs}")
 
     eager_ms = None
-    if sharded and launch_mode != "eager":
+    if args.full and sharded and launch_mode != "eager":
         # the same K steps launched eagerly, so that the record carries BOTH launch modes (advisor r4: the single-GPU default is
         # eager, the sharded default replays a captured step; the N = 1 step is device-bound -- replayed 50.2 vs eager 49.9 ms,
         # DESIGN.md section 5 -- so `value` at N = 1 does not depend on the mode, at N > 1 it does)
@@ -946,7 +954,8 @@ def main():
         out["config"]["rank_edges"] = int(step.E)
         out["value"] = None
         out["rehearsal_ms_per_step"] = round(ms_per_step, 3)
-    if world == 1 and not sharded and not args.exact_f32 and not args.no_exact_f32_leg and not args.hip_graph and not fixed:
+    # ---- --full only: the legs and passes below take runs of their own; a plain run prints `out` as it stands here
+    if args.full and world == 1 and not sharded and not args.exact_f32 and not args.no_exact_f32_leg and not args.hip_graph and not fixed:
         # the same step with every GEMM on the exact-f32 MFMA pipe (v_mfma_f32_32x32x2_f32), next to the headline number
         lib.mrg_gemm_set_mode(1)
         step()
@@ -959,7 +968,7 @@ def main():
         lib.mrg_gemm_set_mode(0)
         out["exact_f32"] = {"ms_per_step": round(ms, 3), "value": round(E_total / ms / 1e3, 4), "unit": "M edges/s",
                             "matrix_core": "exact f32 MFMA (v_mfma_f32_32x32x2_f32) for every GEMM"}
-    if (world == 1 and not sharded and not fixed and args.caller == "fused" and not args.no_caller_leg and not args.hip_graph
+    if (args.full and world == 1 and not sharded and not fixed and args.caller == "fused" and not args.no_caller_leg and not args.hip_graph
             and not args.resample):
         # the same step through the reference's literal caller formulation (supernet.SearchNetwork._forward_reference / calc_score: the
         # reference's own lines of models/model_search_lp.py:131-176 and models/cell_lp.py:25-33,95-152 on this package's operators):
@@ -991,7 +1000,7 @@ def main():
             torch.cuda.empty_cache()
         LZ.ENABLED = lazy_was
         CL.CALLER = "fused"
-    if world == 1 and not sharded and args.workload not in ("c5_fixed_cell", "compgcn_fb15k237"):
+    if args.full and world == 1 and not sharded and args.workload not in ("c5_fixed_cell", "compgcn_fb15k237"):
         log("timing the fused compose+scatter kernel (north-star kernel) on the benchmark graph")
         out["north_star_kernel"] = north_star_kernel(step.g, args.dim, tag=args.workload.split("_")[0])
         if not args.no_c5:
@@ -999,7 +1008,7 @@ def main():
             if free_b > 60 * 2**30:
                 log("... and at the C5 shape (10 M edges, 1 M nodes, D = 256)")
                 out["north_star_kernel_c5"] = north_star_c5(device)
-    if rank == 0 and world == 1 and not args.no_cpu_baseline and not fixed:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline and not fixed:
         state = step.model.state_dict()
         log("timing the CPU oracle (bounded sample, then one full-graph step)")
         out["cpu_baseline"] = cpu_baseline(args, state, step.model.arch_parameters(), step_inputs)

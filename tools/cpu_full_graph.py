@@ -1,8 +1,8 @@
 #!/usr/bin/env python3
 """ONE full-graph supernet step (forward + DistMult BCE + backward) of the CPU oracle on this host's cores: the CPU figure for
 the very workload bench.py's headline is quoted on (fb15k237_supernet_full, E = 544 230, D = 200).  Takes minutes and ~64 GB
-of RAM, so it is recorded once per round (profiles/rN_cpu_full_graph.json) and carried by bench.py as cpu_baseline.full_graph
-instead of being re-run by every default bench invocation.
+of RAM, so it is recorded once per round (profiles/rN_cpu_full_graph.json) and carried by bench.py --full as
+cpu_baseline.full_graph when that run does not time the step itself (--cpu-full-graph 0, too little host memory).
 
     python tools/cpu_full_graph.py [--out gpurun_out/cpu_full_graph.json] [--dim 200]
 """

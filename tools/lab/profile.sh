@@ -11,8 +11,9 @@
 #   sq       the SQ counters (MFMA busy, wave cycles, waits, LDS conflicts): tools/pmc_sq.sh      -> sq_summary.txt
 #   census   kernels per step by name (calls / step, average, ms / step) from the stats CSV (needs the stats pass in the same call)
 #
-# The stats passes run the flags as given (default: bench.py's own defaults, CPU baseline included, extra legs off); the counter
-# passes add --steps 1 --warmup 1 --no-cpu-baseline.
+# Every pass runs bench.py --full (the north-star passes and the traffic calibration launch are --full legs).  The stats passes run
+# the flags as given (default: bench.py's own defaults, CPU baseline included, extra legs off); the counter passes add --steps 1
+# --warmup 1 --no-cpu-baseline.
 # Examples: the round's profile set     tools/lab/profile.sh r5prof stats,stats1,traffic,sq
 #           C5                          tools/lab/profile.sh r5prof_c5 stats,sq --workload c5_fixed_cell
 #           the replayed sampled step   tools/lab/profile.sh r5static stats,census --workload fb15k237_supernet_300 --resample --static-step --hip-graph --steps 50 --warmup 5 --no-cpu-baseline
@@ -21,7 +22,7 @@ R=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/../.." && pwd)}
 TAG=$1; PASSES=$2; shift 2
 O=$R/gpurun_out/$TAG; mkdir -p "$O"
 cd /tmp && export TMPDIR=/tmp
-LEGS="--no-exact-f32-leg --no-caller-leg"
+LEGS="--full --no-exact-f32-leg --no-caller-leg"
 has() { case ",$PASSES," in *",$1,"*) return 0;; esac; return 1; }
 if has stats; then
   rm -rf /tmp/prof_a

@@ -5,10 +5,10 @@ R=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}
 TAG=$1; PAT=$2; shift 2
 O=$R/gpurun_out/$TAG; mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
-rm -rf /tmp/tk
+rm -rf "$TMPDIR/tk"
 if [ "${STREAMS:-single}" = single ]; then export MRG_MIXED_STREAMS=1 MRG_SEGMENT_STREAMS=1; fi
-rocprofv3 --kernel-trace --output-format csv -d /tmp/tk -- python3 $R/bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-exact-f32-leg --no-c5 "$@" > $O/bench.json 2> $O/bench.err || exit 1
-f=$(find /tmp/tk -name "*kernel_trace.csv" | head -1)
+rocprofv3 --kernel-trace --output-format csv -d "$TMPDIR/tk" -- python3 $R/bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --no-exact-f32-leg --no-c5 "$@" > $O/bench.json 2> $O/bench.err || exit 1
+f=$(find "$TMPDIR/tk" -name "*kernel_trace.csv" | head -1)
 python3 - "$f" "$PAT" > $O/trace.txt <<'PY'
 import csv, re, sys
 rows = list(csv.DictReader(open(sys.argv[1])))

@@ -106,7 +106,7 @@ def main():
         kern[key] = {"dispatches": len(fetch.get(key, write.get(key, []))), "fetch_bytes": int(fb), "write_bytes": int(wb),
                      "bytes_per_dispatch": int(fb + wb)}
     res = {"source": "rocprofv3 --pmc FETCH_SIZE and --pmc WRITE_SIZE (separate passes, with --kernel-trace) over "
-                     "`python3 bench.py --steps 1 --warmup 1 --no-cpu-baseline`",
+                     "`python3 bench.py --full --steps 1 --warmup 1 --no-cpu-baseline`",
            "correction": "bytes = 2 * FETCH_SIZE * 1024 + WRITE_SIZE * 1024 per dispatch (MI355X_MICROARCH.md: counters in KiB; "
                          "gfx950 FETCH_SIZE tallies 128-B requests as 64 B)",
            "note": "FETCH_SIZE counts requests that leave L2, Infinity-Cache hits included: it is an upper bound of DRAM reads",
@@ -139,7 +139,7 @@ def main():
         if len(ns) > 1:
             res["per_launch_bytes"]["north_star:c5_synthetic10m"] = kern[ns[-1]]["bytes_per_dispatch"]
     # HBM-side bytes of ONE step: every dispatch of the profiled command except the north-star / calibration passes, divided by the
-    # number of steps it ran (bench.py --steps 1 --warmup 1: warm-up + instrumented + timed = 3)
+    # number of steps it ran (bench.py --full --steps 1 --warmup 1: warm-up + instrumented + timed = 3)
     steps = int(sys.argv[6]) if len(sys.argv) >= 7 else 3
     skip = (NORTH_STAR, "compose_fwd_k")
     tot = sum(v["bytes_per_dispatch"] * v["dispatches"] for (name, grid), v in kern.items() if not any(x in name for x in skip))
