@@ -34,7 +34,7 @@
 extern "C" {
 #endif
 
-#define MRG_ABI_VERSION 16   /* 16: mrg_set_stream_blocks, mrg_gate_collapse and mrg_gate_param_grad removed (the streaming grid bound is fixed; the three-segment forms remain); 15: mrg_gated_branch.valid_rows and the valid_rows argument of mrg_mix_finalize_bwd / mrg_zero_* except colstats (the device row count of a static step graph, passed per call instead of the process-wide registry of 13), mrg_linear_bwd_weight_share (the weight gradient of one range of a grouped launch, instead of the process-wide setter of 14); 14: mrg_clip_sgd_step, mrg_optim_chunk (clip_grad_norm_ + SGD with momentum over every parameter tensor in three launches), mrg_gated_branch.act (tanh behind the BatchNorm: CompGraphConv's tail on the epilogue kernels), mrg_gemm_set_small (few-row products on two-tile column blocks), a weight-gradient share setter, mrg_segmax_bwd_input (a_max's input gradient without a dense product); 13: a registry of device-side row counts (the sampled search step as one replayable HIP graph), mrg_seg_reduce_bwd_ordered (aggregator backward walked in destination order), mrg_gemm_set_q (the 16 x 16 x 32 row GEMM at three workgroups per CU for 129..224 output columns); 12: mrg_act_grad_transpose (the [B, N] scorer's output gradient, activation folded in, as [N, B] rows); 11: mrg_gemm_set_wide8 (eight-tile column block for D = 256); 10: mrg_gemm_set_epilogue(2) (transposed accumulators: a tested comparison point); 9: mrg_gated_branch (the MixedOp epilogue recomputes f_dense_comp's output from its gate and f_sparse_comp's from its row factor), mrg_gate_row_fwd / _bwd, mrg_sum_rows_gather, mrg_wgrad_set_variant, mrg_dense_filter_fwd3 out == NULL; 8: mrg_zero_* (cell-zero MixedOp recomputed from the tables), mrg_linear_bwd_input3_pair, mrg_sample_edge_neighborhood; 7: mrg_gemm_set_epilogue (row-order stores of the split-core row GEMM), mrg_set_stream_blocks, mrg_gemm_set_mode(2); 6: fused a_mean (run-sum epilogue, heads reducer, bit-mask backward), mrg_mix_stats_coef; 5: three-segment dense filter entry points; 4: mrg_linear_relu_segmax_fwd (fused a_max); 3: device graph / plan builders, samplers, [B, N] scorers, ranking; 2: GEMM workspaces, span_gcs ext_scal */
+#define MRG_ABI_VERSION 17   /* 17: mrg_ccorr_rows, mrg_ccorr_matrix, mrg_ccorr_matrix_grad (standalone circular correlation: per-row kernel, and the circulant of a shared row with its gradient fold for the row GEMM); 16: mrg_set_stream_blocks, mrg_gate_collapse and mrg_gate_param_grad removed (the streaming grid bound is fixed; the three-segment forms remain); 15: mrg_gated_branch.valid_rows and the valid_rows argument of mrg_mix_finalize_bwd / mrg_zero_* except colstats (the device row count of a static step graph, passed per call instead of the process-wide registry of 13), mrg_linear_bwd_weight_share (the weight gradient of one range of a grouped launch, instead of the process-wide setter of 14); 14: mrg_clip_sgd_step, mrg_optim_chunk (clip_grad_norm_ + SGD with momentum over every parameter tensor in three launches), mrg_gated_branch.act (tanh behind the BatchNorm: CompGraphConv's tail on the epilogue kernels), mrg_gemm_set_small (few-row products on two-tile column blocks), a weight-gradient share setter, mrg_segmax_bwd_input (a_max's input gradient without a dense product); 13: a registry of device-side row counts (the sampled search step as one replayable HIP graph), mrg_seg_reduce_bwd_ordered (aggregator backward walked in destination order), mrg_gemm_set_q (the 16 x 16 x 32 row GEMM at three workgroups per CU for 129..224 output columns); 12: mrg_act_grad_transpose (the [B, N] scorer's output gradient, activation folded in, as [N, B] rows); 11: mrg_gemm_set_wide8 (eight-tile column block for D = 256); 10: mrg_gemm_set_epilogue(2) (transposed accumulators: a tested comparison point); 9: mrg_gated_branch (the MixedOp epilogue recomputes f_dense_comp's output from its gate and f_sparse_comp's from its row factor), mrg_gate_row_fwd / _bwd, mrg_sum_rows_gather, mrg_wgrad_set_variant, mrg_dense_filter_fwd3 out == NULL; 8: mrg_zero_* (cell-zero MixedOp recomputed from the tables), mrg_linear_bwd_input3_pair, mrg_sample_edge_neighborhood; 7: mrg_gemm_set_epilogue (row-order stores of the split-core row GEMM), mrg_set_stream_blocks, mrg_gemm_set_mode(2); 6: fused a_mean (run-sum epilogue, heads reducer, bit-mask backward), mrg_mix_stats_coef; 5: three-segment dense filter entry points; 4: mrg_linear_relu_segmax_fwd (fused a_max); 3: device graph / plan builders, samplers, [B, N] scorers, ranking; 2: GEMM workspaces, span_gcs ext_scal */
 
 #define MRG_OK            0
 #define MRG_E_NULLPTR    -1   /* a required pointer is NULL */
@@ -640,6 +640,26 @@ int mrg_transe_score_fwd(const float *ent, const float *sub, const float *rel, f
                          int64_t B, int64_t N, int D, void *stream);
 int mrg_transe_score_bwd(const float *ent, const float *sub, const float *rel, const float *gscore, const float *score,
                          float *gent, float *gobj, int64_t B, int64_t N, int D, void *stream);
+/* ---- standalone circular correlation (ABI 17) ---------------------------------------------------------
+ * ccorr(a, b) of reference utils/utils.py:285-301 and models/operations_lp.py:58-68 (pre_corr_op), which the reference
+ * computes as irfft(conj(rfft(a)) * rfft(b)).  Rows of width 1 <= D <= MRG_CCORR_MAX_D, float32, row-major [N][D].
+ * mrg_ccorr_rows: out[i] = corr(X[i], Y[i])  (MRG_CCORR: out[k] = sum_j X[j] Y[(j + k) % D])  or conv(X[i], Y[i])
+ *   (MRG_CCONV: out[m] = sum_j X[j] Y[(m - j) % D]).  dL/da = corr(g, b), dL/db = conv(a, g).  N = 0 launches nothing.
+ *   Sums over j ascending per output: bit-reproducible.
+ * A row r shared by every row of the other operand makes ccorr a row GEMM (mrg_linear_fwd with W = the D x D circulant):
+ * mrg_ccorr_matrix writes W[k][j] = r[(j + k) % D] (MRG_CCORR_H: ccorr(a, r) = a W^T) or W[k][m] = r[(m - k) % D]
+ *   (MRG_CCORR_T: ccorr(r, b) = b W^T);
+ * mrg_ccorr_matrix_grad folds the weight gradient gW [D][D] of that product onto gr [D]: gr[m] = sum_k gW[k][(m - k) % D] (H)
+ *   or sum_k gW[k][(k + m) % D] (T), in a fixed order (no atomics).  W and gW are [D][D], not aliased with r / gr. */
+#define MRG_CCORR_MAX_D 512
+#define MRG_CCORR        0
+#define MRG_CCONV        1
+#define MRG_CCORR_H      0
+#define MRG_CCORR_T      1
+int mrg_ccorr_rows(int mode, const float *X, const float *Y, float *out, int64_t N, int D, void *stream);
+int mrg_ccorr_matrix(int mode, const float *r, float *W, int D, void *stream);
+int mrg_ccorr_matrix_grad(int mode, const float *gW, float *gr, int D, void *stream);
+
 /* gT[n][b] = g[b][n] * act'(y[b][n]): the output gradient of a wide, short Linear (the [B, N] scorers: N = all entities) with the
  * activation's derivative folded in, transposed to [N][B] rows -- the layout both of its gradient products stream
  * (functional._Linear.backward; replaces torch's mul / rsub / mul / strided copy).  act: MRG_ACT_NONE (y may be NULL) / _RELU /

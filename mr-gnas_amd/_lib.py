@@ -14,7 +14,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("MRG_LIB_PATH") or os.path.join(_HERE, "lib", "libmrgnas_hip.so")     # MRG_LIB_PATH: lab builds of the same ABI
 HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "mrgnas.h")
 
-ABI_VERSION = 16
+ABI_VERSION = 17
 
 
 class MrgnasLibraryError(RuntimeError):
@@ -117,6 +117,9 @@ SIGNATURES = {
     "mrg_rank_filtered": (_I, [_P, _P, _P, _L, _L, _P, _P]),
     "mrg_transe_score_fwd": (_I, [_P, _P, _P, _F, _P, _L, _L, _I, _P]),
     "mrg_transe_score_bwd": (_I, [_P, _P, _P, _P, _P, _P, _P, _L, _L, _I, _P]),
+    "mrg_ccorr_rows": (_I, [_I, _P, _P, _P, _L, _I, _P]),
+    "mrg_ccorr_matrix": (_I, [_I, _P, _P, _I, _P]),
+    "mrg_ccorr_matrix_grad": (_I, [_I, _P, _P, _I, _P]),
 }
 
 _lib = None

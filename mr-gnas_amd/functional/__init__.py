@@ -19,6 +19,7 @@ This package re-exports every name of its modules, so callers keep writing ``fro
   mixed       X: the MixedOp epilogue  out = sum_k w_k * ReLU(BatchNorm_k(y_k))  (csrc/mixedop.hip).
   cell_zero   Cell zero: the MixedOp over the compose candidates, recomputed from the entity / relation tables (csrc/mixedop.hip zero_*).
   scoring     The step after the path: DistMult triple scoring and the [B, N] score functions (csrc/scoring.hip).
+  ccorr       Standalone circular correlation ccorr(a, b): per-row kernel, or a shared row's circulant on the row GEMM (csrc/ccorr.hip).
 """
 from . import switches                                   # noqa: F401
 from ._base import (  # noqa: F401
@@ -60,5 +61,8 @@ from .cell_zero import (  # noqa: F401
 )
 from .scoring import (  # noqa: F401
     ScorePlan, _DistMult, distmult_score, distmult_scores_all, _TransE, transe_scores_all,
+)
+from .ccorr import (  # noqa: F401
+    _CCorrRows, _Circulant, ccorr,
 )
 from .._lib import ptr_array, call, f32c, ptr, require_hip, stream_of   # noqa: F401  (part of the module's historical surface)

@@ -1,5 +1,5 @@
 """Lab switches of the autograd layer (each names its environment variable): the shipped defaults are the measured winners;
-the other setting of every switch is a tested comparison point (tests/, tools/).  ``MASK_TAP`` is test instrumentation."""
+the other setting of every switch is a tested comparison point (tests/, tools/).  ``MASK_TAP`` (test instrumentation) and ``CCORR_PATH`` are plain attributes."""
 import os
 
 ROW_FACTOR = os.environ.get("MRG_ROW_FACTOR", "1") == "1"     # lab switch: 0 = f_sparse_comp's output is stored for the epilogue
@@ -26,3 +26,6 @@ DENSE_PAIR = os.environ.get("MRG_DENSE_PAIR", "1") == "1"       # lab switch: 0 
 GATED_RECOMPUTE = os.environ.get("MRG_GATED_RECOMPUTE", "1") == "1"     # lab switch: 0 = f_dense_comp's output is stored for the epilogue
 COMPGCN_TAIL = os.environ.get("MRG_COMPGCN_TAIL", "1") == "1"     # lab switch: 0 = CompGraphConv's BatchNorm -> tanh tail on torch kernels
 SPARSE_AMAX_BWD = os.environ.get("MRG_SPARSE_AMAX_BWD", "1") == "1"   # lab switch: 0 = a_max's input gradient as seg_bwd_k + the dense row GEMM
+# ccorr (functional/ccorr.py): None = a shared row takes the matrix path from ccorr.MATRIX_MIN_ROWS rows on; "rows" / "matrix" force
+# one path wherever the matrix path applies (tests cross-check the two with monkeypatch.setattr).  A plain attribute, no variable.
+CCORR_PATH = None

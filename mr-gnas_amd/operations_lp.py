@@ -76,6 +76,32 @@ class pre_add_op(_PreOp):
     kind = "add"
 
 
+def _rows_now(x):
+    """A lazy handle or the cell's gathered LazyRows as a real tensor."""
+    return x.materialize() if isinstance(x, K.LazyRows) else LZ.real(x)
+
+
+# ---- circular correlation (reference :58-68; not in MIXED_OPS / PRE_OPS there either) ------------------------------------------
+ccorr = K.ccorr
+
+
+class pre_corr_op(_Operator):
+    """ccorr(src_emb, hr.expand_as(src_emb)).  An _Operator (lazy handle, fused epilogue) but NOT a _PreOp: the fused cell-zero
+    kernels that every _PreOp is sent to know only mult / sub / add."""
+
+    def __init__(self):
+        super().__init__()
+
+    def forward(self, g, src_emb, hr):
+        if LZ.wanted(src_emb):
+            return LZ.defer(self, g, src_emb, hr, self.out_shape(g, src_emb))
+        return self.run(g, src_emb, hr)
+
+    def run(self, g, src_emb, hr, for_epilogue=False):
+        src_emb, hr = _rows_now(src_emb), _rows_now(hr)
+        return K.ccorr(src_emb, hr.expand_as(src_emb))
+
+
 # ---- trivial filters -----------------------------------------------------------
 class f_identity_op(_Operator):
     def run(self, g, src_emb, src_emb_in, for_epilogue=False):
