@@ -34,7 +34,7 @@
 extern "C" {
 #endif
 
-#define MRG_ABI_VERSION 17   /* 17: mrg_ccorr_rows, mrg_ccorr_matrix, mrg_ccorr_matrix_grad (standalone circular correlation: per-row kernel, and the circulant of a shared row with its gradient fold for the row GEMM); 16: mrg_set_stream_blocks, mrg_gate_collapse and mrg_gate_param_grad removed (the streaming grid bound is fixed; the three-segment forms remain); 15: mrg_gated_branch.valid_rows and the valid_rows argument of mrg_mix_finalize_bwd / mrg_zero_* except colstats (the device row count of a static step graph, passed per call instead of the process-wide registry of 13), mrg_linear_bwd_weight_share (the weight gradient of one range of a grouped launch, instead of the process-wide setter of 14); 14: mrg_clip_sgd_step, mrg_optim_chunk (clip_grad_norm_ + SGD with momentum over every parameter tensor in three launches), mrg_gated_branch.act (tanh behind the BatchNorm: CompGraphConv's tail on the epilogue kernels), mrg_gemm_set_small (few-row products on two-tile column blocks), a weight-gradient share setter, mrg_segmax_bwd_input (a_max's input gradient without a dense product); 13: a registry of device-side row counts (the sampled search step as one replayable HIP graph), mrg_seg_reduce_bwd_ordered (aggregator backward walked in destination order), mrg_gemm_set_q (the 16 x 16 x 32 row GEMM at three workgroups per CU for 129..224 output columns); 12: mrg_act_grad_transpose (the [B, N] scorer's output gradient, activation folded in, as [N, B] rows); 11: mrg_gemm_set_wide8 (eight-tile column block for D = 256); 10: mrg_gemm_set_epilogue(2) (transposed accumulators: a tested comparison point); 9: mrg_gated_branch (the MixedOp epilogue recomputes f_dense_comp's output from its gate and f_sparse_comp's from its row factor), mrg_gate_row_fwd / _bwd, mrg_sum_rows_gather, mrg_wgrad_set_variant, mrg_dense_filter_fwd3 out == NULL; 8: mrg_zero_* (cell-zero MixedOp recomputed from the tables), mrg_linear_bwd_input3_pair, mrg_sample_edge_neighborhood; 7: mrg_gemm_set_epilogue (row-order stores of the split-core row GEMM), mrg_set_stream_blocks, mrg_gemm_set_mode(2); 6: fused a_mean (run-sum epilogue, heads reducer, bit-mask backward), mrg_mix_stats_coef; 5: three-segment dense filter entry points; 4: mrg_linear_relu_segmax_fwd (fused a_max); 3: device graph / plan builders, samplers, [B, N] scorers, ranking; 2: GEMM workspaces, span_gcs ext_scal */
+#define MRG_ABI_VERSION 18   /* 18: mrg_conve_* (the ConvE feature path: BN0 statistics, conv, BN1, split-K fc and their gradients, stacked or interleaved image layout); 17: mrg_ccorr_rows, mrg_ccorr_matrix, mrg_ccorr_matrix_grad (standalone circular correlation: per-row kernel, and the circulant of a shared row with its gradient fold for the row GEMM); 16: mrg_set_stream_blocks, mrg_gate_collapse and mrg_gate_param_grad removed (the streaming grid bound is fixed; the three-segment forms remain); 15: mrg_gated_branch.valid_rows and the valid_rows argument of mrg_mix_finalize_bwd / mrg_zero_* except colstats (the device row count of a static step graph, passed per call instead of the process-wide registry of 13), mrg_linear_bwd_weight_share (the weight gradient of one range of a grouped launch, instead of the process-wide setter of 14); 14: mrg_clip_sgd_step, mrg_optim_chunk (clip_grad_norm_ + SGD with momentum over every parameter tensor in three launches), mrg_gated_branch.act (tanh behind the BatchNorm: CompGraphConv's tail on the epilogue kernels), mrg_gemm_set_small (few-row products on two-tile column blocks), a weight-gradient share setter, mrg_segmax_bwd_input (a_max's input gradient without a dense product); 13: a registry of device-side row counts (the sampled search step as one replayable HIP graph), mrg_seg_reduce_bwd_ordered (aggregator backward walked in destination order), mrg_gemm_set_q (the 16 x 16 x 32 row GEMM at three workgroups per CU for 129..224 output columns); 12: mrg_act_grad_transpose (the [B, N] scorer's output gradient, activation folded in, as [N, B] rows); 11: mrg_gemm_set_wide8 (eight-tile column block for D = 256); 10: mrg_gemm_set_epilogue(2) (transposed accumulators: a tested comparison point); 9: mrg_gated_branch (the MixedOp epilogue recomputes f_dense_comp's output from its gate and f_sparse_comp's from its row factor), mrg_gate_row_fwd / _bwd, mrg_sum_rows_gather, mrg_wgrad_set_variant, mrg_dense_filter_fwd3 out == NULL; 8: mrg_zero_* (cell-zero MixedOp recomputed from the tables), mrg_linear_bwd_input3_pair, mrg_sample_edge_neighborhood; 7: mrg_gemm_set_epilogue (row-order stores of the split-core row GEMM), mrg_set_stream_blocks, mrg_gemm_set_mode(2); 6: fused a_mean (run-sum epilogue, heads reducer, bit-mask backward), mrg_mix_stats_coef; 5: three-segment dense filter entry points; 4: mrg_linear_relu_segmax_fwd (fused a_max); 3: device graph / plan builders, samplers, [B, N] scorers, ranking; 2: GEMM workspaces, span_gcs ext_scal */
 
 #define MRG_OK            0
 #define MRG_E_NULLPTR    -1   /* a required pointer is NULL */
@@ -659,6 +659,50 @@ int mrg_transe_score_bwd(const float *ent, const float *sub, const float *rel, c
 int mrg_ccorr_rows(int mode, const float *X, const float *Y, float *out, int64_t N, int D, void *stream);
 int mrg_ccorr_matrix(int mode, const float *r, float *W, int D, void *stream);
 int mrg_ccorr_matrix_grad(int mode, const float *gW, float *gr, int D, void *stream);
+
+/* ---- ConvE feature path (ABI 18) ------------------------------------------------------------------------------------------
+ * The scorer of reference models/operations_lp.py:150-205 (sf_ConvE_op) and models/compgcn.py:188-269 (CompGCN_ConvE), from the
+ * (subject, relation) rows to the hidden vector in front of BN2:
+ *   img = layout(sub [B][D], rel [B][D]) [B][1][Hi][Wi], Hi Wi = 2 D;  pixel t of a row (t = y Wi + x):
+ *         MRG_CONVE_STACKED      (sf_ConvE_op.concat):   (t < D ? sub : rel)[t % D]
+ *         MRG_CONVE_INTERLEAVED  (CompGCN_ConvE.concat): (t % 2 == 0 ? sub : rel)[t / 2]
+ *   x0 = BN0(img) (BatchNorm2d(1));  z = conv(x0, Wc [F][1][ks][ks]) + bc (valid, stride 1; bc may be NULL)  [B][F][Ho][Wo]
+ *   a  = keep1 * relu(BN1(z))  (BatchNorm2d(F); keep1 [B][F][Ho][Wo] = the dropout mask scaled by 1 / (1 - p), or NULL)
+ *   h  = keep2 * (a.view(B, K) Wfc^T + bfc),  K = F Ho Wo  (keep2 [B][D] or NULL; bfc may be NULL)
+ * training != 0: BN0 / BN1 use the batch statistics and update running_mean / running_var in place as torch does (momentum, unbiased
+ *   variance; num_batches_tracked is the caller's); training == 0: the running statistics.  stats0 [2] = {mean, invstd} and
+ *   stats1 [2 F] = {mean [F], invstd [F]} are written by the forward and read by the backward.
+ * Shapes: 1 <= D <= MRG_CONVE_MAX_D, 1 <= ks <= MRG_CONVE_MAX_KS, ks <= Hi, Wi; else MRG_E_SHAPE.  f32 FMA arithmetic; statistics and
+ *   gradient sums in float64 in a fixed order (no atomics): bit-reproducible.
+ * Call order, forward: mrg_conve_bn0_fwd -> mrg_conve_conv_fwd (z) -> mrg_conve_bn1_fwd (a) -> mrg_conve_fc_fwd (h; workspace
+ *   mrg_conve_fc_workspace_bytes).  Backward from gh = dL/dh: mrg_conve_fc_bwd (ga = dL/da [B][K], gWfc [D][K], gbfc; the same
+ *   workspace) -> mrg_conve_bn1_bwd (ga -> dL/dz in place; gw1, gb1 [F]) -> mrg_conve_conv_bwd (workspace
+ *   mrg_conve_bwd_workspace_bytes) -> mrg_conve_finish_bwd (same workspace: gsub, grel [B][D], gw0, gb0 [1], gWc [F][ks][ks], gbc [F]
+ *   or NULL). */
+#define MRG_CONVE_STACKED      0
+#define MRG_CONVE_INTERLEAVED  1
+#define MRG_CONVE_MAX_D     1024
+#define MRG_CONVE_MAX_KS      15
+int64_t mrg_conve_fc_workspace_bytes(int64_t B, int64_t K, int D);
+int64_t mrg_conve_bwd_workspace_bytes(int64_t B, int D, int F, int ks);
+int mrg_conve_bn0_fwd(const float *sub, const float *rel, int64_t B, int D, float *running_mean, float *running_var, int training,
+                      float eps, float momentum, float *stats0, void *stream);
+int mrg_conve_conv_fwd(int layout, const float *sub, const float *rel, int64_t B, int D, int Hi, int Wi, const float *stats0,
+                       const float *bn0_w, const float *bn0_b, const float *Wc, const float *bc, int F, int ks, float *z, void *stream);
+int mrg_conve_bn1_fwd(const float *z, int64_t B, int F, int P, const float *bn1_w, const float *bn1_b, float *running_mean,
+                      float *running_var, const float *keep1, int training, float eps, float momentum, float *stats1, float *a,
+                      void *stream);
+int mrg_conve_fc_fwd(const float *a, const float *Wfc, const float *bfc, const float *keep2, float *h, void *ws, int64_t B, int64_t K,
+                     int D, void *stream);
+int mrg_conve_fc_bwd(const float *gh, const float *keep2, const float *a, const float *Wfc, float *ga, float *gWfc, float *gbfc,
+                     void *ws, int64_t B, int64_t K, int D, void *stream);
+int mrg_conve_bn1_bwd(float *g, const float *z, const float *a, const float *keep1, const float *stats1, const float *bn1_w,
+                      int training, int64_t B, int F, int P, float *gw1, float *gb1, void *stream);
+int mrg_conve_conv_bwd(int layout, const float *sub, const float *rel, int64_t B, int D, int Hi, int Wi, const float *stats0,
+                       const float *bn0_w, const float *bn0_b, const float *Wc, int F, int ks, const float *gz, void *ws, void *stream);
+int mrg_conve_finish_bwd(int layout, const float *sub, const float *rel, int64_t B, int D, int F, int ks, const float *stats0,
+                         const float *bn0_w, int training, const void *ws, float *gsub, float *grel, float *gw0, float *gb0,
+                         float *gWc, float *gbc, void *stream);
 
 /* gT[n][b] = g[b][n] * act'(y[b][n]): the output gradient of a wide, short Linear (the [B, N] scorers: N = all entities) with the
  * activation's derivative folded in, transposed to [N][B] rows -- the layout both of its gradient products stream

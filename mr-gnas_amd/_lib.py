@@ -14,7 +14,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("MRG_LIB_PATH") or os.path.join(_HERE, "lib", "libmrgnas_hip.so")     # MRG_LIB_PATH: lab builds of the same ABI
 HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "mrgnas.h")
 
-ABI_VERSION = 17
+ABI_VERSION = 18
 
 
 class MrgnasLibraryError(RuntimeError):
@@ -120,6 +120,16 @@ SIGNATURES = {
     "mrg_ccorr_rows": (_I, [_I, _P, _P, _P, _L, _I, _P]),
     "mrg_ccorr_matrix": (_I, [_I, _P, _P, _I, _P]),
     "mrg_ccorr_matrix_grad": (_I, [_I, _P, _P, _I, _P]),
+    "mrg_conve_fc_workspace_bytes": (_L, [_L, _L, _I]),
+    "mrg_conve_bwd_workspace_bytes": (_L, [_L, _I, _I, _I]),
+    "mrg_conve_bn0_fwd": (_I, [_P, _P, _L, _I, _P, _P, _I, _F, _F, _P, _P]),
+    "mrg_conve_conv_fwd": (_I, [_I, _P, _P, _L, _I, _I, _I, _P, _P, _P, _P, _P, _I, _I, _P, _P]),
+    "mrg_conve_bn1_fwd": (_I, [_P, _L, _I, _I, _P, _P, _P, _P, _P, _I, _F, _F, _P, _P, _P]),
+    "mrg_conve_fc_fwd": (_I, [_P, _P, _P, _P, _P, _P, _L, _L, _I, _P]),
+    "mrg_conve_fc_bwd": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _L, _L, _I, _P]),
+    "mrg_conve_bn1_bwd": (_I, [_P, _P, _P, _P, _P, _P, _I, _L, _I, _I, _P, _P, _P]),
+    "mrg_conve_conv_bwd": (_I, [_I, _P, _P, _L, _I, _I, _I, _P, _P, _P, _P, _I, _I, _P, _P, _P]),
+    "mrg_conve_finish_bwd": (_I, [_I, _P, _P, _L, _I, _I, _I, _P, _P, _I, _P, _P, _P, _P, _P, _P, _P, _P]),
 }
 
 _lib = None

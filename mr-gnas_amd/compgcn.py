@@ -1,9 +1,15 @@
-"""CompGCN layer and stack on the fused HIP kernel, importable in place of the reference's
-``models/compgcn.py`` (``CompGraphConv`` :12-113, ``CompGCN`` :116-185; the ConvE scorer
-``CompGCN_ConvE`` :188-269 is outside the hot path and not provided).
+"""CompGCN layer and stack on the fused HIP kernel, and CompGCN with the ConvE scorer, importable in place of the
+reference's ``models/compgcn.py`` (``CompGraphConv`` :12-113, ``CompGCN`` :116-185, ``CompGCN_ConvE`` :188-269).
 
 Same constructors, same ``forward`` signatures and return values, same parameter names
-(``W_O, W_I, W_S, W_R, loop_rel, bn``; ``basis, weights | rel_embds, n_embds, layers, dropouts``).
+(``W_O, W_I, W_S, W_R, loop_rel, bn``; ``basis, weights | rel_embds, n_embds, layers, dropouts``;
+``compGCN_Model, bn0, bn1, bn2, hidden_drop, feature_drop, m_conv1, fc, bias``).
+
+``CompGCN_ConvE`` runs the ConvE scorer on csrc/conve.hip (the interleaved image) for float32 HIP operands, with BN2 + ReLU on
+the MixedOp epilogue kernels and the [B, N] product on the row GEMM; autocast, forward hooks on a scorer submodule, or a
+BatchNorm without running statistics or with momentum=None run the reference's torch formulation instead.  Unlike the
+reference, it raises a ValueError when ``k_w * k_h != layer_size[-1]`` (the reference's reshape then silently makes several
+images per row and returns more score rows than queries).
 ``g`` is a ``RelGraph`` carrying ``edata['etype'|'norm'|'in_edges_mask'|'out_edges_mask']``.
 
 What changes is the schedule: W_O and W_I are linear and applied before a *sum*, so they
@@ -14,6 +20,7 @@ per-node edge counts.  max|delta| against the reference's per-edge order is ~1e-
 """
 import torch
 import torch.nn as nn
+import torch.nn.functional as F
 
 from . import functional as K
 from .graph import cached_on
@@ -118,3 +125,51 @@ class CompGCN(nn.Module):
             n_feats, r_feats = layer(graph, n_feats, r_feats)
             n_feats = drop(n_feats)
         return n_feats, r_feats
+
+
+class CompGCN_ConvE(nn.Module):
+    """CompGCN with the ConvE score function (reference models/compgcn.py:188-269)."""
+
+    def __init__(self, num_bases, num_rel, num_ent, in_dim, layer_size, comp_fn='sub', batchnorm=True, dropout=0.1,
+                 layer_dropout=[0.3], num_filt=200, hid_drop=0.3, feat_drop=0.3, ker_sz=5, k_w=5, k_h=5):
+        super().__init__()
+        self.embed_dim = layer_size[-1]
+        self.hid_drop, self.feat_drop, self.ker_sz, self.k_w, self.k_h, self.num_filt = hid_drop, feat_drop, ker_sz, k_w, k_h, num_filt
+        self.compGCN_Model = CompGCN(num_bases, num_rel, num_ent, in_dim, layer_size, comp_fn, batchnorm, dropout, layer_dropout)
+        self.bn0 = nn.BatchNorm2d(1)
+        self.bn1 = nn.BatchNorm2d(self.num_filt)
+        self.bn2 = nn.BatchNorm1d(self.embed_dim)
+        self.hidden_drop = nn.Dropout(self.hid_drop)
+        self.feature_drop = nn.Dropout(self.feat_drop)
+        self.m_conv1 = nn.Conv2d(1, out_channels=self.num_filt, kernel_size=(self.ker_sz, self.ker_sz), stride=1, padding=0, bias=False)
+        flat_sz_h = int(2 * self.k_w) - self.ker_sz + 1
+        flat_sz_w = self.k_h - self.ker_sz + 1
+        self.flat_sz = flat_sz_h * flat_sz_w * self.num_filt
+        self.fc = nn.Linear(self.flat_sz, self.embed_dim)
+        self.bias = nn.Parameter(torch.zeros(num_ent))
+        self.register_buffer("_one", torch.ones(1), persistent=False)      # the one-branch epilogue's weight (not in state_dict)
+
+    def concat(self, e1_embed, rel_embed):
+        e1_embed = e1_embed.view(-1, 1, self.embed_dim)
+        rel_embed = rel_embed.view(-1, 1, self.embed_dim)
+        stack_inp = torch.cat([e1_embed, rel_embed], 1)
+        return torch.transpose(stack_inp, 2, 1).reshape((-1, 1, 2 * self.k_w, self.k_h))
+
+    def forward(self, graph, sub, rel):
+        if self.k_w * self.k_h != self.embed_dim:
+            raise ValueError(f"CompGCN_ConvE: k_w * k_h = {self.k_w} * {self.k_h} must equal the embedding width layer_size[-1] = "
+                             f"{self.embed_dim} (one 2 k_w x k_h image per query)")
+        n_feats, r_feats = self.compGCN_Model(graph)
+        sub_emb = n_feats[sub, :]
+        rel_emb = r_feats[rel, :]
+        mods = (self.bn0, self.m_conv1, self.bn1, self.feature_drop, self.fc, self.hidden_drop, self.bn2)
+        if K.conve.hip_path_ok(mods, (self.bn0, self.bn1, self.bn2), (n_feats, sub_emb, rel_emb)):
+            return K.conve_scores(sub_emb, rel_emb, K.conve.INTERLEAVED, (2 * self.k_w, self.k_h), self.bn0, self.m_conv1, self.bn1,
+                                  self.feature_drop, self.fc, self.hidden_drop, self.bn2, self._one, n_feats, self.bias)
+        x = self.bn0(self.concat(sub_emb, rel_emb))
+        x = self.feature_drop(F.relu(self.bn1(self.m_conv1(x))))
+        x = self.fc(x.view(-1, self.flat_sz))
+        x = F.relu(self.bn2(self.hidden_drop(x)))
+        x = torch.mm(x, n_feats.transpose(1, 0))
+        x += self.bias.expand_as(x)
+        return torch.sigmoid(x)

@@ -20,6 +20,7 @@ This package re-exports every name of its modules, so callers keep writing ``fro
   cell_zero   Cell zero: the MixedOp over the compose candidates, recomputed from the entity / relation tables (csrc/mixedop.hip zero_*).
   scoring     The step after the path: DistMult triple scoring and the [B, N] score functions (csrc/scoring.hip).
   ccorr       Standalone circular correlation ccorr(a, b): per-row kernel, or a shared row's circulant on the row GEMM (csrc/ccorr.hip).
+  conve       ConvE feature path: BN0 -> conv -> BN1 -> ReLU -> fc of the (subject, relation) image, and the ConvE scorer (csrc/conve.hip).
 """
 from . import switches                                   # noqa: F401
 from ._base import (  # noqa: F401
@@ -64,5 +65,8 @@ from .scoring import (  # noqa: F401
 )
 from .ccorr import (  # noqa: F401
     _CCorrRows, _Circulant, ccorr,
+)
+from .conve import (  # noqa: F401
+    _ConvEFeatures, conve_features, conve_scores, drop_masks, hip_path_ok,
 )
 from .._lib import ptr_array, call, f32c, ptr, require_hip, stream_of   # noqa: F401  (part of the module's historical surface)

@@ -297,7 +297,9 @@ class sf_DisMult_op(nn.Module):
 
 
 class sf_ConvE_op(nn.Module):
-    """ConvE scorer: 2-D conv over the stacked (subject, relation) embedding."""
+    """ConvE scorer: 2-D conv over the stacked (subject, relation) embedding (reference :150-205).  Float32 HIP operands run on
+    csrc/conve.hip (functional.conve); CPU or other-dtype operands, autocast, forward hooks on a submodule, or a BatchNorm without
+    running statistics or with momentum=None run the torch formulation below."""
 
     def __init__(self, args):
         super().__init__()
@@ -311,9 +313,16 @@ class sf_ConvE_op(nn.Module):
         self.flat_sz = (2 * self.k_h - self.ker_sz + 1) * (self.k_w - self.ker_sz + 1) * self.num_filt
         self.fc = nn.Linear(self.flat_sz, self.embed_dim)
 
+        self.register_buffer("_one", torch.ones(1), persistent=False)      # the one-branch epilogue's weight (not in state_dict)
+
     def forward(self, all_ent, sub_emb, rel_emb):
         if self.embed_dim != self.k_h * self.k_w:
             raise AssertionError("embed_dim must equal k_h * k_w")
+        mods = (self.bn0, self.conv2d, self.bn1, self.feature_drop, self.fc, self.hidden_drop, self.bn2)
+        if K.conve.hip_path_ok(mods, (self.bn0, self.bn1, self.bn2), (all_ent, sub_emb, rel_emb)):
+            # the stacked image (reference :167-178) on csrc/conve.hip; BN2 + ReLU on the epilogue kernels, the product on the row GEMM
+            return K.conve_scores(sub_emb, rel_emb, K.conve.STACKED, (2 * self.k_h, self.k_w), self.bn0, self.conv2d, self.bn1,
+                                  self.feature_drop, self.fc, self.hidden_drop, self.bn2, self._one, all_ent, None)
         x = torch.stack([sub_emb, rel_emb], dim=1).reshape(-1, 1, 2 * self.k_h, self.k_w)
         x = self.feature_drop(F.relu(self.bn1(self.conv2d(self.bn0(x)))))
         x = F.relu(self.bn2(self.hidden_drop(self.fc(x.flatten(1)))))
