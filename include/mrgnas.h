@@ -34,7 +34,7 @@
 extern "C" {
 #endif
 
-#define MRG_ABI_VERSION 18   /* 18: mrg_conve_* (the ConvE feature path: BN0 statistics, conv, BN1, split-K fc and their gradients, stacked or interleaved image layout); 17: mrg_ccorr_rows, mrg_ccorr_matrix, mrg_ccorr_matrix_grad (standalone circular correlation: per-row kernel, and the circulant of a shared row with its gradient fold for the row GEMM); 16: mrg_set_stream_blocks, mrg_gate_collapse and mrg_gate_param_grad removed (the streaming grid bound is fixed; the three-segment forms remain); 15: mrg_gated_branch.valid_rows and the valid_rows argument of mrg_mix_finalize_bwd / mrg_zero_* except colstats (the device row count of a static step graph, passed per call instead of the process-wide registry of 13), mrg_linear_bwd_weight_share (the weight gradient of one range of a grouped launch, instead of the process-wide setter of 14); 14: mrg_clip_sgd_step, mrg_optim_chunk (clip_grad_norm_ + SGD with momentum over every parameter tensor in three launches), mrg_gated_branch.act (tanh behind the BatchNorm: CompGraphConv's tail on the epilogue kernels), mrg_gemm_set_small (few-row products on two-tile column blocks), a weight-gradient share setter, mrg_segmax_bwd_input (a_max's input gradient without a dense product); 13: a registry of device-side row counts (the sampled search step as one replayable HIP graph), mrg_seg_reduce_bwd_ordered (aggregator backward walked in destination order), mrg_gemm_set_q (the 16 x 16 x 32 row GEMM at three workgroups per CU for 129..224 output columns); 12: mrg_act_grad_transpose (the [B, N] scorer's output gradient, activation folded in, as [N, B] rows); 11: mrg_gemm_set_wide8 (eight-tile column block for D = 256); 10: mrg_gemm_set_epilogue(2) (transposed accumulators: a tested comparison point); 9: mrg_gated_branch (the MixedOp epilogue recomputes f_dense_comp's output from its gate and f_sparse_comp's from its row factor), mrg_gate_row_fwd / _bwd, mrg_sum_rows_gather, mrg_wgrad_set_variant, mrg_dense_filter_fwd3 out == NULL; 8: mrg_zero_* (cell-zero MixedOp recomputed from the tables), mrg_linear_bwd_input3_pair, mrg_sample_edge_neighborhood; 7: mrg_gemm_set_epilogue (row-order stores of the split-core row GEMM), mrg_set_stream_blocks, mrg_gemm_set_mode(2); 6: fused a_mean (run-sum epilogue, heads reducer, bit-mask backward), mrg_mix_stats_coef; 5: three-segment dense filter entry points; 4: mrg_linear_relu_segmax_fwd (fused a_max); 3: device graph / plan builders, samplers, [B, N] scorers, ranking; 2: GEMM workspaces, span_gcs ext_scal */
+#define MRG_ABI_VERSION 19   /* 19: mrg_seg_std_workspace_bytes, mrg_seg_std_fwd, mrg_seg_std_bwd (a_std, the standard-deviation aggregator of the node-classification task); 18: mrg_conve_* (the ConvE feature path: BN0 statistics, conv, BN1, split-K fc and their gradients, stacked or interleaved image layout); 17: mrg_ccorr_rows, mrg_ccorr_matrix, mrg_ccorr_matrix_grad (standalone circular correlation: per-row kernel, and the circulant of a shared row with its gradient fold for the row GEMM); 16: mrg_set_stream_blocks, mrg_gate_collapse and mrg_gate_param_grad removed (the streaming grid bound is fixed; the three-segment forms remain); 15: mrg_gated_branch.valid_rows and the valid_rows argument of mrg_mix_finalize_bwd / mrg_zero_* except colstats (the device row count of a static step graph, passed per call instead of the process-wide registry of 13), mrg_linear_bwd_weight_share (the weight gradient of one range of a grouped launch, instead of the process-wide setter of 14); 14: mrg_clip_sgd_step, mrg_optim_chunk (clip_grad_norm_ + SGD with momentum over every parameter tensor in three launches), mrg_gated_branch.act (tanh behind the BatchNorm: CompGraphConv's tail on the epilogue kernels), mrg_gemm_set_small (few-row products on two-tile column blocks), a weight-gradient share setter, mrg_segmax_bwd_input (a_max's input gradient without a dense product); 13: a registry of device-side row counts (the sampled search step as one replayable HIP graph), mrg_seg_reduce_bwd_ordered (aggregator backward walked in destination order), mrg_gemm_set_q (the 16 x 16 x 32 row GEMM at three workgroups per CU for 129..224 output columns); 12: mrg_act_grad_transpose (the [B, N] scorer's output gradient, activation folded in, as [N, B] rows); 11: mrg_gemm_set_wide8 (eight-tile column block for D = 256); 10: mrg_gemm_set_epilogue(2) (transposed accumulators: a tested comparison point); 9: mrg_gated_branch (the MixedOp epilogue recomputes f_dense_comp's output from its gate and f_sparse_comp's from its row factor), mrg_gate_row_fwd / _bwd, mrg_sum_rows_gather, mrg_wgrad_set_variant, mrg_dense_filter_fwd3 out == NULL; 8: mrg_zero_* (cell-zero MixedOp recomputed from the tables), mrg_linear_bwd_input3_pair, mrg_sample_edge_neighborhood; 7: mrg_gemm_set_epilogue (row-order stores of the split-core row GEMM), mrg_set_stream_blocks, mrg_gemm_set_mode(2); 6: fused a_mean (run-sum epilogue, heads reducer, bit-mask backward), mrg_mix_stats_coef; 5: three-segment dense filter entry points; 4: mrg_linear_relu_segmax_fwd (fused a_max); 3: device graph / plan builders, samplers, [B, N] scorers, ranking; 2: GEMM workspaces, span_gcs ext_scal */
 
 #define MRG_OK            0
 #define MRG_E_NULLPTR    -1   /* a required pointer is NULL */
@@ -185,6 +185,25 @@ int mrg_seg_reduce_bwd_ordered(int mode, const float *gout, const int32_t *dst, 
 int mrg_segmax_bwd_input_ok(int D, int Kin);
 int mrg_segmax_bwd_input(const float *gout, const float *mx, const int32_t *dst, const int32_t *arg, const float *W, float *gmsg,
                          float *gx, const int32_t *order, int64_t E, int64_t N, int D, int Kin, void *stream);
+
+/* ---- a_std: destination-segmented standard deviation (ABI 19) ------------------------------------------------------------
+ * The node-classification aggregator of reference models/operations.py:168-190, update_all(copy_edge, reduce_std) on a block:
+ *   out[v,c] = sqrt(relu(mean_e x[e,c]^2 - (mean_e x[e,c])^2) + 1e-5)   over the in-edges e of v;  0 where v has no in-edge.
+ * msg [E, D]; the chunk plan (eid, chunk_*, hub_*, n_slots, in_degree) is the one of mrg_seg_reduce_fwd; ws: at least
+ * mrg_seg_std_workspace_bytes(n_slots, D) bytes when n_slots > 0.  Besides out [N, D] the forward writes, per (node, column),
+ * mean [N, D] (the mean of the messages) and coef [N, D] = [u > 0] / (deg * out), u the variance before the ReLU (0 where
+ * deg == 0).  Sums of x and x^2 in float64 in list order (partials of split lists added in slot order): no atomics,
+ * bit-reproducible.  The backward is the exact derivative of the formula, ReLU mask included:
+ *   gmsg[e,c] = gout[v,c] * coef[v,c] * (msg[e,c] - mean[v,c]),  v = dst[e]
+ * one independent row per edge; order [E] (NULL: edge-id order) = the edge ids sorted by destination, the walk that keeps
+ * the gathered [N, D] rows in cache.  Same D limits as mrg_seg_reduce_fwd; no host synchronisation, no allocation. */
+int64_t mrg_seg_std_workspace_bytes(int64_t n_slots, int D);
+int mrg_seg_std_fwd(const float *msg, const int32_t *eid, const int32_t *chunk_node, const int32_t *chunk_start,
+                    const int32_t *chunk_end, const int32_t *chunk_slot, int64_t n_chunks, const int32_t *hub_node,
+                    const int32_t *hub_first, const int32_t *hub_count, int64_t n_hubs, int64_t n_slots,
+                    const int32_t *in_degree, float *out, float *mean, float *coef, void *ws, int64_t N, int D, void *stream);
+int mrg_seg_std_bwd(const float *gout, const float *msg, const int32_t *dst, const float *mean, const float *coef,
+                    const int32_t *order, float *gmsg, int64_t E, int64_t N, int D, void *stream);
 
 /* ---- a9: fused gather -> compose -> segmented sum ------------------------------
  * CompGraphConv.forward steps 1-3, reference models/compgcn.py:58-87:

@@ -21,6 +21,7 @@ This package re-exports every name of its modules, so callers keep writing ``fro
   scoring     The step after the path: DistMult triple scoring and the [B, N] score functions (csrc/scoring.hip).
   ccorr       Standalone circular correlation ccorr(a, b): per-row kernel, or a shared row's circulant on the row GEMM (csrc/ccorr.hip).
   conve       ConvE feature path: BN0 -> conv -> BN1 -> ReLU -> fc of the (subject, relation) image, and the ConvE scorer (csrc/conve.hip).
+  nc          Node-classification aggregators on a block: a_std (csrc/segstd.hip) and a_sum / a_mean / a_max without self rows.
 """
 from . import switches                                   # noqa: F401
 from ._base import (  # noqa: F401
@@ -68,5 +69,8 @@ from .ccorr import (  # noqa: F401
 )
 from .conve import (  # noqa: F401
     _ConvEFeatures, conve_features, conve_scores, drop_masks, hip_path_ok,
+)
+from .nc import (  # noqa: F401
+    _SegStd, aggregate_std, inv_in_degree, aggregate_nc, linear_relu_aggregate_nc,
 )
 from .._lib import ptr_array, call, f32c, ptr, require_hip, stream_of   # noqa: F401  (part of the module's historical surface)

@@ -485,6 +485,69 @@ class RelGraph:
         return n
 
 
+# DGL's names of the id / type fields (dgl.EID, dgl.NID, dgl.ETYPE): the node-classification network reads block.edata[EID],
+# block.edata[ETYPE] and block.dstdata[NID] (reference models/model.py:148-152, 176-179)
+EID = NID = "_ID"
+ETYPE = "_TYPE"
+
+
+class Block(RelGraph):
+    """One message-passing layer of a node-classification minibatch, in place of DGL's block (the node-classification task:
+    reference models/operations.py, models/model.py; built by sampler.full_neighbor_blocks).
+
+    Edges run from ``n_src`` source rows to ``n_dst`` destination rows; ``src`` / ``dst`` are LOCAL indices.  The graph's node
+    count, ``number_of_nodes()``, is ``n_dst``: what the aggregator kernels size their [n_dst, D] output by.  ``srcdata`` and
+    ``dstdata`` are separate frames, each holding the global node ids under ``NID``; ``ndata`` is ``dstdata``.  ``edata`` holds
+    the global edge ids (int64) under ``EID`` and the relation types under ``ETYPE``."""
+
+    def __init__(self, src_nodes, dst_nodes, src, dst, eid, etype=None):
+        super().__init__(int(dst_nodes.numel()), src, dst, device=dst_nodes.device)
+        self._n_src = int(src_nodes.numel())
+        self._srcdata = {NID: src_nodes.long()}
+        self._dstdata = {NID: dst_nodes.long()}
+        self.ndata = self._dstdata
+        self.edata[EID] = eid.long()
+        if etype is not None:
+            self.edata[ETYPE] = etype.long()
+
+    @property
+    def srcdata(self):
+        return self._srcdata
+
+    @property
+    def dstdata(self):
+        return self._dstdata
+
+    def number_of_src_nodes(self):
+        return self._n_src
+
+    def number_of_dst_nodes(self):
+        return self._n
+
+    num_src_nodes = number_of_src_nodes
+    num_dst_nodes = number_of_dst_nodes
+
+    @contextlib.contextmanager
+    def local_scope(self):
+        sd, dd, ed = dict(self._srcdata), dict(self._dstdata), dict(self.edata)
+        try:
+            yield
+        finally:
+            for frame, saved in ((self._srcdata, sd), (self._dstdata, dd), (self.edata, ed)):
+                frame.clear(); frame.update(saved)
+
+    def to(self, device):
+        device = torch.device(device)
+        if device == self.device:
+            return self
+        b = Block(self._srcdata[NID].to(device), self._dstdata[NID].to(device), self._src.to(device), self._dst.to(device),
+                  self.edata[EID].to(device))
+        b.edata.update({k: v.to(device) for k, v in self.edata.items()})
+        b._srcdata.update({k: v.to(device) for k, v in self._srcdata.items()})
+        b._dstdata.update({k: v.to(device) for k, v in self._dstdata.items()})
+        return b
+
+
 # ---- graph construction (the step before the hot path) ----------------------------
 def _deg_norm(in_deg):
     with np.errstate(divide="ignore"):

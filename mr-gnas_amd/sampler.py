@@ -227,3 +227,54 @@ class LabelIndex:
         call("mrg_multi_hot_labels", (ptr(self.keys), ptr(self.rowptr), ptr(self.objs), ptr(q), B, int(self.keys.numel()), self.num_ent,
                                       float(v[0]), float(v[1]), ptr(out), stream_of(q)))
         return out
+
+
+def _edge_types(graph):
+    for key in (G.ETYPE, "e_type", "etype"):
+        if key in graph.edata:
+            return graph.edata[key]
+    return None
+
+
+def full_neighbor_blocks(graph, seeds, num_layers):
+    """The blocks of DGL's ``MultiLayerFullNeighborSampler(num_layers, return_eids=True)`` for the destination nodes ``seeds``
+    (reference search/mr_nc_search.py:43, train/mr_nc_train.py:42), outermost first, as graph.Block objects:
+
+    * the last block's destination nodes are ``seeds`` (unique ids), in the given order;
+    * block j's destination nodes are block j + 1's source nodes, in the same order;
+    * a block's source nodes are its destination nodes first, then the new sources in order of first appearance over its edge list;
+    * a block's edges are every in-edge of its destination nodes, grouped by destination in destination order, edge ids ascending
+      within a destination; ``edata[EID]`` holds their ids in ``graph``, ``edata[ETYPE]`` their types (graph.edata[ETYPE], or
+      'e_type' / 'etype').
+
+    Torch ops on the tensors' device (CPU included); two host reads of sizes per layer."""
+    dev = graph.device
+    N = graph.number_of_nodes()
+    gsrc, gdst = graph.edges()
+    gsrc, gdst = gsrc.long(), gdst.long()
+    etype = _edge_types(graph)
+    order = torch.argsort(gdst, stable=True)                         # edge ids by destination, ascending within one
+    deg = torch.zeros(N, dtype=torch.long, device=dev).scatter_add_(0, gdst, torch.ones_like(gdst))
+    rowptr = torch.cumsum(deg, 0) - deg
+    dst_nodes = torch.as_tensor(seeds, device=dev).long().reshape(-1)
+    blocks = []
+    for _ in range(int(num_layers)):
+        n_dst = int(dst_nodes.numel())
+        d = deg[dst_nodes]
+        E = int(d.sum())                                             # host read 1
+        ldst = torch.repeat_interleave(torch.arange(n_dst, device=dev), d, output_size=E)
+        first = torch.cumsum(d, 0) - d
+        pos = torch.arange(E, device=dev) - first[ldst] + rowptr[dst_nodes][ldst]
+        eid = order[pos]
+        s = gsrc[eid]
+        local = torch.full((N,), -1, dtype=torch.long, device=dev)
+        local[dst_nodes] = torch.arange(n_dst, device=dev)
+        firstpos = torch.full((N,), E, dtype=torch.long, device=dev)
+        firstpos.scatter_reduce_(0, s, torch.arange(E, device=dev), reduce="amin")
+        fresh = (local[s] < 0) & (firstpos[s] == torch.arange(E, device=dev))
+        new = s[fresh]                                               # new sources in order of first appearance (host read 2)
+        local[new] = torch.arange(n_dst, n_dst + int(new.numel()), device=dev)
+        src_nodes = torch.cat((dst_nodes, new))
+        blocks.append(G.Block(src_nodes, dst_nodes, local[s], ldst, eid, etype[eid].long() if etype is not None else None))
+        dst_nodes = src_nodes
+    return blocks[::-1]
