@@ -42,6 +42,15 @@ struct GemmGroups {
   float scale[3];
   int use_rowscale[3];
 };
+// Host: blocks of range s follow those of range s - 1.  Fills tile0[] for gbm rows per workgroup; returns the number of workgroups.
+inline int gemm_group_tiles(GemmGroups& g, int gbm) {
+  g.tile0[0] = 0;
+  for (int i = 0; i < 3; ++i) {
+    const int64_t r = i < g.n && g.hi[i] > g.lo[i] ? g.hi[i] - g.lo[i] : 0;
+    g.tile0[i + 1] = g.tile0[i] + (int)((r + gbm - 1) / gbm);
+  }
+  return g.tile0[3];
+}
 
 struct GemmArgs {
   const float* A1; const float* A2;   // [rows][K1], [rows][K2] row-major; A2 may be NULL (K2 = 0)
@@ -241,9 +250,6 @@ __device__ __forceinline__ float4 gemm_mask_a(float4 v, const GemmArgs& a, int64
 // Every load (bias, row scale, gate multiplicand, accumulate input) is issued unconditionally from a
 // clamped address BEFORE the stores, and a full tile stores without per-element branches: a store inside
 // a data-dependent branch makes hipcc wait vmcnt(0) per store, which serialises the 16*NT stores of a lane.
-#ifndef MRG_C_NT
-#define MRG_C_NT 0
-#endif
 template <int NT, int EPI>
 __device__ __forceinline__ void gemm_epilogue(const GemmArgs& a, f32x16 (&acc)[NT], int64_t rowbase, int col0, int li, int lh,
                                               bool full) {
@@ -305,13 +311,7 @@ __device__ __forceinline__ void gemm_epilogue(const GemmArgs& a, f32x16 (&acc)[N
       if (cok) {
         if (cstore) {
 #pragma unroll
-          for (int r = 0; r < 16; ++r) {
-#if MRG_C_NT
-            __builtin_nontemporal_store(v[r], crow[r] + n * 32);         // lab: C is written once and re-read by a later kernel
-#else
-            crow[r][n * 32] = v[r];
-#endif
-          }
+          for (int r = 0; r < 16; ++r) crow[r][n * 32] = v[r];
         }
         if (EPI == EPI_GATE && a.aux) {
 #pragma unroll
@@ -737,12 +737,8 @@ __global__ __launch_bounds__(MRG_BLOCK, 2) void rowgemm_dma_k(GemmArgs a) {
   gemm_epilogue<NT, EPI>(a, acc, row0 + wave * 32, col0, li, lh, row0 + GBM <= a.rows);
 }
 
-#ifndef MRG_FORCE_NT4
-#define MRG_FORCE_NT4 0     // lab: column blocks of four tiles whatever the width (N = 200: 2 blocks, 8 tiles, A read twice)
-#endif
 inline int gemm_pick_nt(int ncols) {
   int t = (ncols + 31) / 32;
-  if (MRG_FORCE_NT4 && t > 4) return 4;
   if (t <= 1) return 1;
   if (t <= 2) return 2;
   if (t <= 4) return 4;

@@ -24,33 +24,9 @@
 #include <type_traits>
 #include "gemm.hpp"
 
-// lab switches (tools/gemm_x3_lab.hip): 1 no epilogue stores, 2 no A split, 4 no DMA after the first slab, 8 no barrier,
-// 32 no B loads after the first slab, 64 no split at all, 128 no fragment reads, 256 staggered start (desynchronised rounds)
-#ifndef MRG_X3_DBG
-#define MRG_X3_DBG 0
-#endif
-// cache policy of the streamed A operand's DMA (lab: 0 default, 2 = nt)
-#ifndef MRG_A_CPOL
-#define MRG_A_CPOL 0
-#endif
-// VALU instructions the scheduler may place after each MFMA of a tile (lab sweep: 2 / 3 / 4 / 6)
-// lab switch 256: s_sleep(127) repetitions (64 * 127 cycles each) the odd workgroups of the first round wait
-#ifndef MRG_X3_STAGGER
-#define MRG_X3_STAGGER 6
-#endif
-#ifndef MRG_X3_VPM
-#define MRG_X3_VPM 3
-#endif
-
 namespace mrg {
 
-// lab switch 512: per-wave phase timestamps (100 MHz wall clock) -> mrg_x3_trace[wave slot * 4 + {start, loop, epilogue, end}]
-#if MRG_X3_DBG & 512
-__device__ unsigned long long* mrg_x3_trace;
-#define MRG_X3_STAMP(slot, i) do { if (lane == 0) mrg_x3_trace[(int64_t)(slot) * 4 + (i)] = wall_clock64(); } while (0)
-#else
-#define MRG_X3_STAMP(slot, i) do { } while (0)
-#endif
+constexpr int X3_VPM = 3;     // VALU instructions the scheduler may place after each MFMA of a tile (lab sweep: 2 / 3 / 4 / 6)
 
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
@@ -210,12 +186,6 @@ __global__ __launch_bounds__(X3_THREADS, 1) void rowgemm_x3_k(GemmArgs a, const 
   const int col0 = blockIdx.y * (NT * 32);
   const int K = a.K1 + a.K2;
   const int nslab = (K + 15) >> 4;
-
-  if ((MRG_X3_DBG & 256) && blockIdx.x < 256 && (blockIdx.x & 1)) {     // lab: first-round workgroups of every other CU start late
-    for (int i = 0; i < MRG_X3_STAGGER; ++i) __builtin_amdgcn_s_sleep(127);
-  }
-  [[maybe_unused]] const int64_t trace_slot = ((int64_t)blockIdx.y * gridDim.x + blockIdx.x) * 4 + wave;
-  MRG_X3_STAMP(trace_slot, 0);
   f32x16 acc[MT][NT];
 #pragma unroll
   for (int m = 0; m < MT; ++m)
@@ -251,7 +221,7 @@ __global__ __launch_bounds__(X3_THREADS, 1) void rowgemm_x3_k(GemmArgs a, const 
       } else {
         p = arow1[i] + (k + 4 <= K ? k : K - 4);
       }
-      __builtin_amdgcn_global_load_lds((gbl_ptr_t)p, (lds_ptr_t)(dst + 64 * i * 4), 16, 0, MRG_A_CPOL);
+      __builtin_amdgcn_global_load_lds((gbl_ptr_t)p, (lds_ptr_t)(dst + 64 * i * 4), 16, 0, 0);
     }
   };
   const unsigned lds_ring = (unsigned)(size_t)(lds_ptr_t)ring;
@@ -292,8 +262,7 @@ __global__ __launch_bounds__(X3_THREADS, 1) void rowgemm_x3_k(GemmArgs a, const 
     const int m = j >> 2, q = j & 3;
     const v4f& v = x[m][q >> 1];
     unsigned h, mm, l;
-    if (MRG_X3_DBG & 2) { h = __builtin_bit_cast(unsigned, v.x); mm = h; l = h; }
-    else if (q & 1) split_pair(v.z, v.w, h, mm, l);
+    if (q & 1) split_pair(v.z, v.w, h, mm, l);
     else split_pair(v.x, v.y, h, mm, l);
     H[m][q] = h; M[m][q] = mm; L[m][q] = l;
   };
@@ -308,7 +277,6 @@ __global__ __launch_bounds__(X3_THREADS, 1) void rowgemm_x3_k(GemmArgs a, const 
   read_a(0);
   asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
   __builtin_amdgcn_sched_barrier(0);
-  MRG_X3_STAMP(trace_slot, 1);
 #pragma unroll
   for (int j = 0; j < NPAIR; ++j) split_one(j, ch, cm, cl);
 
@@ -325,9 +293,9 @@ __global__ __launch_bounds__(X3_THREADS, 1) void rowgemm_x3_k(GemmArgs a, const 
       if (MODE < 0) { if (s >= 2) wait_vmcnt(2 * NBL + ((s + 2 < nslab) ? NA : 0)); }
       else if (MODE == 2) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(2 * NBL) : "memory");
       else asm volatile("s_waitcnt vmcnt(%0)" ::"n"(2 * NBL + NA) : "memory");
-      if (!(MRG_X3_DBG & 128)) read_a(s + 1);
+      read_a(s + 1);
     }
-    if (do_dma && !((MRG_X3_DBG & 4) && s > 0)) fetch_a(s + 3);
+    if (do_dma) fetch_a(s + 3);
 #pragma unroll
     for (int n = 0; n < NT; ++n) {
       // B(s) tile n: younger = rest of B(s), this slab's A DMA, the B(s+1) tiles issued so far
@@ -338,7 +306,7 @@ __global__ __launch_bounds__(X3_THREADS, 1) void rowgemm_x3_k(GemmArgs a, const 
       constexpr int N0 = NT > 1 ? 1 : 0;              // the splits start one tile late: the LDS reads issued at the top have landed by then
       if (n == N0 && has_next) asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");     // raw fragments of the next slab
       __builtin_amdgcn_sched_barrier(0);
-      if (has_next && n >= N0 && !(MRG_X3_DBG & 64)) {                      // VALU work for the shadow of this tile's MFMAs
+      if (has_next && n >= N0) {                      // VALU work for the shadow of this tile's MFMAs
 #pragma unroll
         for (int j = (n - N0) * PP; j < (n - N0 + 1) * PP && j < NPAIR; ++j) split_one(j, nh, nm, nl);
       }
@@ -356,7 +324,7 @@ __global__ __launch_bounds__(X3_THREADS, 1) void rowgemm_x3_k(GemmArgs a, const 
       MRG_X3_TERM(ch, Bm);
       MRG_X3_TERM(ch, Bh);
 #undef MRG_X3_TERM
-      if (has_next && n == NT - 1 && !(MRG_X3_DBG & 64)) {
+      if (has_next && n == NT - 1) {
 #pragma unroll
         for (int m = 0; m < MT; ++m) { ch[m] = nh[m]; cm[m] = nm[m]; cl[m] = nl[m]; }
       }
@@ -364,10 +332,10 @@ __global__ __launch_bounds__(X3_THREADS, 1) void rowgemm_x3_k(GemmArgs a, const 
 #pragma unroll
       for (int i = 0; i < 6 * MT; ++i) {
         __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-        __builtin_amdgcn_sched_group_barrier(0x002, MRG_X3_VPM, 0);
+        __builtin_amdgcn_sched_group_barrier(0x002, X3_VPM, 0);
       }
       __builtin_amdgcn_sched_barrier(0);
-      if (has_next && !((MRG_X3_DBG & 32) && s > 0)) load_b(n, s + 1);
+      if (has_next) load_b(n, s + 1);
     }
   };
   // the host guarantees nslab >= 4 (x3_eligible)
@@ -375,8 +343,6 @@ __global__ __launch_bounds__(X3_THREADS, 1) void rowgemm_x3_k(GemmArgs a, const 
   slab(std::integral_constant<int, 1>{}, nslab - 3);
   slab(std::integral_constant<int, 2>{}, nslab - 2);
   slab(std::integral_constant<int, 3>{}, nslab - 1);
-  MRG_X3_STAMP(trace_slot, 2);
-  if ((MRG_X3_DBG & 1) && acc[0][0][0] != 123.456f) return;
 #pragma unroll
   for (int m = 0; m < MT; ++m) {
     if constexpr (EPI == EPI_SEGMAX) gemm_epilogue_segmax<NT>(a, acc[m], roww + m * 32, col0, li, lh);
@@ -384,7 +350,6 @@ __global__ __launch_bounds__(X3_THREADS, 1) void rowgemm_x3_k(GemmArgs a, const 
     else if constexpr (LDSEPI) gemm_epilogue_lds<NT, EPI>(a, acc[m], roww + m * 32, col0, lane, ring);
     else gemm_epilogue<NT, EPI>(a, acc[m], roww + m * 32, col0, li, lh, row0 + GBM <= a.rows);
   }
-  if (MRG_X3_DBG & 512) { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); MRG_X3_STAMP(trace_slot, 3); }
 }
 
 inline bool x3_eligible(const GemmArgs& a) {
@@ -400,14 +365,7 @@ inline int launch_rowgemm_x3(GemmArgs a, const void* Bp, hipStream_t st, int nt_
   const int ntile = x3_tiles(a.N, nt);
   const int mt = a.rows > 128 * 512 ? 2 : 1;            // short operands: more, smaller workgroups
   const int gbm = 32 * mt * (X3_THREADS / 64);
-  if (a.grp.n > 0) {                                    // grouped: blocks of range s follow those of range s - 1
-    a.grp.tile0[0] = 0;
-    for (int i = 0; i < 3; ++i) {
-      const int64_t r = i < a.grp.n && a.grp.hi[i] > a.grp.lo[i] ? a.grp.hi[i] - a.grp.lo[i] : 0;
-      a.grp.tile0[i + 1] = a.grp.tile0[i] + (int)((r + gbm - 1) / gbm);
-    }
-    if (a.grp.tile0[3] == 0) return MRG_OK;
-  }
+  if (a.grp.n > 0 && gemm_group_tiles(a.grp, gbm) == 0) return MRG_OK;     // grouped launch: nothing to do
   dim3 grid((unsigned)(a.grp.n > 0 ? a.grp.tile0[3] : (a.rows + gbm - 1) / gbm), (unsigned)(ntile / nt));
   const size_t ring_floats = (size_t)X3_SLOTS * 32 * mt * 16;
   a.epi_lds = (gemm_epi_lds() && gemm_epilogue_lds_ok<EPI>(a)) ? 1 : 0;

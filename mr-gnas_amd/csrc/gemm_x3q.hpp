@@ -183,18 +183,11 @@ __device__ __forceinline__ void gemm_epilogue_q(const GemmArgs& a, f32x4v (&acc)
   }
 }
 
-#ifndef MRG_X3Q_WPS
-#define MRG_X3Q_WPS 3        // lab: waves per SIMD the kernel is compiled for (3: <= 168 registers)
-#endif
-// lab switches (timing only -- wrong results; tools/lab/kernel_lab.sh libs NAME=-DMRG_X3Q_DBG=V:linear.hip,dense.hip builds one library per value into tools/labso/):
-// 1 no epilogue, 2 no A loads after the prologue, 4 no weight DMA after the prologue, 8 no barriers after the prologue,
-// 16 no fragment reads after the first tile, 32 no split arithmetic
-#ifndef MRG_X3Q_DBG
-#define MRG_X3Q_DBG 0
-#endif
+constexpr int X3Q_WPS = 3;   // waves per SIMD the kernel is compiled for (3: <= 168 registers)
+// (what each part of the kernel costs, one part removed at a time: profiles/r5_rowgemm_q.txt)
 
 template <int EPI, bool DUAL>
-__global__ __launch_bounds__(256, MRG_X3Q_WPS) void rowgemm_x3q_k(GemmArgs a, const char* __restrict__ Bp) {
+__global__ __launch_bounds__(256, X3Q_WPS) void rowgemm_x3q_k(GemmArgs a, const char* __restrict__ Bp) {
   constexpr int NCH = X3Q_HT * 3;               // 1 KB pieces (64 lanes x 16 B) of a half-slab
   constexpr int NBW = (NCH + 3) / 4;            // DMA instructions per wave and half-slab
   extern __shared__ __align__(16) char smem_q[];          // [2][X3Q_CHUNK]
@@ -264,10 +257,7 @@ __global__ __launch_bounds__(256, MRG_X3Q_WPS) void rowgemm_x3q_k(GemmArgs a, co
   };
   const unsigned lds0 = (unsigned)(size_t)(lds_ptr_t)smem_q + (unsigned)lane * 16u;
   u32x4 bq[2][3];                                        // [ping-pong][plane]: the fragments of one column tile
-  bool lab_first = true;
   auto read_b = [&](int t, int buf, u32x4 (&q)[3]) {
-    if ((MRG_X3Q_DBG & 16) && !lab_first) return;
-    lab_first = false;
     const unsigned ad = lds0 + (unsigned)(buf * X3Q_CHUNK + t * 3072);
     asm volatile("ds_read_b128 %0, %1" : "=v"(q[0]) : "v"(ad));
     asm volatile("ds_read_b128 %0, %1 offset:1024" : "=v"(q[1]) : "v"(ad));
@@ -277,8 +267,7 @@ __global__ __launch_bounds__(256, MRG_X3Q_WPS) void rowgemm_x3q_k(GemmArgs a, co
   auto split_pair_of = [&](const v4f (&x)[2], int q, u32x4& H, u32x4& M, u32x4& L) {     // q = 0..3: floats 2q, 2q + 1 of the 8
     const v4f& v = x[q >> 1];
     unsigned h, m, l;
-    if (MRG_X3Q_DBG & 32) { h = __builtin_bit_cast(unsigned, (q & 1) ? v.z : v.x); m = __builtin_bit_cast(unsigned, (q & 1) ? v.w : v.y); l = h; }
-    else if (q & 1) split_pair(v.z, v.w, h, m, l); else split_pair(v.x, v.y, h, m, l);
+    if (q & 1) split_pair(v.z, v.w, h, m, l); else split_pair(v.x, v.y, h, m, l);
     H[q] = h; M[q] = m; L[q] = l;
   };
 
@@ -341,18 +330,17 @@ __global__ __launch_bounds__(256, MRG_X3Q_WPS) void rowgemm_x3q_k(GemmArgs a, co
   auto slab = [&](auto r_c, int s) {
     constexpr int R = decltype(r_c)::value;
     const bool has_next = s + 1 < nslab;
-    if (s > 0 && !(MRG_X3Q_DBG & 4)) fetch_b(2 * s + 1);
+    if (s > 0) fetch_b(2 * s + 1);
     half_slab(std::integral_constant<int, 0>{}, std::false_type{}, xr[0]);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    if (!(MRG_X3Q_DBG & 8)) __builtin_amdgcn_s_barrier();
-    if (has_next && !(MRG_X3Q_DBG & 4)) fetch_b(2 * s + 2);
-    if (!(MRG_X3Q_DBG & 2)) load_a(s + 2, xr[R]);
+    __builtin_amdgcn_s_barrier();
+    if (has_next) fetch_b(2 * s + 2);
+    load_a(s + 2, xr[R]);
     half_slab(std::integral_constant<int, 1>{}, std::true_type{}, xr[R ^ 1]);
     ch = nh; cm = nm; cl = nl;
     if (has_next) {
-      if (MRG_X3Q_DBG & 6) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      else asm volatile("s_waitcnt vmcnt(2)" ::: "memory");
-      if (!(MRG_X3Q_DBG & 8)) __builtin_amdgcn_s_barrier();
+      asm volatile("s_waitcnt vmcnt(2)" ::: "memory");
+      __builtin_amdgcn_s_barrier();
     }
   };
   int s = 0;
@@ -365,7 +353,6 @@ __global__ __launch_bounds__(256, MRG_X3Q_WPS) void rowgemm_x3q_k(GemmArgs a, co
   asm volatile("" :: "v"(xr[0][0]), "v"(xr[0][1]), "v"(xr[1][0]), "v"(xr[1][1]));
 
   const int li = lane & 31, lh = lane >> 5;
-  if ((MRG_X3Q_DBG & 1) && acc[0][0] != 123.456f) return;
   gemm_epilogue_q<EPI>(a, acc, roww, li, lh, row0 + X3Q_ROWS <= a.rows);
 }
 
@@ -377,14 +364,7 @@ inline int launch_rowgemm_x3q(GemmArgs a, const void* Bp, hipStream_t st) {
   if (a.rows <= 0) return MRG_OK;
   if (!a.A2 || a.K2 == 0) { a.A2 = a.A1; a.K2 = 0; }
   const int gbm = X3Q_ROWS;
-  if (a.grp.n > 0) {
-    a.grp.tile0[0] = 0;
-    for (int i = 0; i < 3; ++i) {
-      const int64_t r = i < a.grp.n && a.grp.hi[i] > a.grp.lo[i] ? a.grp.hi[i] - a.grp.lo[i] : 0;
-      a.grp.tile0[i + 1] = a.grp.tile0[i] + (int)((r + gbm - 1) / gbm);
-    }
-    if (a.grp.tile0[3] == 0) return MRG_OK;
-  }
+  if (a.grp.n > 0 && gemm_group_tiles(a.grp, gbm) == 0) return MRG_OK;     // grouped launch: nothing to do
   dim3 grid((unsigned)(a.grp.n > 0 ? a.grp.tile0[3] : (a.rows + gbm - 1) / gbm));
   const size_t lds = (size_t)2 * X3Q_CHUNK;
   if constexpr (EPI == EPI_SEGMAX || EPI == EPI_SEGSUM) {

@@ -19,51 +19,21 @@
 #pragma once
 #include "gemm_x3.hpp"
 
-// lab switches (tools/x3s_dbg_lab.hip, timing only -- wrong results): 1 no epilogue, 2 no A loads after the prologue,
-// 4 no B DMA after the prologue, 8 no barriers, 16 phase stamps, 64 no split arithmetic, 128 no fragment reads after the first slab,
-// 256 nothing but the epilogue, 512 the tile's stores paced through the k-loop (use with 1).  (A "no splits" switch left asynchronous register fills unconsumed and
-// faulted: every asm load's registers must be read after its wait -- see gemm_x3.hpp.)
-#ifndef MRG_X3S_DBG
-#define MRG_X3S_DBG 0
-#endif
-// lab: s_sleep(127) repetitions (~3.5 us each) the SECOND workgroup of every CU waits in the first round (blocks 256..511 share
-// their CUs with blocks 0..255 under round-robin dispatch): desynchronises the two workgroups of a CU.  0 = off.
-#ifndef MRG_X3S_STAGGER
-#define MRG_X3S_STAGGER 0
-#endif
-// 1 (round 4 lab; bit-identical, measured equal): the weight fragments of a slab's FIRST column-tile pair are read during the previous slab's LAST pair -- the
-// barrier that publishes slab s + 1 stands in front of slab s's last pair instead of behind it -- so that the LDS round trip and
-// the barrier's skew no longer open every slab (round 4; 0 = round 3's schedule).  Needs an even number of tile pairs per slab.
-#ifndef MRG_X3S_PIPE
-#define MRG_X3S_PIPE 0
-#endif
-// 1: the slabs with s + 4 < nslab run a branch-free instance of the slab body with a running activation pointer (round 4 lab;
-// bit-identical, measured equal: 0.407-0.414 vs 0.410-0.414 ms at rows 558 771 -- profiles/r4_rowgemm_phases.txt).  0 (default) = round 3's form.
-#ifndef MRG_X3S_STEADY
-#define MRG_X3S_STEADY 0
-#endif
+// Tried and dropped, each bit-identical and measured equal (profiles/r4_rowgemm_phases.txt): the barrier that publishes slab s + 1 in
+// front of slab s's last tile pair instead of behind it; a branch-free instance of the slab body with a running activation pointer for
+// the slabs with s + 4 < nslab (0.407-0.414 vs 0.410-0.414 ms at rows 558 771).  A delayed start of the second workgroup of every CU
+// changed nothing measurable either (LAB_NOTES.md).  The part-removal timings (no epilogue / A loads / B DMA / barriers / splits /
+// fragment reads, paced stores) are in profiles/r3_rowgemm_lds_weight.txt, profiles/r4_rowgemm_phases.txt and profiles/r4_rowgemm_wide8.txt.
 
 namespace mrg {
-
-// lab switch 16: per-wave phase stamps (shader clock, s_memtime) -> mrg_x3s_trace[wave slot * 24 + i]:
-// 0 start, 1 first slab, 2 + s = end of slab s (s < 16), 18 k-loop done, 19 stores issued, 20 stores landed, 21 HW_ID | XCC_ID << 32,
-// 22 / 23 the 100 MHz clock at the end / start
-#if MRG_X3S_DBG & 16
-__device__ unsigned long long* mrg_x3s_trace;
-#define MRG_X3S_STAMP(i) do { if (lane == 0) mrg_x3s_trace[trace_slot * 24 + (i)] = __builtin_amdgcn_s_memtime(); } while (0)
-#else
-#define MRG_X3S_STAMP(i) do { } while (0)
-#endif
 
 // TR: the MFMA operands change places (weight fragment first, activation fragment second), which transposes the accumulator
 // tile -- a lane then holds ONE row's columns 8g + 4 lh + {0..3} in registers 4g..4g+3 -- so that the epilogue loads and stores
 // 16 bytes per lane (gemm_epilogue_tr below): 4 * NT store instructions per strip instead of 16 * NT.  Same products, same
 // order of accumulation: bit-identical results.
-#ifndef MRG_X3S_WPS4
-#define MRG_X3S_WPS4 2      // lab: waves per SIMD the NT <= 4 instances are compiled for (3 = at most 168 registers)
-#endif
+// Two waves per SIMD for every NT (three for NT <= 4, at most 168 registers, was tried in the lab).
 template <int NT, int EPI, bool DUAL, bool TR>
-__global__ __launch_bounds__(256, (NT <= 4 ? MRG_X3S_WPS4 : 2)) void rowgemm_x3s_k(GemmArgs a, const char* __restrict__ Bp, int ntile) {
+__global__ __launch_bounds__(256, 2) void rowgemm_x3s_k(GemmArgs a, const char* __restrict__ Bp, int ntile) {
   constexpr int GBM = 128;
   constexpr int NCH = NT * 3;                   // 1 KB chunks (64 lanes x 16 B) of one pre-split B slab of this column block
   constexpr int BSLAB = NCH * 1024;
@@ -91,36 +61,13 @@ __global__ __launch_bounds__(256, (NT <= 4 ? MRG_X3S_WPS4 : 2)) void rowgemm_x3s
   const int col0 = blockIdx.y * (NT * 32);
   const int K = a.K1 + a.K2;
   const int nslab = (K + 15) >> 4;
-  if (MRG_X3S_STAGGER > 0 && blockIdx.x >= 256 && blockIdx.x < 512) {
-    for (int i = 0; i < MRG_X3S_STAGGER; ++i) __builtin_amdgcn_s_sleep(127);
-  }
 
-  [[maybe_unused]] const int64_t trace_slot = ((int64_t)blockIdx.y * gridDim.x + blockIdx.x) * 4 + wave;
-  MRG_X3S_STAMP(0);
-#if MRG_X3S_DBG & 16
-  if (lane == 0) mrg_x3s_trace[trace_slot * 24 + 23] = __builtin_amdgcn_s_memrealtime();
-#endif
   f32x16 acc[NT];
 #pragma unroll
   for (int n = 0; n < NT; ++n)
 #pragma unroll
     for (int r = 0; r < 16; ++r) acc[n][r] = 0.f;
 
-#if MRG_X3S_DBG & 256
-  // lab: nothing but the epilogue (what the store pattern alone costs at this grid and residency)
-#pragma unroll
-  for (int n = 0; n < NT; ++n)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) acc[n][r] = (float)(lane + n + r);
-  if constexpr (EPI == EPI_SEGMAX) gemm_epilogue_segmax<NT>(a, acc, roww, col0, li, lh);
-  else if constexpr (EPI == EPI_SEGSUM) gemm_epilogue_segsum<NT>(a, acc, roww, col0, li, lh);
-  else if constexpr (TR) gemm_epilogue_tr<NT, EPI>(a, acc, roww, col0, li, lh);
-  else gemm_epilogue<NT, EPI>(a, acc, roww, col0, li, lh, row0 + GBM <= a.rows);
-  return;
-#endif
-#if MRG_X3S_DBG & 512
-  float* paced_c = (roww + 32 <= a.rows && col0 + NT * 32 <= a.ldc + 31) ? a.C + (roww + 4 * lh) * a.ldc + (col0 + li < a.N ? col0 + li : a.N - 1) : nullptr;
-#endif
   // ---- A: this lane's fragment of a slab = row li, k = slab * 16 + lh * 8 + {0..3, 4..7}: two 16-byte loads
   int64_t rc = roww + li < a.rows ? roww + li : a.rows - 1;
   if (rc < 0) rc = 0;
@@ -145,14 +92,6 @@ __global__ __launch_bounds__(256, (NT <= 4 ? MRG_X3S_WPS4 : 2)) void rowgemm_x3s
     asm volatile("global_load_dwordx4 %0, %1, off" : "=v"(x[0]) : "v"(p0));
     asm volatile("global_load_dwordx4 %0, %1, off" : "=v"(x[1]) : "v"(p1));
   };
-  // steady state (slab + 3 < nslab - 1, single source): no clamp is needed, and the address is a running pointer that advances by one
-  // slab per call -- two VALU instructions instead of thirteen
-  const float* pa = ar1 + 3 * 16 + lh * 8;
-  auto load_a_run = [&](v4f (&x)[2]) {
-    asm volatile("global_load_dwordx4 %0, %1, off" : "=v"(x[0]) : "v"(pa));
-    asm volatile("global_load_dwordx4 %0, %1, off offset:16" : "=v"(x[1]) : "v"(pa));
-    pa += 16;
-  };
   // ---- B: the slab's NCH chunks, NBW per wave (the last wave repeats the last chunk: same bytes to the same place)
   const char* bcol = Bq + (int64_t)blockIdx.y * NT * 3072;
   auto fetch_b = [&](int slab, int buf) {
@@ -166,9 +105,7 @@ __global__ __launch_bounds__(256, (NT <= 4 ? MRG_X3S_WPS4 : 2)) void rowgemm_x3s
   };
   const unsigned lds0 = (unsigned)(size_t)(lds_ptr_t)smem_b + (unsigned)lane * 16u;
   u32x4 bq2[2][2][3];                                    // [double buffer][tile of the pair][plane]
-  bool lab_reads = true;                                 // lab switch 128: no fragment reads after the first slab
   auto read_b = [&](int n, int buf, u32x4 (&q)[3]) {
-    if ((MRG_X3S_DBG & 128) && !lab_reads) return;
     const unsigned ad = lds0 + (unsigned)(buf * BSLAB + n * 3072);
     asm volatile("ds_read_b128 %0, %1" : "=v"(q[0]) : "v"(ad));
     asm volatile("ds_read_b128 %0, %1 offset:1024" : "=v"(q[1]) : "v"(ad));
@@ -178,45 +115,12 @@ __global__ __launch_bounds__(256, (NT <= 4 ? MRG_X3S_WPS4 : 2)) void rowgemm_x3s
   auto split_pair_of = [&](const v4f (&x)[2], int q, u32x4& H, u32x4& M, u32x4& L) {     // q = 0..3: floats 2q, 2q + 1 of the 8
     const v4f& v = x[q >> 1];
     unsigned h, m, l;
-    if (MRG_X3S_DBG & 64) { h = __builtin_bit_cast(unsigned, (q & 1) ? v.z : v.x); m = __builtin_bit_cast(unsigned, (q & 1) ? v.w : v.y); l = h; }   // lab: no split
-    else if (q & 1) split_pair(v.z, v.w, h, m, l); else split_pair(v.x, v.y, h, m, l);
+    if (q & 1) split_pair(v.z, v.w, h, m, l); else split_pair(v.x, v.y, h, m, l);
     H[q] = h; M[q] = m; L[q] = l;
   };
   auto nb_issued = [&](int j) { return (j >= -2 && j + 2 < nslab) ? NBW : 0; };   // B DMAs issued at the top of slab j (j < 0: prologue)
-  // lab switch 512: stores a wave issues inside slab j (they count in vmcnt like the loads); 0 in the product
-  auto paced_in = [&](int j) -> int {
-#if MRG_X3S_DBG & 512
-    if (paced_c == nullptr || j < 0 || j >= nslab) return 0;
-    const int np = (NT + 1) / 2, per = (16 * NT + nslab * np - 1) / (nslab * np);
-    int n = 0;
-    for (int pp = 0; pp < np; ++pp)
-      for (int q = 0; q < 3; ++q) n += (q < per && (j * np + pp) * per + q < 16 * NT) ? 1 : 0;
-    return n;
-#else
-    (void)j;
-    return 0;
-#endif
-  };
   constexpr int NP = (NT + 1) / 2;                          // column-tile pairs per slab
-  constexpr bool PIPE = MRG_X3S_PIPE && (NP % 2 == 0);      // the pair buffers alternate across slabs: their parity must not depend on s
-  auto nbw = [&](int j) { return (j >= 1 && j < nslab) ? NBW : 0; };              // PIPE: DMAs of B(j) that stand BEHIND older A loads (B(0) leads)
 
-  if constexpr (PIPE) {
-    // issue order of a wave:  A(0) B(0) A(1) A(2) B(1) | A(3) B(2) | A(4) B(3) | ...   (slab s issues A(s+3) at its top and
-    // B(s+2) behind the barrier in front of its last pair)
-    load_a(0, xr[0]);
-    fetch_b(0, 0);
-    load_a(1, xr[1]);
-    load_a(2, xr[2]);
-    if (nslab > 1) fetch_b(1, 1);
-    wait_vmcnt(4 + nbw(1));                                  // A(0) and this wave's share of B(0) have landed
-    __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-    for (int q = 0; q < 4; ++q) split_pair_of(xr[0], q, ch, cm, cl);
-    __builtin_amdgcn_s_barrier();                            // everybody's share of B(0) is in LDS
-    read_b(0, 0, bq2[0][0]);                                 // slab 0's first pair
-    if (NT > 1) read_b(1, 0, bq2[0][1]);
-  } else {
   // ---- prologue, in the steady state's issue order: A(0) | B(0) A(1) | B(1) A(2)
   load_a(0, xr[0]);
   fetch_b(0, 0);
@@ -228,8 +132,6 @@ __global__ __launch_bounds__(256, (NT <= 4 ? MRG_X3S_WPS4 : 2)) void rowgemm_x3s
 #pragma unroll
   for (int q = 0; q < 4; ++q) split_pair_of(xr[0], q, ch, cm, cl);
   __builtin_amdgcn_s_barrier();                              // everybody's share of B(0) is in LDS
-  }
-  MRG_X3S_STAMP(1);
 
   // One k-slab; R = s % 3 at compile time (ring positions of the raw fragments and of the B buffers).
   // In-order vector-memory history of a wave at the top of slab s:  ... A(s+1) | B(s+1) A(s+2)      (B(s) in LDS: barrier)
@@ -238,57 +140,23 @@ __global__ __launch_bounds__(256, (NT <= 4 ? MRG_X3S_WPS4 : 2)) void rowgemm_x3s
   //   the splits need A(s+1): younger = B(s+1) A(s+2) B(s+2) A(s+3);
   //   end: B(s+1) must be in LDS before the barrier: younger = A(s+2) B(s+2) A(s+3).
 #define MRG_MM(AF, BF, C) (TR ? __builtin_amdgcn_mfma_f32_32x32x16_bf16(BF, AF, C, 0, 0, 0) : __builtin_amdgcn_mfma_f32_32x32x16_bf16(AF, BF, C, 0, 0, 0))
-  // ST (steady state, s + 4 < nslab): every condition and every wait count below is a compile-time constant -- the scalar branches of
-  // the run-time form cost a wave that has its SIMD's matrix pipe to itself about one MFMA slot each, ~450 of a slab's 1 800 cycles
-  // with nothing but MFMAs left in the loop (profiles/r4_rowgemm_phases.txt)
-  auto slab = [&](auto r_c, auto st_c, int s) {
+  auto slab = [&](auto r_c, int s) {
     constexpr int R = decltype(r_c)::value;
-    constexpr bool ST = decltype(st_c)::value;
-    const bool has_next = ST ? true : (s + 1 < nslab);
-    if (!PIPE && (ST || s + 2 < nslab) && !(MRG_X3S_DBG & 4)) fetch_b(s + 2, (R + 2) % 3);
-    if (!(MRG_X3S_DBG & 2)) {
-      if constexpr (ST && !DUAL) load_a_run(xr[R]);
-      else load_a(s + 3, xr[R]);
-    }
+    const bool has_next = s + 1 < nslab;
+    if (s + 2 < nslab) fetch_b(s + 2, (R + 2) % 3);
+    load_a(s + 3, xr[R]);
     // Column tiles in PAIRS: the twelve MFMAs of a pair alternate between its two accumulators (a dependent MFMA issued back to
     // back waits for its predecessor's result; with another accumulator's MFMA in between the pipe stays busy) and the VALU
     // instructions of the A split are spread between them (sched_group_barrier: 1 MFMA, then up to 3 VALU) instead of
     // standing in front of the MFMAs.  Each accumulator still receives its six terms in the same order: bit-identical results.
     constexpr int SPP = (4 + NP - 1) / NP;                    // split pairs handled in the shadow of one tile pair
-    if constexpr (PIPE) {
-      // A(s+1) is split during this slab; younger than it: B(s) [unless s == 0: B(0) leads the prologue] A(s+2) B(s+1) A(s+3)
-      if (has_next && !(MRG_X3S_DBG & 6)) wait_vmcnt(nbw(s) + 2 + nbw(s + 1) + 2);
-      if (has_next && (MRG_X3S_DBG & 6)) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    } else {
     read_b(0, R, bq2[0][0]);
     if (NT > 1) read_b(1, R, bq2[0][1]);
-    if constexpr (ST && !(MRG_X3S_DBG & 6)) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(2 * NBW + 4) : "memory");
-    else if (has_next && !(MRG_X3S_DBG & 6)) wait_vmcnt(nb_issued(s - 1) + 2 + nb_issued(s) + 2 + paced_in(s - 2) + paced_in(s - 1));
-    if (has_next && (MRG_X3S_DBG & 6)) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    }
+    if (has_next) wait_vmcnt(nb_issued(s - 1) + 2 + nb_issued(s) + 2);     // A(s+1) is split during this slab
 #pragma unroll
     for (int pp = 0; pp < NP; ++pp) {
-      constexpr int dummy = 0; (void)dummy;
       const int n0 = 2 * pp, n1 = 2 * pp + 1;
-      if (PIPE && pp + 1 == NP) {
-        // in front of the last pair: publish slab s + 1, start the DMA of slab s + 2 into the buffer slab s - 1 was read from
-        // (every wave is past that slab), and read slab s + 1's first pair
-        if (has_next) {
-          if (MRG_X3S_DBG & 6) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-          else asm volatile("s_waitcnt vmcnt(2)" ::: "memory");     // this wave's share of B(s+1): only A(s+3) is younger
-          if (!(MRG_X3S_DBG & 8)) __builtin_amdgcn_s_barrier();
-          if (s + 2 < nslab && !(MRG_X3S_DBG & 4)) fetch_b(s + 2, (R + 2) % 3);
-          read_b(0, (R + 1) % 3, bq2[(pp + 1) & 1][0]);
-          if (NT > 1) {
-            read_b(1, (R + 1) % 3, bq2[(pp + 1) & 1][1]);
-            asm volatile("s_waitcnt lgkmcnt(6)" ::: "memory");
-          } else {
-            asm volatile("s_waitcnt lgkmcnt(3)" ::: "memory");
-          }
-        } else {
-          asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        }
-      } else if (pp + 1 < NP) {
+      if (pp + 1 < NP) {
         read_b(n0 + 2, R, bq2[(pp + 1) & 1][0]);
         if (n1 + 2 < NT) {
           read_b(n1 + 2, R, bq2[(pp + 1) & 1][1]);
@@ -311,15 +179,12 @@ __global__ __launch_bounds__(256, (NT <= 4 ? MRG_X3S_WPS4 : 2)) void rowgemm_x3s
         const bf16x8 Bh1 = __builtin_bit_cast(bf16x8, bq2[pp & 1][1][0]), Bm1 = __builtin_bit_cast(bf16x8, bq2[pp & 1][1][1]),
                      Bl1 = __builtin_bit_cast(bf16x8, bq2[pp & 1][1][2]);
         // small terms first, the leading term last (same order per accumulator as rowgemm_x3_k)
-        // (lab switch 1024, timing only: the three 2^-16 terms are left out -- what a two-plane operand format would issue)
-        if (!(MRG_X3S_DBG & 1024)) {
-          acc[n0] = MRG_MM(Am, Bm0, acc[n0]);
-          acc[n1] = MRG_MM(Am, Bm1, acc[n1]);
-          acc[n0] = MRG_MM(Al, Bh0, acc[n0]);
-          acc[n1] = MRG_MM(Al, Bh1, acc[n1]);
-          acc[n0] = MRG_MM(Ah, Bl0, acc[n0]);
-          acc[n1] = MRG_MM(Ah, Bl1, acc[n1]);
-        }
+        acc[n0] = MRG_MM(Am, Bm0, acc[n0]);
+        acc[n1] = MRG_MM(Am, Bm1, acc[n1]);
+        acc[n0] = MRG_MM(Al, Bh0, acc[n0]);
+        acc[n1] = MRG_MM(Al, Bh1, acc[n1]);
+        acc[n0] = MRG_MM(Ah, Bl0, acc[n0]);
+        acc[n1] = MRG_MM(Ah, Bl1, acc[n1]);
         acc[n0] = MRG_MM(Am, Bh0, acc[n0]);
         acc[n1] = MRG_MM(Am, Bh1, acc[n1]);
         acc[n0] = MRG_MM(Ah, Bm0, acc[n0]);
@@ -327,11 +192,9 @@ __global__ __launch_bounds__(256, (NT <= 4 ? MRG_X3S_WPS4 : 2)) void rowgemm_x3s
         acc[n0] = MRG_MM(Ah, Bh0, acc[n0]);
         acc[n1] = MRG_MM(Ah, Bh1, acc[n1]);
       } else {
-        if (!(MRG_X3S_DBG & 1024)) {
-          acc[n0] = MRG_MM(Am, Bm0, acc[n0]);
-          acc[n0] = MRG_MM(Al, Bh0, acc[n0]);
-          acc[n0] = MRG_MM(Ah, Bl0, acc[n0]);
-        }
+        acc[n0] = MRG_MM(Am, Bm0, acc[n0]);
+        acc[n0] = MRG_MM(Al, Bh0, acc[n0]);
+        acc[n0] = MRG_MM(Ah, Bl0, acc[n0]);
         acc[n0] = MRG_MM(Am, Bh0, acc[n0]);
         acc[n0] = MRG_MM(Ah, Bm0, acc[n0]);
         acc[n0] = MRG_MM(Ah, Bh0, acc[n0]);
@@ -342,22 +205,6 @@ __global__ __launch_bounds__(256, (NT <= 4 ? MRG_X3S_WPS4 : 2)) void rowgemm_x3s
         __builtin_amdgcn_sched_group_barrier(0x002, 3, 0);     // ... then up to three VALU
       }
       __builtin_amdgcn_sched_barrier(0);
-#if MRG_X3S_DBG & 512
-      // lab (timing only, wrong results): the tile's 16 * NT dword stores PACED through the k-loop -- two or three behind every tile
-      // pair, every (tile, register) address of the strip written once per tile -- instead of the burst behind it (switch 1 drops that)
-      if (paced_c != nullptr) {
-        const int slot = s * NP + pp;                       // 0 .. nslab * NP - 1
-        const int per = (16 * NT + nslab * NP - 1) / (nslab * NP);
-#pragma unroll
-        for (int j = 0; j < 3; ++j) {
-          const int idx = slot * per + j;                   // which (tile, register) of the strip: run-time, only the address depends on it
-          if (j < per && idx < 16 * NT) {
-            const int tn = idx >> 4, tr = idx & 15;
-            paced_c[(int64_t)((tr & 3) + 8 * (tr >> 2)) * a.ldc + tn * 32] = acc[(pp * 2 + (j & 1)) % NT][(R * 4 + j) & 15];
-          }
-        }
-      }
-#endif
     }
     if (NT < 4 && has_next) {
 #pragma unroll
@@ -365,54 +212,26 @@ __global__ __launch_bounds__(256, (NT <= 4 ? MRG_X3S_WPS4 : 2)) void rowgemm_x3s
     }
     if (has_next) {
       ch = nh; cm = nm; cl = nl;
-      if constexpr (!PIPE) {
-      if constexpr (ST && !(MRG_X3S_DBG & 6)) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(NBW + 4) : "memory");
-      else if (!(MRG_X3S_DBG & 6)) wait_vmcnt(2 + nb_issued(s) + 2 + paced_in(s - 1) + paced_in(s));     // this wave's share of B(s+1) is in LDS
-      else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      if (!(MRG_X3S_DBG & 8)) __builtin_amdgcn_s_barrier();   // ... and everybody's; all reads of this slab's buffer are done
-      }
+      wait_vmcnt(2 + nb_issued(s) + 2);                      // this wave's share of B(s+1) is in LDS
+      __builtin_amdgcn_s_barrier();                          // ... and everybody's; all reads of this slab's buffer are done
     }
-#if MRG_X3S_DBG & 16
-    if (s < 16) MRG_X3S_STAMP(2 + s);
-#endif
-    if (MRG_X3S_DBG & 128) lab_reads = false;
   };
 #undef MRG_MM
   int s = 0;
-  constexpr bool STEADY = MRG_X3S_STEADY && !PIPE;
-  if constexpr (STEADY) {
-    for (; s + 6 < nslab; s += 3) {             // all three slabs satisfy s' + 4 < nslab
-      slab(std::integral_constant<int, 0>{}, std::true_type{}, s);
-      slab(std::integral_constant<int, 1>{}, std::true_type{}, s + 1);
-      slab(std::integral_constant<int, 2>{}, std::true_type{}, s + 2);
-    }
-  }
   for (; s + 2 < nslab; s += 3) {
-    slab(std::integral_constant<int, 0>{}, std::false_type{}, s);
-    slab(std::integral_constant<int, 1>{}, std::false_type{}, s + 1);
-    slab(std::integral_constant<int, 2>{}, std::false_type{}, s + 2);
+    slab(std::integral_constant<int, 0>{}, s);
+    slab(std::integral_constant<int, 1>{}, s + 1);
+    slab(std::integral_constant<int, 2>{}, s + 2);
   }
-  if (s < nslab) { slab(std::integral_constant<int, 0>{}, std::false_type{}, s); ++s; }
-  if (s < nslab) { slab(std::integral_constant<int, 1>{}, std::false_type{}, s); ++s; }
+  if (s < nslab) { slab(std::integral_constant<int, 0>{}, s); ++s; }
+  if (s < nslab) { slab(std::integral_constant<int, 1>{}, s); ++s; }
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");            // the tail's unused A fills: their registers must stay until they land
   asm volatile("" :: "v"(xr[0][0]), "v"(xr[0][1]), "v"(xr[1][0]), "v"(xr[1][1]), "v"(xr[2][0]), "v"(xr[2][1]));
 
-  MRG_X3S_STAMP(18);
-  if ((MRG_X3S_DBG & 1) && acc[0][0] != 123.456f) return;
   if constexpr (EPI == EPI_SEGMAX) gemm_epilogue_segmax<NT>(a, acc, roww, col0, li, lh);
   else if constexpr (EPI == EPI_SEGSUM) gemm_epilogue_segsum<NT>(a, acc, roww, col0, li, lh);
   else if constexpr (TR) gemm_epilogue_tr<NT, EPI>(a, acc, roww, col0, li, lh);
   else gemm_epilogue<NT, EPI>(a, acc, roww, col0, li, lh, row0 + GBM <= a.rows);
-#if MRG_X3S_DBG & 16
-  MRG_X3S_STAMP(19);
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  MRG_X3S_STAMP(20);
-  if (lane == 0) {
-    mrg_x3s_trace[trace_slot * 24 + 21] = (unsigned long long)__builtin_amdgcn_s_getreg(4 | (31 << 11))            // HW_REG_HW_ID
-                                        | ((unsigned long long)__builtin_amdgcn_s_getreg(20 | (31 << 11)) << 32);   // HW_REG_XCC_ID
-    mrg_x3s_trace[trace_slot * 24 + 22] = __builtin_amdgcn_s_memrealtime();
-  }
-#endif
 }
 
 inline bool x3s_eligible(const GemmArgs& a) { return x3_eligible(a) && a.rows > 0; }
@@ -425,19 +244,9 @@ inline int launch_rowgemm_x3s(GemmArgs a, const void* Bp, hipStream_t st) {
   const int nt = gemm_pick_nt(a.N);
   const int ntile = x3_tiles(a.N, nt);
   const int gbm = 128;
-  if (a.grp.n > 0) {
-    a.grp.tile0[0] = 0;
-    for (int i = 0; i < 3; ++i) {
-      const int64_t r = i < a.grp.n && a.grp.hi[i] > a.grp.lo[i] ? a.grp.hi[i] - a.grp.lo[i] : 0;
-      a.grp.tile0[i + 1] = a.grp.tile0[i] + (int)((r + gbm - 1) / gbm);
-    }
-    if (a.grp.tile0[3] == 0) return MRG_OK;
-  }
+  if (a.grp.n > 0 && gemm_group_tiles(a.grp, gbm) == 0) return MRG_OK;     // grouped launch: nothing to do
   dim3 grid((unsigned)(a.grp.n > 0 ? a.grp.tile0[3] : (a.rows + gbm - 1) / gbm), (unsigned)(ntile / nt));
   size_t lds = (size_t)3 * nt * 3 * 1024;
-#if MRG_X3S_DBG
-  if (getenv("MRG_X3S_LDS_EXTRA")) lds += (size_t)atoi(getenv("MRG_X3S_LDS_EXTRA"));     // lab: one workgroup per CU
-#endif
   bool tr = false;
   if constexpr (EPI != EPI_SEGMAX && EPI != EPI_SEGSUM) tr = gemm_epi_mode() == 2 && gemm_epilogue_tr_ok<EPI>(a);
 #define MRG_GOS3(NTV, DV, TV)                                                                                         \

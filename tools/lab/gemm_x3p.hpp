@@ -96,7 +96,7 @@ __global__ __launch_bounds__(X3_THREADS, 1) void rowgemm_x3p_k(GemmArgs a, const
     for (int i = 0; i < NA; ++i) {
       const int r = row_base + 16 * i;
       const float* p = src + (int64_t)(r < last_row ? r : last_row) * ld + kc;
-      __builtin_amdgcn_global_load_lds((gbl_ptr_t)p, (lds_ptr_t)(dst + 64 * i * 4), 16, 0, MRG_A_CPOL);
+      __builtin_amdgcn_global_load_lds((gbl_ptr_t)p, (lds_ptr_t)(dst + 64 * i * 4), 16, 0, 0);
     }
   };
   const unsigned lds_ring = (unsigned)(size_t)(lds_ptr_t)ring;
@@ -197,7 +197,7 @@ __global__ __launch_bounds__(X3_THREADS, 1) void rowgemm_x3p_k(GemmArgs a, const
 #pragma unroll
       for (int i = 0; i < 6 * MT; ++i) {
         __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-        __builtin_amdgcn_sched_group_barrier(0x002, MRG_X3_VPM, 0);
+        __builtin_amdgcn_sched_group_barrier(0x002, X3_VPM, 0);
       }
       __builtin_amdgcn_sched_barrier(0);
       load_b(n, s1);

@@ -17,6 +17,11 @@
 #pragma once
 #include "gemm_x3.hpp"
 
+// part-removal switches of this kernel and of gemm_x3p.hpp (timing only -- wrong results): 1 no epilogue, 4 no A DMA after the first
+// slab, 32 no B loads after the first slab, 64 no split after the first slab
+#ifndef MRG_X3_DBG
+#define MRG_X3_DBG 0
+#endif
 // s_sleep(127) repetitions (~3.8 us each) the second workgroup of a CU waits in the first round; 0 = off
 #ifndef MRG_X3W_MAP
 #define MRG_X3W_MAP 0
@@ -30,7 +35,7 @@ namespace mrg {
 // one wave: rows [roww, roww + 64) x column tiles [tile0, tile0 + NT)
 template <int NT, int EPI, bool DUAL>
 __device__ __forceinline__ void x3w_wave_tile(const GemmArgs& a, const char* __restrict__ Bp, int ntile, int64_t roww, int tile0,
-                                              float* ring, int lane, bool full, int64_t trace_slot) {
+                                              float* ring, int lane, bool full) {
   constexpr int MT = 2, WROWS = 64;
   constexpr int SLOT_CH = WROWS * 4;          // 16-byte chunks per ring slot
   constexpr int NA = SLOT_CH / 64;            // DMA instructions per slab (4)
@@ -42,7 +47,6 @@ __device__ __forceinline__ void x3w_wave_tile(const GemmArgs& a, const char* __r
   const int K = a.K1 + a.K2;
   const int nslab = (K + 15) >> 4;
 
-  MRG_X3_STAMP(trace_slot, 0);
   f32x16 acc[MT][NT];
 #pragma unroll
   for (int m = 0; m < MT; ++m)
@@ -128,7 +132,6 @@ __device__ __forceinline__ void x3w_wave_tile(const GemmArgs& a, const char* __r
     if (do_dma && !((MRG_X3_DBG & 4) && s > 0)) fetch_a(s + 3);                       // slot (s+3)%4 held slab s-1, whose fragments were consumed a slab ago
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     __builtin_amdgcn_sched_barrier(0);
-    if ((MRG_X3_DBG & 512) && s == 0) MRG_X3_STAMP(trace_slot, 1);
     if (!((MRG_X3_DBG & 64) && s > 0))
 #pragma unroll
     for (int m = 0; m < MT; ++m)
@@ -167,11 +170,9 @@ __device__ __forceinline__ void x3w_wave_tile(const GemmArgs& a, const char* __r
   slab(std::integral_constant<int, 1>{}, nslab - 3);
   slab(std::integral_constant<int, 2>{}, nslab - 2);
   slab(std::integral_constant<int, 3>{}, nslab - 1);
-  MRG_X3_STAMP(trace_slot, 2);
   if ((MRG_X3_DBG & 1) && acc[0][0][0] != 123.456f) return;
 #pragma unroll
   for (int m = 0; m < MT; ++m) gemm_epilogue<NT, EPI>(a, acc[m], roww + m * 32, tile0 * 32, li, lh, full);
-  if (MRG_X3_DBG & 512) { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); MRG_X3_STAMP(trace_slot, 3); }
 }
 
 // grid.x = 2 * (row blocks rounded up to 8): id -> (xcd = id % 8, j = id / 8): column half j & 1 of row block (j >> 1) * 8 + xcd,
@@ -204,9 +205,8 @@ __global__ __launch_bounds__(X3_THREADS, 2) void rowgemm_x3w_k(GemmArgs a, const
   }
   float* ring = smem + wave * (X3_SLOTS * 64 * 4 * 4);
   const bool full = row0 + 256 <= a.rows;
-  [[maybe_unused]] const int64_t trace_slot = ((int64_t)blockIdx.y * gridDim.x + blockIdx.x) * 4 + wave;
-  if (half == 0) x3w_wave_tile<4, EPI, DUAL>(a, Bp, ntile, roww, tile0, ring, lane, full, trace_slot);
-  else x3w_wave_tile<3, EPI, DUAL>(a, Bp, ntile, roww, tile0, ring, lane, full, trace_slot);
+  if (half == 0) x3w_wave_tile<4, EPI, DUAL>(a, Bp, ntile, roww, tile0, ring, lane, full);
+  else x3w_wave_tile<3, EPI, DUAL>(a, Bp, ntile, roww, tile0, ring, lane, full);
 }
 
 // operands the kernel is built for: B split for blocks of seven tiles (gemm_pick_nt == 7), enough rows to fill the chip twice

@@ -6,9 +6,9 @@
 #   tools/lab/kernel_lab.sh run TAG BIN 'ARGS' ['ARGS' ...]       run the binary once per argument list, output under gpurun_out/TAG/
 #   tools/lab/kernel_lab.sh libs NAME=-DSWITCH=V:a.hip,b.hip [...]  one libmrgnas per lab switch -> tools/labso/libmrgnas_NAME.so (MRG_LIB_PATH selects it)
 #
-# Examples: phase stamps of the shipped row GEMM        kernel_lab.sh build tools/x3s_trace_lab.hip; kernel_lab.sh run stamps x3s_trace_lab '558771 200 200' '558771 400 200'
-#           rowgemm_x3q_k with one part removed at a time  kernel_lab.sh libs noepi=-DMRG_X3Q_DBG=1:linear.hip,dense.hip noa=-DMRG_X3Q_DBG=2:linear.hip,dense.hip
-#                                                          then  tools/lab/ab.sh parts 'MRG_LIB_PATH=tools/labso/libmrgnas_noepi.so' ... -- python tools/rowgemm_ab.py
+# Examples: time and bit identity of the row-GEMM kernels  kernel_lab.sh build tools/gemm_x3_lab.hip; kernel_lab.sh run x3 gemm_x3_lab '558771 200 200 200' '558771 400 0 200'
+#           a library with other scalar-row span bounds      kernel_lab.sh libs um8=-DMRG_SPAN_UM=8:fused_gcs.hip um2=-DMRG_SPAN_UM=2:fused_gcs.hip
+#                                                          then  tools/lab/ab.sh spans 'MRG_LIB_PATH=tools/labso/libmrgnas_um8.so' ... -- --steps 10 --warmup 3 --no-cpu-baseline
 set -eu
 R=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/../.." && pwd)}
 cd "$R"
