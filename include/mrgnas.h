@@ -38,7 +38,9 @@ extern "C" {
 
 #define MRG_OK            0
 #define MRG_E_NULLPTR    -1   /* a required pointer is NULL */
-#define MRG_E_SHAPE      -2   /* negative size, or a size the kernels do not cover (D > 1024, or D > 256 with D % 4 != 0) */
+#define MRG_E_SHAPE      -2   /* negative size, or a size the kernels do not cover: D > 1024, or D > 256 with D % 4 != 0, or D > 256
+                                * with a row pointer (inputs, output, workspace) that is not 16-byte aligned -- the scalar lanes
+                                * that serve such rows cover 256 columns */
 #define MRG_E_ENUM       -3   /* unknown op / mode / act code */
 #define MRG_E_WORKSPACE  -4   /* workspace pointer missing */
 

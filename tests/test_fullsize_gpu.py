@@ -170,11 +170,21 @@ def test_distmult_full_batch_checksum(kg):
     assert abs(float(score.double().sum()) - ref_sum) <= 1e-6 * ref_abs
 
 
-@pytest.mark.parametrize("fn_", ["sub", "mul"])
+def corr64_host(a, b, block=1 << 16):
+    """ccorr of device rows in float64 through the host FFT (gcs_ref.corr64), 2^16 rows at a time: no [E, D] float64 FFT
+    input beyond ~100 MB."""
+    from gcs_ref import corr64
+    out = torch.empty_like(a)
+    for lo in range(0, a.shape[0], block):
+        out[lo:lo + block] = corr64(a[lo:lo + block].cpu(), b[lo:lo + block].cpu()).to(a.device)
+    return out
+
+
+@pytest.mark.parametrize("fn_", ["sub", "mul", "ccorr"])
 def test_comp_graph_conv_full_graph(kg, fn_):
     """CompGraphConv (reference models/compgcn.py:48-113) on the full graph, batch norm off, dropout off, against the
     same layer written with torch indexing / index_add_ in float64 on the device (every edge, both directions,
-    self loop, the 1/3 scale and tanh)."""
+    self loop, the 1/3 scale and tanh; the ccorr message through the float64 FFT on the host)."""
     from mr_gnas_amd import compgcn as C
     N, E, R = kg["N"], kg["E"], kg["R"]
     g = G.RelGraph(N, kg["src"], kg["dst"], device=DEV)
@@ -189,7 +199,7 @@ def test_comp_graph_conv_full_graph(kg, fn_):
         n_out, r_out = layer(g, n_in, r_in)
         r_all = torch.cat((r_in, layer.loop_rel), 0).double()
         h = n_in.double()
-        comp = (lambda a, b: a - b) if fn_ == "sub" else (lambda a, b: a * b)
+        comp = {"sub": lambda a, b: a - b, "mul": lambda a, b: a * b, "ccorr": corr64_host}[fn_]
         ef = r_all[kg["etype"].long()] * g.edata["norm"].double().view(-1, 1)
         msg = comp(h[kg["src"].long()], ef)
         msg = torch.where(in_mask.view(-1, 1), msg @ layer.W_I.weight.double().t() + layer.W_I.bias.double(),
