@@ -25,6 +25,9 @@
 namespace mrg {
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
+typedef float v4f __attribute__((ext_vector_type(4)));
+typedef __attribute__((address_space(3))) void* lds_ptr_t;             // LDS-DMA destination / LDS byte address of a __shared__ object
+typedef const __attribute__((address_space(1))) void* gbl_ptr_t;       // LDS-DMA source
 
 constexpr int GBM_MAX = 256;      // rows per workgroup = 128 * MT (MT row tiles of 32 per wave)
 
@@ -76,6 +79,19 @@ struct GemmArgs {
   int epi_lds; int wave_lds_floats;
   GemmGroups grp;                     // split core, one-wave kernel only
 };
+
+// The 4 floats at column k of the concatenated row [r1 (K1 floats) | r2 (K2 floats)] (DUAL) or of r1 alone (K floats), clamped
+// into the row: beyond the end a chunk re-reads the row's last 4 floats -- any finite values, the weight's rows there are zero.
+// Used by every kernel that fetches activations in 16-byte chunks (rowgemm_dma_k and the split-core kernels).
+template <bool DUAL>
+__device__ __forceinline__ const float* gemm_a_ptr(const float* r1, const float* r2, int K1, int K2, int K, int k) {
+  if (DUAL) {
+    const bool first = k < K1;
+    const int kk = first ? k : k - K1, ld = first ? K1 : K2;
+    return (first ? r1 : r2) + (kk + 4 <= ld ? kk : ld - 4);
+  }
+  return r1 + (k + 4 <= K ? k : K - 4);
+}
 
 // ---- a_max: ReLU + destination-segmented max as the GEMM's epilogue (reference models/operations_lp.py:230-234) ----------
 // The GEMM walks the edges in destination order (row_index = the by-destination edge list), so the 32 rows of an accumulator
@@ -635,8 +651,6 @@ __global__ __launch_bounds__(MRG_BLOCK, 2) void rowgemm_dma_k(GemmArgs a) {
   constexpr int NA = GBM * F4R / MRG_BLOCK, NBT = NT * 32 * F4R, NB = (NBT + MRG_BLOCK - 1) / MRG_BLOCK;
   extern __shared__ __align__(16) float smem[];
   constexpr int A_TILE = GBM * GLD, B_TILE = NT * 32 * GLD, STAGE = A_TILE + B_TILE;
-  typedef __attribute__((address_space(3))) void* lds_ptr_t;
-  typedef const __attribute__((address_space(1))) void* gbl_ptr_t;
   const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, li = lane & 31, lh = lane >> 5;
   const int64_t row0 = (int64_t)blockIdx.x * GBM;
   const int col0 = blockIdx.y * (NT * 32);
@@ -669,14 +683,7 @@ __global__ __launch_bounds__(MRG_BLOCK, 2) void rowgemm_dma_k(GemmArgs a) {
     for (int i = 0; i < NA; ++i) {
       const int f = tid + i * MRG_BLOCK;
       const int k = k0 + (f % F4R) * 4;
-      const float* p;
-      if (DUAL) {
-        const bool first = k < a.K1;
-        const int kk = first ? k : k - a.K1, ld = first ? a.K1 : a.K2;
-        p = (first ? arow1[i] : arow2[i]) + (kk + 4 <= ld ? kk : ld - 4);
-      } else {
-        p = arow1[i] + (k + 4 <= K ? k : K - 4);
-      }
+      const float* p = gemm_a_ptr<DUAL>(arow1[i], arow2[i], a.K1, a.K2, K, k);
       __builtin_amdgcn_global_load_lds((gbl_ptr_t)p, (lds_ptr_t)(smem + buf * STAGE + (f - lane) * 4), 16, 0, 0);
     }
 #pragma unroll
@@ -694,7 +701,6 @@ __global__ __launch_bounds__(MRG_BLOCK, 2) void rowgemm_dma_k(GemmArgs a) {
   // first ds_read that follows a global_load_lds (it assumes the DMA may alias it), which would drain the
   // DMA of the NEXT tile before this tile's MFMAs start.  Hazards are handled by hand: the reads only touch
   // the buffer whose DMA was waited for (vmcnt(0)) before the barrier that ended the previous iteration.
-  typedef float v4f __attribute__((ext_vector_type(4)));
   const unsigned lds0 = (unsigned)(size_t)(lds_ptr_t)smem;
   const unsigned a_off = (unsigned)(((wave * 32 + li) * GLD + lh * 4) * sizeof(float));
   const unsigned b_off = (unsigned)((A_TILE + li * GLD + lh * 4) * sizeof(float));

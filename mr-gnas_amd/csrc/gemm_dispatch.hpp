@@ -1,6 +1,14 @@
-// Dispatch between the two matrix cores of the tall-skinny GEMM (gemm.hpp: exact f32; gemm_x3.hpp / gemm_x3s.hpp: split bf16).
-// Rounds 2-3 also carried a persistent transposed-accumulator kernel (mode 3) and a two-waves-per-SIMD kernel (mode 4) as tested
-// comparison points; both lost to gemm_x3s.hpp and live in tools/lab/ since round 4 (tools/gemm_x3_lab.hip still times them).
+// Which kernel a row GEMM launch takes.  Two matrix cores:
+//   gemm.hpp        exact f32 (v_mfma_f32_32x32x2_f32): rowgemm_dma_k / rowgemm_k.  Mode 1, operands the split core cannot take, no workspace.
+//   split bf16      (arithmetic, weight split and every shared part: x3_parts.hpp), four kernels that agree bit for bit unless noted:
+//     gemm_x3s.hpp   rowgemm_x3s_k   the default: weight slabs shared through LDS, 128-row workgroups, two per CU; grouped launches,
+//                                    dual source, the fused aggregators' epilogues; outputs up to 7 column tiles per block
+//     gemm_x3s8.hpp  rowgemm_x3s8_k  plain single-source launches of 225..256 columns (D = 256) as ONE block of eight tiles
+//     gemm_x3q.hpp   rowgemm_x3q_k   16 x 16 x 32 tiles, 64-row workgroups, three per CU: 129..224 columns with K > X3Q_MIN_K
+//                                    (sums 32 k at a time: agrees with the others to rounding, not bit for bit)
+//     gemm_x3.hpp    rowgemm_x3_k    wave-autonomous, one wave per SIMD: few rows (<= X3N_MAX_ROWS, two-tile column blocks) and mode 2
+// The persistent transposed-accumulator kernel and the two-waves-per-SIMD kernel of rounds 2-3 live in tools/lab/ (tools/gemm_x3_lab.hip
+// still times them).  The switches that move a launch off its default kernel are GemmSwitches (x3_parts.hpp).
 #pragma once
 #include "gemm_x3.hpp"
 #include "gemm_x3s.hpp"
@@ -9,15 +17,11 @@
 
 namespace mrg {
 
-// ---- dispatch between the two cores ---------------------------------------------------------------
-// mode 0 (default): split-bf16 core whenever the operands qualify and a workspace was given;
-// mode 1: exact-f32 core only (v_mfma_f32_32x32x2_f32) -- the comparison point of the tests and of bench.py.
-// mode 2: the same arithmetic on the wave-autonomous one-wave-per-SIMD kernel of gemm_x3.hpp (rounds 1-2's default).
-// Since round 3 the default split-core kernel is gemm_x3s.hpp (weight slabs shared through LDS, 128-row workgroups, two per
-// CU): bit-identical results; alone 0.191 vs 0.22-0.23 ms at rows 272 115, K = N = 200 and equal at 558 771 rows, but inside the
-// supernet step every row-GEMM entry point gains 9-22 % (input gradients 10.3 -> 8.4 ms, fused a_max / a_mean 4.1 -> 3.2,
-// dense-filter forward 6.5 -> 5.9; 68.2 -> 65.5 ms / step, profiles/r3_rowgemm_lds_weight.txt).
-inline int& gemm_mode() { static int m = 0; return m; }
+// Since round 3 the default split-core kernel is gemm_x3s.hpp: bit-identical with gemm_x3.hpp; alone 0.191 vs 0.22-0.23 ms at rows
+// 272 115, K = N = 200 and equal at 558 771 rows, but inside the supernet step every row-GEMM entry point gains 9-22 % (input
+// gradients 10.3 -> 8.4 ms, fused a_max / a_mean 4.1 -> 3.2, dense-filter forward 6.5 -> 5.9; 68.2 -> 65.5 ms / step,
+// profiles/r3_rowgemm_lds_weight.txt).
+inline int gemm_mode() { return gemm_switches().mode; }
 
 // Which launches take the 16 x 16 x 32 kernel of gemm_x3q.hpp (round 5): a pure function of the epilogue kind and of the product's
 // shape, so that the code that prepares the weight split and the code that launches the GEMM agree without talking.  Its column
@@ -26,11 +30,11 @@ inline int& gemm_mode() { static int m = 0; return m; }
 // Measured (profiles/r5_rowgemm_q.txt, rows 558 771, interleaved rounds in one process): at K = 400 (the dense filters' forward on
 // two operands, the paired input gradient) 0.552 vs 0.584 ms (-5 %), gate-only forward -7..-12 %; at K = 200 equal (0.986-1.017): the
 // reduction dimension has to be long enough for the smaller tile's doubled weight traffic (L2 -> LDS 2.6 GB instead of 1.2 GB per
-// launch) to be paid back, so gemm_q() == 1 (default) takes only K > X3Q_MIN_K; 2 (lab) takes every K > 48.
+// launch) to be paid back, so switch q == 1 (default) takes only K > X3Q_MIN_K; 2 (lab) takes every K > 48.
 constexpr int X3Q_MIN_K = 224;
 inline bool x3q_shape(int epi, int N, int K) {
-  return gemm_mode() == 0 && gemm_q() != 0 && epi != EPI_SEGMAX && epi != EPI_SEGSUM && N > 128 && N <= X3Q_NT * 16
-         && K > (gemm_q() == 2 ? 48 : X3Q_MIN_K);
+  const int q = gemm_switches().q;
+  return gemm_mode() == 0 && q != 0 && epi != EPI_SEGMAX && epi != EPI_SEGSUM && N > 128 && N <= X3Q_NT * 16 && K > (q == 2 ? 48 : X3Q_MIN_K);
 }
 
 // FEW ROWS (round 5: the sampled search step of graph_batch_size 300, a rank's node chunk).  A 128-row workgroup of rowgemm_x3s_k
@@ -40,11 +44,9 @@ inline bool x3q_shape(int epi, int N, int K) {
 // the k-sum per output element: bit-identical with rowgemm_x3s_k (tests/test_ops_gpu.py::test_few_rows_row_gemm_is_bit_exact), so a
 // grouped launch and its per-range launches may fall on different sides of the bound.  Not for the shapes of rowgemm_x3q_k (another
 // summation order: those keep one kernel for every row count).  mrg_gemm_set_small(0) switches it off.
-constexpr int64_t X3N_MAX_ROWS = 16384;     // measured crossover (linear 200 x 200, one MI355X): 13 vs 24 us at 4 096 rows, 19 vs 27 at 16 384, 31 vs 30 at 32 768
-constexpr int X3N_NT = 2;
-inline int64_t& gemm_small() { static int64_t m = X3N_MAX_ROWS; return m; }     // the row bound; 0 = off (mrg_gemm_set_small)
+constexpr int X3N_NT = 2;                   // (the default row bound X3N_MAX_ROWS is next to the switch: x3_parts.hpp)
 inline bool x3n_shape(int epi, int64_t rows, int N, int K) {
-  return gemm_mode() == 0 && rows > 0 && rows <= gemm_small() && gemm_pick_nt(N) > X3N_NT && N <= 224 && !x3q_shape(epi, N, K);
+  return gemm_mode() == 0 && rows > 0 && rows <= gemm_switches().small_rows && gemm_pick_nt(N) > X3N_NT && N <= 224 && !x3q_shape(epi, N, K);
 }
 
 // bytes of ONE pre-split weight in whichever layout a launch of this shape may use

@@ -1,144 +1,23 @@
-// Tall-skinny GEMM core on the bf16 matrix pipe with f32-equivalent accuracy ("3-way split").
+// Tall-skinny GEMM on the bf16 matrix pipe with f32-equivalent accuracy ("3-way split"): the wave-autonomous kernel.
 //
 //   C[rows, N] = epilogue( [A1 | A2][rows, K1+K2] * B[N, K1+K2]^T )          (same contract as gemm.hpp)
 //
-// Every f32 operand is written as the exact-to-2^-26 sum of three bf16 numbers,
-//   x = h + m + l,   h = bf16(x),  m = bf16(x - h),  l = bf16(x - h - m)       (round-to-nearest-even each)
-// and a product is evaluated as the six leading cross terms, accumulated in f32 by the MFMA:
-//   a*b ~= ah*bh + ah*bm + am*bh + ah*bl + al*bh + am*bm        dropped: am*bl + al*bm + al*bl  (<= 2^-25 |a b|)
-// so the result carries an error below one f32 ulp of each product -- the same class as the f32 pipe
-// (tests pin |err| against a float64 product next to the exact-f32 kernel).  Why: v_mfma_f32_32x32x2_f32
-// retires 64 flop/cycle/SIMD (157 TF/s chip peak), v_mfma_f32_32x32x16_bf16 1024; six bf16 MFMAs replace
-// eight f32 MFMAs per 16 k-columns at 1/16 of the cycles each: 2.7x less matrix-pipe time for the same
-// answer.  The price is VALU work for the splits, which is why
-//   * B (a weight matrix, a few hundred KB) is split ONCE per call by bsplit3_k into fragment order
-//     ([k-slab][column tile][plane][lane][8 bf16], one ds_read_b128 per fragment, conflict free), and
+// The arithmetic (three bf16 planes per f32 operand, six cross terms per product), the weight split and every other part this
+// kernel shares with its siblings are in x3_parts.hpp.
+//   * B (a weight matrix, a few hundred KB) is split ONCE per call by bsplit_k into fragment order
+//     ([k-slab][column tile][plane][lane][8 bf16], one 16-byte load per fragment and plane), and
 //   * A (activations, read once from HBM as f32 by LDS-DMA) is split in registers right after its
 //     fragment read: 44 VALU instructions per 16 k-columns per wave against 6*NT MFMAs.
-// Geometry as gemm.hpp: 256 threads own 128 rows x NT*32 columns, wave w owns rows [32w, 32w+32); two
-// workgroups per CU; k walked in slabs of 16 with double-buffered LDS-DMA.  The DMA writes LDS linearly
-// (wave base + lane*16 B), so the A tile is swizzled by choosing WHICH global chunk each lane fetches:
+// Geometry as gemm.hpp: 256 threads own 128 rows x NT*32 columns, wave w owns rows [32w, 32w+32); k walked in slabs of 16.
+// The DMA writes LDS linearly (wave base + lane*16 B), so the A tile is swizzled by choosing WHICH global chunk each lane fetches:
 // chunk (row, c) lives at 16-byte slot row*4 + (c ^ ((row >> 2) & 3)), which makes the fragment reads
 // (8 consecutive k per lane = two ds_read_b128) bank-conflict free.
 #pragma once
-#include <type_traits>
-#include "gemm.hpp"
+#include "x3_parts.hpp"
 
 namespace mrg {
 
 constexpr int X3_VPM = 3;     // VALU instructions the scheduler may place after each MFMA of a tile (lab sweep: 2 / 3 / 4 / 6)
-
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-
-// two floats -> three packed bf16 pairs (element 0 in the low half).
-// The residual subtractions are spelled as single v_sub_f32: hipcc would SLP-pack the pair into v_pk_add_f32,
-// which costs ~13 cycles of matrix-pipe time each when issued beside MFMAs (MI355X_MICROARCH.md, "price of one
-// filler"), against ~0 for a plain 4-cycle VALU instruction.
-__device__ __forceinline__ float sub1(float a, float b) {
-  float r;
-  asm("v_sub_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
-  return r;
-}
-__device__ __forceinline__ void split_pair(float x0, float x1, unsigned& h, unsigned& m, unsigned& l) {
-  f32x2 v = {x0, x1};
-  h = __builtin_bit_cast(unsigned, __builtin_convertvector(v, bf16x2));
-  f32x2 r = {sub1(x0, __builtin_bit_cast(float, h << 16)), sub1(x1, __builtin_bit_cast(float, h & 0xffff0000u))};
-  m = __builtin_bit_cast(unsigned, __builtin_convertvector(r, bf16x2));
-  f32x2 r2 = {sub1(r.x, __builtin_bit_cast(float, m << 16)), sub1(r.y, __builtin_bit_cast(float, m & 0xffff0000u))};
-  l = __builtin_bit_cast(unsigned, __builtin_convertvector(r2, bf16x2));
-}
-
-inline int x3_tiles(int N, int nt) { return ((N + nt * 32 - 1) / (nt * 32)) * nt; }     // column tiles, padded to blocks of nt
-inline int x3_slabs(int K) { return (K + 15) / 16; }
-inline size_t x3_bsplit_bytes(int N, int K, int nt) { return (size_t)x3_slabs(K) * x3_tiles(N, nt) * 3 * 64 * 16; }
-
-// B(n, k) = B[n * sn + k * sk]  ->  Bp[slab][tile][plane][lane] (16 B = 8 bf16: n = tile*32 + lane%32,
-// k = slab*16 + (lane/32)*8 + j).  Rows >= N and columns >= K are zero, which is also what makes the
-// clamped out-of-range A chunks harmless.  sk != 1 presents W^T without a transpose pass.
-// Up to three weights of the same shape in one launch (blockIdx.y): the direction segments of a dense filter.
-// Optional second source along k (the input gradient of two candidates in one product, [dz_a | dz_b] [W_a ; W_b]):
-// columns k >= ksplit come from B2 at k - ksplit (ksplit = 0: single source).
-struct BSplit3 { const float* B[3]; u32x4* out[3]; const float* B2[3]; int ksplit; };
-static __global__ void bsplit3_k(BSplit3 p, int64_t sn, int64_t sk, int N, int K, int ntile, int nslab) {
-  const float* __restrict__ B = p.B[blockIdx.y];
-  const float* __restrict__ B2 = p.B2[blockIdx.y];
-  const int ksplit = (p.ksplit > 0 && B2) ? p.ksplit : K;
-  u32x4* __restrict__ Bp = p.out[blockIdx.y];
-  if (!B) return;
-  const int idx = blockIdx.x * blockDim.x + threadIdx.x;
-  if (idx >= nslab * ntile * 64) return;
-  const int lane = idx & 63, tile = (idx >> 6) % ntile, slab = (idx >> 6) / ntile;
-  const int n = tile * 32 + (lane & 31), k0 = slab * 16 + (lane >> 5) * 8;
-  float v[8];
-#pragma unroll
-  for (int j = 0; j < 8; ++j) {
-    const int k = k0 + j;
-    v[j] = (n < N && k < K) ? (k < ksplit ? B[n * sn + k * sk] : B2[n * sn + (k - ksplit) * sk]) : 0.f;
-  }
-  u32x4 h, m, l;
-#pragma unroll
-  for (int j = 0; j < 4; ++j) {
-    unsigned a, b, c;
-    split_pair(v[2 * j], v[2 * j + 1], a, b, c);
-    h[j] = a; m[j] = b; l[j] = c;
-  }
-  u32x4* o = Bp + ((int64_t)(slab * ntile + tile) * 3) * 64 + lane;
-  o[0] = h; o[64] = m; o[128] = l;
-}
-
-inline void launch_bsplit3(const float* const* B, int64_t sn, int64_t sk, int N, int K, int nt, void* const* out, hipStream_t st,
-                           const float* const* B2 = nullptr, int ksplit = 0) {
-  const int ntile = x3_tiles(N, nt), nslab = x3_slabs(K);
-  const int total = nslab * ntile * 64;
-  BSplit3 p{};
-  for (int i = 0; i < 3; ++i) { p.B[i] = B[i]; p.out[i] = (u32x4*)out[i]; p.B2[i] = B2 ? B2[i] : nullptr; }
-  p.ksplit = B2 ? ksplit : 0;
-  hipLaunchKernelGGL(bsplit3_k, dim3((total + 255) / 256, 3), dim3(256), 0, st, p, sn, sk, N, K, ntile, nslab);
-}
-
-inline void launch_bsplit(const float* B, int64_t sn, int64_t sk, int N, int K, int nt, void* Bp, hipStream_t st) {
-  const int ntile = x3_tiles(N, nt), nslab = x3_slabs(K);
-  const int total = nslab * ntile * 64;
-  BSplit3 p{};
-  p.B[0] = B; p.out[0] = (u32x4*)Bp;
-  hipLaunchKernelGGL(bsplit3_k, dim3((total + 255) / 256, 1), dim3(256), 0, st, p, sn, sk, N, K, ntile, nslab);
-}
-
-// s_waitcnt vmcnt(n) with a run-time (wave-uniform) n <= 63
-__device__ __forceinline__ void wait_vmcnt(int n) {
-#define MRG_VM(N) case N: asm volatile("s_waitcnt vmcnt(" #N ")" ::: "memory"); break;
-#define MRG_VM8(B) MRG_VM(B + 0) MRG_VM(B + 1) MRG_VM(B + 2) MRG_VM(B + 3) MRG_VM(B + 4) MRG_VM(B + 5) MRG_VM(B + 6) MRG_VM(B + 7)
-  switch (n) {
-    MRG_VM(0) MRG_VM(1) MRG_VM(2) MRG_VM(3) MRG_VM(4) MRG_VM(5) MRG_VM(6) MRG_VM(7)
-    MRG_VM(8) MRG_VM(9) MRG_VM(10) MRG_VM(11) MRG_VM(12) MRG_VM(13) MRG_VM(14) MRG_VM(15)
-    MRG_VM(16) MRG_VM(17) MRG_VM(18) MRG_VM(19) MRG_VM(20) MRG_VM(21) MRG_VM(22) MRG_VM(23)
-    MRG_VM(24) MRG_VM(25) MRG_VM(26) MRG_VM(27) MRG_VM(28) MRG_VM(29) MRG_VM(30) MRG_VM(31)
-    MRG_VM(32) MRG_VM(33) MRG_VM(34) MRG_VM(35) MRG_VM(36) MRG_VM(37) MRG_VM(38) MRG_VM(39)
-    MRG_VM(40) MRG_VM(41) MRG_VM(42) MRG_VM(43) MRG_VM(44) MRG_VM(45) MRG_VM(46) MRG_VM(47)
-    MRG_VM(48) MRG_VM(49) MRG_VM(50) MRG_VM(51) MRG_VM(52) MRG_VM(53) MRG_VM(54) MRG_VM(55)
-    MRG_VM(56) MRG_VM(57) MRG_VM(58) MRG_VM(59) MRG_VM(60) MRG_VM(61) MRG_VM(62)
-    default: asm volatile("s_waitcnt vmcnt(63)" ::: "memory"); break;
-  }
-#undef MRG_VM8
-#undef MRG_VM
-}
-
-// mrg_gemm_set_epilogue: 1 = row-order 16-byte stores through LDS where the operands allow, 0 (default) = accumulator-order stores.
-// Round 3 measured the store tail NOT to be bound by the number of store instructions: with 4.5x fewer (25 instead of 112 per
-// strip) the plain epilogue is 9 % slower alone (0.249 vs 0.228 ms at rows 272 115, K = N = 200; the LDS round trip is pure
-// overhead), the accumulate epilogue 5-8 % faster (its input is read in row order too), the gate epilogue equal; in the supernet
-// step the row GEMM entry points lose 0.9 ms / step in total (profiles/r3_rowgemm_epilogue.txt).  Kept as a tested option.
-inline int& gemm_epi_lds() { static int m = 0; return m; }
-// Round 4: 2 = TRANSPOSED accumulators in the LDS-weight kernel (gemm_x3s.hpp, gemm_epilogue_tr): the MFMA operands change
-// places, a lane owns one row's 4-column chunks, and every epilogue load / store is 16 bytes per lane with no LDS round trip (28
-// store instructions per 32-row strip instead of 112).  Bit-identical, and SLOWER (rows 558 771, K = N = 200: plain 0.426 vs
-// 0.393 ms, accumulate 0.598 vs 0.463, gate 0.717 vs 0.611): a store instruction that writes 32 rows x 32 bytes costs the memory
-// pipeline more than one that writes 2 rows x 128 bytes, and the epilogue is not bound by its instruction count -- the same
-// 112 stores alone, at the kernel's grid, move 4.0 TB/s (profiles/r4_rowgemm_phases.txt).  Kept as a tested comparison point.
-inline int& gemm_epi_mode() { static int m = 0; return m; }
 
 constexpr int X3_THREADS = 256;     // 4 waves, one per SIMD
 constexpr int X3_SLOTS = 4;         // per-wave LDS ring of A slabs
@@ -162,26 +41,8 @@ __global__ __launch_bounds__(X3_THREADS, 1) void rowgemm_x3_k(GemmArgs a, const 
   constexpr int NPAIR = MT * 4;               // float pairs to split per slab and lane
   constexpr int PP = NT > 1 ? (NPAIR + NT - 2) / (NT - 1) : NPAIR;   // pairs split in the shadow of one column tile
   extern __shared__ __align__(16) float smem[];
-  typedef __attribute__((address_space(3))) void* lds_ptr_t;
-  typedef const __attribute__((address_space(1))) void* gbl_ptr_t;
-  typedef float v4f __attribute__((ext_vector_type(4)));
   const int tid = threadIdx.x, wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63, li = lane & 31, lh = lane >> 5;
-  int64_t row0 = (int64_t)blockIdx.x * GBM;
-  // grouped launch: this workgroup's row range and its weight.  The range index and the weight pointer are formed by
-  // unconditional scalar arithmetic (bp_stride = 0 in a plain launch): the B loads address through an SGPR pair.
-  int sg = 0;
-  if (a.grp.n > 0) sg = ((int)blockIdx.x >= a.grp.tile0[1] ? 1 : 0) + ((int)blockIdx.x >= a.grp.tile0[2] ? 1 : 0);
-  sg = __builtin_amdgcn_readfirstlane(sg);
-  const char* __restrict__ Bq = Bp + (int64_t)sg * a.grp.bp_stride;
-  if (a.grp.n > 0) {                                     // constant indices only: a dynamic one would move the argument block to scratch
-#define MRG_PICK(F) (sg == 0 ? a.grp.F[0] : (sg == 1 ? a.grp.F[1] : a.grp.F[2]))
-    row0 = MRG_PICK(lo) + (int64_t)((int)blockIdx.x - MRG_PICK(tile0)) * GBM;
-    a.rows = MRG_PICK(hi);
-    a.bias = MRG_PICK(bias);
-    a.scale = MRG_PICK(scale);
-    if (!MRG_PICK(use_rowscale)) a.rowscale = nullptr;
-#undef MRG_PICK
-  }
+  MRG_GROUP_SELECT(GBM)                                // row0, Bq; a.rows / bias / scale / rowscale of a grouped launch's range
   const int64_t roww = row0 + wave * WROWS;
   const int col0 = blockIdx.y * (NT * 32);
   const int K = a.K1 + a.K2;
@@ -213,14 +74,7 @@ __global__ __launch_bounds__(X3_THREADS, 1) void rowgemm_x3_k(GemmArgs a, const 
 #pragma unroll
     for (int i = 0; i < NA; ++i) {
       const int k = k0 + acol[i];
-      const float* p;
-      if (DUAL) {
-        const bool first = k < a.K1;
-        const int kk = first ? k : k - a.K1, ld = first ? a.K1 : a.K2;
-        p = (first ? arow1[i] : arow2[i]) + (kk + 4 <= ld ? kk : ld - 4);
-      } else {
-        p = arow1[i] + (k + 4 <= K ? k : K - 4);
-      }
+      const float* p = gemm_a_ptr<DUAL>(arow1[i], arow2[i], a.K1, a.K2, K, k);
       __builtin_amdgcn_global_load_lds((gbl_ptr_t)p, (lds_ptr_t)(dst + 64 * i * 4), 16, 0, 0);
     }
   };
@@ -259,12 +113,7 @@ __global__ __launch_bounds__(X3_THREADS, 1) void rowgemm_x3_k(GemmArgs a, const 
   u32x4 ch[MT], cm[MT], cl[MT];                   // split planes of the CURRENT slab
   u32x4 nh[MT], nm[MT], nl[MT];                   // ... being produced for the next one
   auto split_one = [&](int j, u32x4 (&H)[MT], u32x4 (&M)[MT], u32x4 (&L)[MT]) {   // pair j of 4*MT
-    const int m = j >> 2, q = j & 3;
-    const v4f& v = x[m][q >> 1];
-    unsigned h, mm, l;
-    if (q & 1) split_pair(v.z, v.w, h, mm, l);
-    else split_pair(v.x, v.y, h, mm, l);
-    H[m][q] = h; M[m][q] = mm; L[m][q] = l;
+    split_pair_of(x[j >> 2], j & 3, H[j >> 2], M[j >> 2], L[j >> 2]);
   };
 
   // ---- prologue: A slabs 0..2 and B slab 0 in flight; slab 0 split
@@ -312,18 +161,8 @@ __global__ __launch_bounds__(X3_THREADS, 1) void rowgemm_x3_k(GemmArgs a, const 
       }
       const bf16x8 Bh = __builtin_bit_cast(bf16x8, bq[n][0]), Bm = __builtin_bit_cast(bf16x8, bq[n][1]),
                    Bl = __builtin_bit_cast(bf16x8, bq[n][2]);
-      // Row tiles interleaved (a dependent MFMA issued back to back costs ~6 extra cycles, measured with
-      // tools/mfma_bf16_peak.hip); small terms first, the leading term last.
-#define MRG_X3_TERM(AP, BP)                                                                             \
-  _Pragma("unroll") for (int m = 0; m < MT; ++m)                                                          \
-      acc[m][n] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, AP[m]), BP, acc[m][n], 0, 0, 0)
-      MRG_X3_TERM(cm, Bm);
-      MRG_X3_TERM(cl, Bh);
-      MRG_X3_TERM(ch, Bl);
-      MRG_X3_TERM(cm, Bh);
-      MRG_X3_TERM(ch, Bm);
-      MRG_X3_TERM(ch, Bh);
-#undef MRG_X3_TERM
+      // row tiles interleaved; every accumulator takes its six terms in the order of x3_parts.hpp
+      x3_chain_rows(acc, n, ch, cm, cl, Bh, Bm, Bl);
       if (has_next && n == NT - 1) {
 #pragma unroll
         for (int m = 0; m < MT; ++m) { ch[m] = nh[m]; cm[m] = nm[m]; cl[m] = nl[m]; }
@@ -368,14 +207,10 @@ inline int launch_rowgemm_x3(GemmArgs a, const void* Bp, hipStream_t st, int nt_
   if (a.grp.n > 0 && gemm_group_tiles(a.grp, gbm) == 0) return MRG_OK;     // grouped launch: nothing to do
   dim3 grid((unsigned)(a.grp.n > 0 ? a.grp.tile0[3] : (a.rows + gbm - 1) / gbm), (unsigned)(ntile / nt));
   const size_t ring_floats = (size_t)X3_SLOTS * 32 * mt * 16;
-  a.epi_lds = (gemm_epi_lds() && gemm_epilogue_lds_ok<EPI>(a)) ? 1 : 0;
+  a.epi_lds = (gemm_switches().epilogue == 1 && gemm_epilogue_lds_ok<EPI>(a)) ? 1 : 0;
   a.wave_lds_floats = (int)((a.epi_lds && gemm_stage_floats(nt) > ring_floats) ? gemm_stage_floats(nt) : ring_floats);
   const size_t lds = (size_t)(X3_THREADS / 64) * a.wave_lds_floats * sizeof(float);
-#define MRG_GOX3(NTV, MTV, DV, LV)                                                                                    \
-  do {                                                                                                                \
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&rowgemm_x3_k<NTV, MTV, EPI, DV, LV>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
-    hipLaunchKernelGGL((rowgemm_x3_k<NTV, MTV, EPI, DV, LV>), grid, dim3(X3_THREADS), lds, st, a, (const char*)Bp, ntile); \
-  } while (0)
+#define MRG_GOX3(NTV, MTV, DV, LV) return launch_kernel(rowgemm_x3_k<NTV, MTV, EPI, DV, LV>, grid, dim3(X3_THREADS), lds, st, a, Bp, ntile)
 #define MRG_GOX2(NTV, MTV, DV)                                                                                        \
   do {                                                                                                                \
     if constexpr (EPI == EPI_SEGMAX || EPI == EPI_SEGSUM) MRG_GOX3(NTV, MTV, DV, false);                              \
@@ -395,8 +230,6 @@ inline int launch_rowgemm_x3(GemmArgs a, const void* Bp, hipStream_t st, int nt_
 #undef MRG_GOX
 #undef MRG_GOX2
 #undef MRG_GOX3
-  hipError_t e = hipGetLastError();
-  return e == hipSuccess ? MRG_OK : (int)e;
 }
 
 }  // namespace mrg

@@ -30,62 +30,11 @@
 
 namespace mrg {
 
-typedef float f32x4v __attribute__((ext_vector_type(4)));
-
-// lab / rollback switch: 0 = every launch stays on rowgemm_x3s_k (mrg_gemm_set_q)
-inline int& gemm_q() { static int m = 1; return m; }
-
-constexpr int X3Q_HT = 7;                       // 16-column tiles per half-slab
-constexpr int X3Q_NT = 2 * X3Q_HT;              // 14 tiles = 224 columns
+// (X3Q_HT = 7 tiles of 16 columns per half-slab, X3Q_NT = 14 per slab: x3_parts.hpp, next to the weight split's layout)
 constexpr int X3Q_CHUNK = X3Q_HT * 3 * 1024;    // bytes of one half-slab of the pre-split weight
 constexpr int X3Q_ROWS = 64;                    // rows per workgroup
 
-inline int x3q_slabs(int K) { return (K + 31) / 32; }
 inline size_t x3q_bsplit_bytes(int K) { return (size_t)x3q_slabs(K) * 2 * X3Q_CHUNK; }
-
-struct BSplitQ { const float* B[3]; u32x4* out[3]; const float* B2[3]; int ksplit; };
-static __global__ void bsplitq_k(BSplitQ p, int64_t sn, int64_t sk, int N, int K, int nslab) {
-  const float* __restrict__ B = p.B[blockIdx.y];
-  const float* __restrict__ B2 = p.B2[blockIdx.y];
-  const int ksplit = (p.ksplit > 0 && B2) ? p.ksplit : K;
-  u32x4* __restrict__ Bp = p.out[blockIdx.y];
-  if (!B) return;
-  const int idx = blockIdx.x * blockDim.x + threadIdx.x;
-  if (idx >= nslab * X3Q_NT * 64) return;
-  const int lane = idx & 63, tile = (idx >> 6) % X3Q_NT, slab = (idx >> 6) / X3Q_NT;
-  const int n = tile * 16 + (lane & 15), k0 = slab * 32 + (lane >> 4) * 8;
-  float v[8];
-#pragma unroll
-  for (int j = 0; j < 8; ++j) {
-    const int k = k0 + j;
-    v[j] = (n < N && k < K) ? (k < ksplit ? B[n * sn + k * sk] : B2[n * sn + (k - ksplit) * sk]) : 0.f;
-  }
-  u32x4 h, m, l;
-#pragma unroll
-  for (int j = 0; j < 4; ++j) {
-    unsigned a, b, c;
-    split_pair(v[2 * j], v[2 * j + 1], a, b, c);
-    h[j] = a; m[j] = b; l[j] = c;
-  }
-  // [slab][half][tile in half][plane][lane]
-  const int half = tile / X3Q_HT, t = tile - half * X3Q_HT;
-  u32x4* o = Bp + ((int64_t)((slab * 2 + half) * X3Q_HT + t) * 3) * 64 + lane;
-  o[0] = h; o[64] = m; o[128] = l;
-}
-
-inline void launch_bsplitq3(const float* const* B, int64_t sn, int64_t sk, int N, int K, void* const* out, int count, hipStream_t st,
-                            const float* const* B2 = nullptr, int ksplit = 0) {
-  const int nslab = x3q_slabs(K);
-  const int total = nslab * X3Q_NT * 64;
-  BSplitQ p{};
-  for (int i = 0; i < 3; ++i) {
-    p.B[i] = i < count ? B[i] : nullptr;
-    p.out[i] = i < count ? (u32x4*)out[i] : nullptr;
-    p.B2[i] = (B2 && i < count) ? B2[i] : nullptr;
-  }
-  p.ksplit = B2 ? ksplit : 0;
-  hipLaunchKernelGGL(bsplitq_k, dim3((total + 255) / 256, count), dim3(256), 0, st, p, sn, sk, N, K, nslab);
-}
 
 // ---- epilogue on PAIRS of 16 x 16 tiles ------------------------------------------------------------------------------------------
 // C/D map of a 16 x 16 tile: col = lane & 15, row = 4 * (lane >> 4) + reg.  v_permlane16_swap_b32 a, b exchanges a's odd 16-lane
@@ -191,25 +140,9 @@ __global__ __launch_bounds__(256, X3Q_WPS) void rowgemm_x3q_k(GemmArgs a, const 
   constexpr int NCH = X3Q_HT * 3;               // 1 KB pieces (64 lanes x 16 B) of a half-slab
   constexpr int NBW = (NCH + 3) / 4;            // DMA instructions per wave and half-slab
   extern __shared__ __align__(16) char smem_q[];          // [2][X3Q_CHUNK]
-  typedef __attribute__((address_space(3))) void* lds_ptr_t;
-  typedef const __attribute__((address_space(1))) void* gbl_ptr_t;
-  typedef float v4f __attribute__((ext_vector_type(4)));
   const int tid = threadIdx.x, wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63;
   const int lr = lane & 15, lg = lane >> 4;              // MFMA operand coordinates: row (column for B) and k-group
-  int64_t row0 = (int64_t)blockIdx.x * X3Q_ROWS;
-  int sg = 0;
-  if (a.grp.n > 0) sg = ((int)blockIdx.x >= a.grp.tile0[1] ? 1 : 0) + ((int)blockIdx.x >= a.grp.tile0[2] ? 1 : 0);
-  sg = __builtin_amdgcn_readfirstlane(sg);
-  const char* __restrict__ Bq = Bp + (int64_t)sg * a.grp.bp_stride;
-  if (a.grp.n > 0) {                                     // grouped launch, as in rowgemm_x3_k (constant indices only)
-#define MRG_PICK(F) (sg == 0 ? a.grp.F[0] : (sg == 1 ? a.grp.F[1] : a.grp.F[2]))
-    row0 = MRG_PICK(lo) + (int64_t)((int)blockIdx.x - MRG_PICK(tile0)) * X3Q_ROWS;
-    a.rows = MRG_PICK(hi);
-    a.bias = MRG_PICK(bias);
-    a.scale = MRG_PICK(scale);
-    if (!MRG_PICK(use_rowscale)) a.rowscale = nullptr;
-#undef MRG_PICK
-  }
+  MRG_GROUP_SELECT(X3Q_ROWS)                                // row0, Bq; a.rows / bias / scale / rowscale of a grouped launch's range
   const int64_t roww = row0 + wave * 16;
   const int K = a.K1 + a.K2;
   const int nslab = (K + 31) >> 5;
@@ -221,56 +154,16 @@ __global__ __launch_bounds__(256, X3Q_WPS) void rowgemm_x3q_k(GemmArgs a, const 
     for (int r = 0; r < 4; ++r) acc[n][r] = 0.f;
 
   // ---- A: this lane's fragment of slab s = row lr, k = 32 s + 8 lg + {0..3, 4..7}: two 16-byte loads
-  int64_t rc = roww + lr < a.rows ? roww + lr : a.rows - 1;
-  if (rc < 0) rc = 0;
-  if (a.row_index) rc = a.row_index[rc];                 // gathered rows
-  const float* ar1 = a.A1 + rc * a.K1;
-  const float* ar2 = a.A2 + rc * a.K2;
-  auto a_ptr = [&](int k) -> const float* {
-    if (DUAL) {
-      const bool first = k < a.K1;
-      const int kk = first ? k : k - a.K1, ld = first ? a.K1 : a.K2;
-      return (first ? ar1 : ar2) + (kk + 4 <= ld ? kk : ld - 4);
-    }
-    return ar1 + (k + 4 <= K ? k : K - 4);               // beyond K: any finite values, the weight's rows there are zero
-  };
-  // asynchronous register fills, first read behind the matching counted s_waitcnt (see gemm_x3.hpp)
+  const float* ar1; const float* ar2;
+  x3_a_row(a, roww + lr, ar1, ar2);
   v4f xr[2][2];                                          // raw fragments: a ring of two slabs
-  auto load_a = [&](int slab, v4f (&x)[2]) {
-    const int sl = slab < nslab ? slab : nslab - 1;      // beyond the end: re-read the last slab (an asynchronous fill is never conditional)
-    const int k = sl * 32 + lg * 8;
-    const float* p0 = a_ptr(k);
-    const float* p1 = a_ptr(k + 4);
-    asm volatile("global_load_dwordx4 %0, %1, off" : "=v"(x[0]) : "v"(p0));
-    asm volatile("global_load_dwordx4 %0, %1, off" : "=v"(x[1]) : "v"(p1));
-  };
+  auto load_a = [&](int slab, v4f (&x)[2]) { x3_load_a<32, DUAL>(x, slab, nslab, lg, ar1, ar2, a.K1, a.K2, K); };
   // ---- B: half-slab c = 2 s + half lives in buffer `half`; NBW pieces per wave (the last wave repeats the last piece)
-  auto fetch_b = [&](int c) {
-    const char* src = Bq + (int64_t)c * X3Q_CHUNK;
-    const int buf = c & 1;
-#pragma unroll
-    for (int i = 0; i < NBW; ++i) {
-      int pc = wave * NBW + i;
-      pc = pc < NCH ? pc : NCH - 1;
-      __builtin_amdgcn_global_load_lds((gbl_ptr_t)(src + pc * 1024 + lane * 16), (lds_ptr_t)(smem_q + buf * X3Q_CHUNK + pc * 1024), 16, 0, 0);
-    }
-  };
+  auto fetch_b = [&](int c) { x3_fetch_b<NCH>(Bq + (int64_t)c * X3Q_CHUNK, smem_q + (c & 1) * X3Q_CHUNK, wave, lane); };
   const unsigned lds0 = (unsigned)(size_t)(lds_ptr_t)smem_q + (unsigned)lane * 16u;
   u32x4 bq[2][3];                                        // [ping-pong][plane]: the fragments of one column tile
-  auto read_b = [&](int t, int buf, u32x4 (&q)[3]) {
-    const unsigned ad = lds0 + (unsigned)(buf * X3Q_CHUNK + t * 3072);
-    asm volatile("ds_read_b128 %0, %1" : "=v"(q[0]) : "v"(ad));
-    asm volatile("ds_read_b128 %0, %1 offset:1024" : "=v"(q[1]) : "v"(ad));
-    asm volatile("ds_read_b128 %0, %1 offset:2048" : "=v"(q[2]) : "v"(ad));
-  };
+  auto read_b = [&](int t, int buf, u32x4 (&q)[3]) { x3_read_b(lds0 + (unsigned)(buf * X3Q_CHUNK + t * 3072), q); };
   u32x4 ch, cm, cl, nh, nm, nl;
-  auto split_pair_of = [&](const v4f (&x)[2], int q, u32x4& H, u32x4& M, u32x4& L) {     // q = 0..3: floats 2q, 2q + 1 of the 8
-    const v4f& v = x[q >> 1];
-    unsigned h, m, l;
-    if (q & 1) split_pair(v.z, v.w, h, m, l); else split_pair(v.x, v.y, h, m, l);
-    H[q] = h; M[q] = m; L[q] = l;
-  };
-
   // ---- prologue.  Issue order of a wave:  A(0) B(0) B(1) A(1) | s = 0, half 1: B(2) A(2) | s = 1, half 0: B(3) | half 1: B(4) A(3) | ...
   load_a(0, xr[0]);
   fetch_b(0);
@@ -301,15 +194,7 @@ __global__ __launch_bounds__(256, X3Q_WPS) void rowgemm_x3q_k(GemmArgs a, const 
       if (SPLIT && t < 4) split_pair_of(xn, t, nh, nm, nl);
       const bf16x8 Ah = __builtin_bit_cast(bf16x8, ch), Am = __builtin_bit_cast(bf16x8, cm), Al = __builtin_bit_cast(bf16x8, cl);
       const bf16x8 Bh = __builtin_bit_cast(bf16x8, bq[t & 1][0]), Bm = __builtin_bit_cast(bf16x8, bq[t & 1][1]), Bl = __builtin_bit_cast(bf16x8, bq[t & 1][2]);
-      f32x4v c = acc[HF * X3Q_HT + t];
-      // small terms first, the leading term last (the order of the other split-core kernels)
-      c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(Am, Bm, c, 0, 0, 0);
-      c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(Al, Bh, c, 0, 0, 0);
-      c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(Ah, Bl, c, 0, 0, 0);
-      c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(Am, Bh, c, 0, 0, 0);
-      c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(Ah, Bm, c, 0, 0, 0);
-      c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(Ah, Bh, c, 0, 0, 0);
-      acc[HF * X3Q_HT + t] = c;
+      x3_chain(acc[HF * X3Q_HT + t], Ah, Am, Al, Bh, Bm, Bl);
       if (SPLIT) {
 #pragma unroll
         for (int i = 0; i < 6; ++i) {
@@ -370,15 +255,8 @@ inline int launch_rowgemm_x3q(GemmArgs a, const void* Bp, hipStream_t st) {
   if constexpr (EPI == EPI_SEGMAX || EPI == EPI_SEGSUM) {
     return MRG_E_SHAPE;                                   // the fused aggregators' epilogues stay on rowgemm_x3s_k (x3q_shape says so)
   } else {
-#define MRG_GOQ(DV)                                                                                                   \
-  do {                                                                                                                \
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&rowgemm_x3q_k<EPI, DV>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
-    hipLaunchKernelGGL((rowgemm_x3q_k<EPI, DV>), grid, dim3(256), lds, st, a, (const char*)Bp);                       \
-  } while (0)
-    if (a.K2 > 0) MRG_GOQ(true); else MRG_GOQ(false);
-#undef MRG_GOQ
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? MRG_OK : (int)e;
+    if (a.K2 > 0) return launch_kernel(rowgemm_x3q_k<EPI, true>, grid, dim3(256), lds, st, a, Bp);
+    return launch_kernel(rowgemm_x3q_k<EPI, false>, grid, dim3(256), lds, st, a, Bp);
   }
 }
 

@@ -39,24 +39,8 @@ __global__ __launch_bounds__(256, 2) void rowgemm_x3s_k(GemmArgs a, const char* 
   constexpr int BSLAB = NCH * 1024;
   constexpr int NBW = (NCH + 3) / 4;            // DMA instructions per wave and slab
   extern __shared__ __align__(16) char smem_b[];     // [3][BSLAB]: 63 KB for seven column tiles, below the DMA's 64 KiB
-  typedef __attribute__((address_space(3))) void* lds_ptr_t;
-  typedef const __attribute__((address_space(1))) void* gbl_ptr_t;
-  typedef float v4f __attribute__((ext_vector_type(4)));
   const int tid = threadIdx.x, wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63, li = lane & 31, lh = lane >> 5;
-  int64_t row0 = (int64_t)blockIdx.x * GBM;
-  int sg = 0;
-  if (a.grp.n > 0) sg = ((int)blockIdx.x >= a.grp.tile0[1] ? 1 : 0) + ((int)blockIdx.x >= a.grp.tile0[2] ? 1 : 0);
-  sg = __builtin_amdgcn_readfirstlane(sg);
-  const char* __restrict__ Bq = Bp + (int64_t)sg * a.grp.bp_stride;
-  if (a.grp.n > 0) {                                     // grouped launch, as in rowgemm_x3_k (constant indices only)
-#define MRG_PICK(F) (sg == 0 ? a.grp.F[0] : (sg == 1 ? a.grp.F[1] : a.grp.F[2]))
-    row0 = MRG_PICK(lo) + (int64_t)((int)blockIdx.x - MRG_PICK(tile0)) * GBM;
-    a.rows = MRG_PICK(hi);
-    a.bias = MRG_PICK(bias);
-    a.scale = MRG_PICK(scale);
-    if (!MRG_PICK(use_rowscale)) a.rowscale = nullptr;
-#undef MRG_PICK
-  }
+  MRG_GROUP_SELECT(GBM)                                // row0, Bq; a.rows / bias / scale / rowscale of a grouped launch's range
   const int64_t roww = row0 + wave * 32;
   const int col0 = blockIdx.y * (NT * 32);
   const int K = a.K1 + a.K2;
@@ -69,55 +53,17 @@ __global__ __launch_bounds__(256, 2) void rowgemm_x3s_k(GemmArgs a, const char* 
     for (int r = 0; r < 16; ++r) acc[n][r] = 0.f;
 
   // ---- A: this lane's fragment of a slab = row li, k = slab * 16 + lh * 8 + {0..3, 4..7}: two 16-byte loads
-  int64_t rc = roww + li < a.rows ? roww + li : a.rows - 1;
-  if (rc < 0) rc = 0;
-  if (a.row_index) rc = a.row_index[rc];                 // gathered rows (EPI_SEGMAX / EPI_SEGSUM: edges in destination order)
-  const float* ar1 = a.A1 + rc * a.K1;
-  const float* ar2 = a.A2 + rc * a.K2;
-  auto a_ptr = [&](int k) -> const float* {
-    if (DUAL) {
-      const bool first = k < a.K1;
-      const int kk = first ? k : k - a.K1, ld = first ? a.K1 : a.K2;
-      return (first ? ar1 : ar2) + (kk + 4 <= ld ? kk : ld - 4);
-    }
-    return ar1 + (k + 4 <= K ? k : K - 4);               // beyond K: any finite values, the weight's rows there are zero
-  };
-  // asynchronous register fills, first read behind the matching counted s_waitcnt (see gemm_x3.hpp)
+  const float* ar1; const float* ar2;
+  x3_a_row(a, roww + li, ar1, ar2);
   v4f xr[3][2];                                          // raw fragments: a ring of three slabs
-  auto load_a = [&](int slab, v4f (&x)[2]) {
-    const int sl = slab < nslab ? slab : nslab - 1;      // beyond the end: re-read the last slab (an asynchronous fill is never conditional)
-    const int k = sl * 16 + lh * 8;
-    const float* p0 = a_ptr(k);
-    const float* p1 = a_ptr(k + 4);
-    asm volatile("global_load_dwordx4 %0, %1, off" : "=v"(x[0]) : "v"(p0));
-    asm volatile("global_load_dwordx4 %0, %1, off" : "=v"(x[1]) : "v"(p1));
-  };
+  auto load_a = [&](int slab, v4f (&x)[2]) { x3_load_a<16, DUAL>(x, slab, nslab, lh, ar1, ar2, a.K1, a.K2, K); };
   // ---- B: the slab's NCH chunks, NBW per wave (the last wave repeats the last chunk: same bytes to the same place)
   const char* bcol = Bq + (int64_t)blockIdx.y * NT * 3072;
-  auto fetch_b = [&](int slab, int buf) {
-    const char* src = bcol + (int64_t)slab * ntile * 3072;
-#pragma unroll
-    for (int i = 0; i < NBW; ++i) {
-      int c = wave * NBW + i;
-      c = c < NCH ? c : NCH - 1;
-      __builtin_amdgcn_global_load_lds((gbl_ptr_t)(src + c * 1024 + lane * 16), (lds_ptr_t)(smem_b + buf * BSLAB + c * 1024), 16, 0, 0);
-    }
-  };
+  auto fetch_b = [&](int slab, int buf) { x3_fetch_b<NCH>(bcol + (int64_t)slab * ntile * 3072, smem_b + buf * BSLAB, wave, lane); };
   const unsigned lds0 = (unsigned)(size_t)(lds_ptr_t)smem_b + (unsigned)lane * 16u;
   u32x4 bq2[2][2][3];                                    // [double buffer][tile of the pair][plane]
-  auto read_b = [&](int n, int buf, u32x4 (&q)[3]) {
-    const unsigned ad = lds0 + (unsigned)(buf * BSLAB + n * 3072);
-    asm volatile("ds_read_b128 %0, %1" : "=v"(q[0]) : "v"(ad));
-    asm volatile("ds_read_b128 %0, %1 offset:1024" : "=v"(q[1]) : "v"(ad));
-    asm volatile("ds_read_b128 %0, %1 offset:2048" : "=v"(q[2]) : "v"(ad));
-  };
+  auto read_b = [&](int n, int buf, u32x4 (&q)[3]) { x3_read_b(lds0 + (unsigned)(buf * BSLAB + n * 3072), q); };
   u32x4 ch, cm, cl, nh, nm, nl;
-  auto split_pair_of = [&](const v4f (&x)[2], int q, u32x4& H, u32x4& M, u32x4& L) {     // q = 0..3: floats 2q, 2q + 1 of the 8
-    const v4f& v = x[q >> 1];
-    unsigned h, m, l;
-    if (q & 1) split_pair(v.z, v.w, h, m, l); else split_pair(v.x, v.y, h, m, l);
-    H[q] = h; M[q] = m; L[q] = l;
-  };
   auto nb_issued = [&](int j) { return (j >= -2 && j + 2 < nslab) ? NBW : 0; };   // B DMAs issued at the top of slab j (j < 0: prologue)
   constexpr int NP = (NT + 1) / 2;                          // column-tile pairs per slab
 
@@ -139,7 +85,6 @@ __global__ __launch_bounds__(256, 2) void rowgemm_x3s_k(GemmArgs a, const char* 
   //        the raw registers slab s-1 split from;
   //   the splits need A(s+1): younger = B(s+1) A(s+2) B(s+2) A(s+3);
   //   end: B(s+1) must be in LDS before the barrier: younger = A(s+2) B(s+2) A(s+3).
-#define MRG_MM(AF, BF, C) (TR ? __builtin_amdgcn_mfma_f32_32x32x16_bf16(BF, AF, C, 0, 0, 0) : __builtin_amdgcn_mfma_f32_32x32x16_bf16(AF, BF, C, 0, 0, 0))
   auto slab = [&](auto r_c, int s) {
     constexpr int R = decltype(r_c)::value;
     const bool has_next = s + 1 < nslab;
@@ -178,26 +123,9 @@ __global__ __launch_bounds__(256, 2) void rowgemm_x3s_k(GemmArgs a, const char* 
       if (n1 < NT) {
         const bf16x8 Bh1 = __builtin_bit_cast(bf16x8, bq2[pp & 1][1][0]), Bm1 = __builtin_bit_cast(bf16x8, bq2[pp & 1][1][1]),
                      Bl1 = __builtin_bit_cast(bf16x8, bq2[pp & 1][1][2]);
-        // small terms first, the leading term last (same order per accumulator as rowgemm_x3_k)
-        acc[n0] = MRG_MM(Am, Bm0, acc[n0]);
-        acc[n1] = MRG_MM(Am, Bm1, acc[n1]);
-        acc[n0] = MRG_MM(Al, Bh0, acc[n0]);
-        acc[n1] = MRG_MM(Al, Bh1, acc[n1]);
-        acc[n0] = MRG_MM(Ah, Bl0, acc[n0]);
-        acc[n1] = MRG_MM(Ah, Bl1, acc[n1]);
-        acc[n0] = MRG_MM(Am, Bh0, acc[n0]);
-        acc[n1] = MRG_MM(Am, Bh1, acc[n1]);
-        acc[n0] = MRG_MM(Ah, Bm0, acc[n0]);
-        acc[n1] = MRG_MM(Ah, Bm1, acc[n1]);
-        acc[n0] = MRG_MM(Ah, Bh0, acc[n0]);
-        acc[n1] = MRG_MM(Ah, Bh1, acc[n1]);
+        x3_chain2<TR>(acc[n0], acc[n1], Ah, Am, Al, Bh0, Bm0, Bl0, Ah, Am, Al, Bh1, Bm1, Bl1);
       } else {
-        acc[n0] = MRG_MM(Am, Bm0, acc[n0]);
-        acc[n0] = MRG_MM(Al, Bh0, acc[n0]);
-        acc[n0] = MRG_MM(Ah, Bl0, acc[n0]);
-        acc[n0] = MRG_MM(Am, Bh0, acc[n0]);
-        acc[n0] = MRG_MM(Ah, Bm0, acc[n0]);
-        acc[n0] = MRG_MM(Ah, Bh0, acc[n0]);
+        x3_chain<TR>(acc[n0], Ah, Am, Al, Bh0, Bm0, Bl0);
       }
 #pragma unroll
       for (int i = 0; i < 12; ++i) {
@@ -216,7 +144,6 @@ __global__ __launch_bounds__(256, 2) void rowgemm_x3s_k(GemmArgs a, const char* 
       __builtin_amdgcn_s_barrier();                          // ... and everybody's; all reads of this slab's buffer are done
     }
   };
-#undef MRG_MM
   int s = 0;
   for (; s + 2 < nslab; s += 3) {
     slab(std::integral_constant<int, 0>{}, s);
@@ -248,12 +175,8 @@ inline int launch_rowgemm_x3s(GemmArgs a, const void* Bp, hipStream_t st) {
   dim3 grid((unsigned)(a.grp.n > 0 ? a.grp.tile0[3] : (a.rows + gbm - 1) / gbm), (unsigned)(ntile / nt));
   size_t lds = (size_t)3 * nt * 3 * 1024;
   bool tr = false;
-  if constexpr (EPI != EPI_SEGMAX && EPI != EPI_SEGSUM) tr = gemm_epi_mode() == 2 && gemm_epilogue_tr_ok<EPI>(a);
-#define MRG_GOS3(NTV, DV, TV)                                                                                         \
-  do {                                                                                                                \
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&rowgemm_x3s_k<NTV, EPI, DV, TV>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
-    hipLaunchKernelGGL((rowgemm_x3s_k<NTV, EPI, DV, TV>), grid, dim3(256), lds, st, a, (const char*)Bp, ntile);       \
-  } while (0)
+  if constexpr (EPI != EPI_SEGMAX && EPI != EPI_SEGSUM) tr = gemm_switches().epilogue == 2 && gemm_epilogue_tr_ok<EPI>(a);
+#define MRG_GOS3(NTV, DV, TV) return launch_kernel(rowgemm_x3s_k<NTV, EPI, DV, TV>, grid, dim3(256), lds, st, a, Bp, ntile)
 #define MRG_GOS2(NTV, DV)                                                                                             \
   do {                                                                                                                \
     if constexpr (EPI == EPI_SEGMAX || EPI == EPI_SEGSUM) MRG_GOS3(NTV, DV, false);                                   \
@@ -269,8 +192,6 @@ inline int launch_rowgemm_x3s(GemmArgs a, const void* Bp, hipStream_t st) {
 #undef MRG_GOS
 #undef MRG_GOS2
 #undef MRG_GOS3
-  hipError_t e = hipGetLastError();
-  return e == hipSuccess ? MRG_OK : (int)e;
 }
 
 }  // namespace mrg

@@ -27,9 +27,6 @@ __global__ __launch_bounds__(256, 2) void rowgemm_x3s8_k(GemmArgs a, const char*
   constexpr int NBW = (NCH + 3) / 4;            // DMA instructions per wave and slab (the last wave repeats the last chunk: same bytes, same place)
   constexpr int NP = (NT + 1) / 2;
   extern __shared__ __align__(16) char smem_b8[];    // [2][BSLAB] = 48 KB at eight tiles
-  typedef __attribute__((address_space(3))) void* lds_ptr_t;
-  typedef const __attribute__((address_space(1))) void* gbl_ptr_t;
-  typedef float v4f __attribute__((ext_vector_type(4)));
   const int tid = threadIdx.x, wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63, li = lane & 31, lh = lane >> 5;
   const int64_t row0 = (int64_t)blockIdx.x * GBM;
   const int64_t roww = row0 + wave * 32;
@@ -42,11 +39,10 @@ __global__ __launch_bounds__(256, 2) void rowgemm_x3s8_k(GemmArgs a, const char*
 #pragma unroll
     for (int r = 0; r < 16; ++r) acc[n][r] = 0.f;
 
-  int64_t rc = roww + li < a.rows ? roww + li : a.rows - 1;
-  if (rc < 0) rc = 0;
-  if (a.row_index) rc = a.row_index[rc];                 // gathered rows (fused a_max / a_mean: edges in destination order)
-  const float* ar1 = a.A1 + rc * a.K1;
+  const float* ar1; const float* ar2;                    // (single source: ar2 is not read)
+  x3_a_row(a, roww + li, ar1, ar2);
   v4f xr[2][2];                                          // raw fragments: a ring of two slabs
+  // x3_load_a<16, false> spelled out: the shared form computes the same two addresses with two VALU instructions in another place
   auto load_a = [&](int slab, v4f (&x)[2]) {
     const int sl = slab < nslab ? slab : nslab - 1;      // beyond the end: re-read the last slab (an asynchronous fill is never conditional)
     const int k = sl * 16 + lh * 8;
@@ -55,31 +51,11 @@ __global__ __launch_bounds__(256, 2) void rowgemm_x3s8_k(GemmArgs a, const char*
     asm volatile("global_load_dwordx4 %0, %1, off" : "=v"(x[0]) : "v"(p0));
     asm volatile("global_load_dwordx4 %0, %1, off" : "=v"(x[1]) : "v"(p1));
   };
-  auto fetch_b = [&](int slab, int buf) {
-    const char* src = Bp + (int64_t)slab * ntile * 3072;
-#pragma unroll
-    for (int i = 0; i < NBW; ++i) {
-      int c = wave * NBW + i;
-      c = c < NCH ? c : NCH - 1;
-      __builtin_amdgcn_global_load_lds((gbl_ptr_t)(src + c * 1024 + lane * 16), (lds_ptr_t)(smem_b8 + buf * BSLAB + c * 1024), 16, 0, 0);
-    }
-  };
+  auto fetch_b = [&](int slab, int buf) { x3_fetch_b<NCH>(Bp + (int64_t)slab * ntile * 3072, smem_b8 + buf * BSLAB, wave, lane); };
   const unsigned lds0 = (unsigned)(size_t)(lds_ptr_t)smem_b8 + (unsigned)lane * 16u;
   u32x4 bq2[2][2][3];                                    // [double buffer][tile of the pair][plane]
-  auto read_b = [&](int n, int buf, u32x4 (&q)[3]) {
-    const unsigned ad = lds0 + (unsigned)(buf * BSLAB + n * 3072);
-    asm volatile("ds_read_b128 %0, %1" : "=v"(q[0]) : "v"(ad));
-    asm volatile("ds_read_b128 %0, %1 offset:1024" : "=v"(q[1]) : "v"(ad));
-    asm volatile("ds_read_b128 %0, %1 offset:2048" : "=v"(q[2]) : "v"(ad));
-  };
+  auto read_b = [&](int n, int buf, u32x4 (&q)[3]) { x3_read_b(lds0 + (unsigned)(buf * BSLAB + n * 3072), q); };
   u32x4 ch, cm, cl, nh, nm, nl;
-  auto split_pair_of = [&](const v4f (&x)[2], int q, u32x4& H, u32x4& M, u32x4& L) {     // q = 0..3: floats 2q, 2q + 1 of the 8
-    const v4f& v = x[q >> 1];
-    unsigned h, m, l;
-    if (q & 1) split_pair(v.z, v.w, h, m, l); else split_pair(v.x, v.y, h, m, l);
-    H[q] = h; M[q] = m; L[q] = l;
-  };
-
   // ---- prologue:  A(0) B(0) A(1)
   load_a(0, xr[0]);
   fetch_b(0, 0);
@@ -115,19 +91,8 @@ __global__ __launch_bounds__(256, 2) void rowgemm_x3s8_k(GemmArgs a, const char*
                    Bl0 = __builtin_bit_cast(bf16x8, bq2[pp & 1][0][2]);
       const bf16x8 Bh1 = __builtin_bit_cast(bf16x8, bq2[pp & 1][1][0]), Bm1 = __builtin_bit_cast(bf16x8, bq2[pp & 1][1][1]),
                    Bl1 = __builtin_bit_cast(bf16x8, bq2[pp & 1][1][2]);
-      // small terms first, the leading term last (the order of every split-core kernel)
-      acc[n0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(Am, Bm0, acc[n0], 0, 0, 0);
-      if (two) acc[n1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(Am, Bm1, acc[n1], 0, 0, 0);
-      acc[n0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(Al, Bh0, acc[n0], 0, 0, 0);
-      if (two) acc[n1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(Al, Bh1, acc[n1], 0, 0, 0);
-      acc[n0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(Ah, Bl0, acc[n0], 0, 0, 0);
-      if (two) acc[n1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(Ah, Bl1, acc[n1], 0, 0, 0);
-      acc[n0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(Am, Bh0, acc[n0], 0, 0, 0);
-      if (two) acc[n1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(Am, Bh1, acc[n1], 0, 0, 0);
-      acc[n0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(Ah, Bm0, acc[n0], 0, 0, 0);
-      if (two) acc[n1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(Ah, Bm1, acc[n1], 0, 0, 0);
-      acc[n0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(Ah, Bh0, acc[n0], 0, 0, 0);
-      if (two) acc[n1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(Ah, Bh1, acc[n1], 0, 0, 0);
+      if (two) x3_chain2(acc[n0], acc[n1], Ah, Am, Al, Bh0, Bm0, Bl0, Ah, Am, Al, Bh1, Bm1, Bl1);
+      else x3_chain(acc[n0], Ah, Am, Al, Bh0, Bm0, Bl0);
 #pragma unroll
       for (int i = 0; i < (two ? 12 : 6); ++i) {
         __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);     // one MFMA ...
@@ -157,14 +122,11 @@ __global__ __launch_bounds__(256, 2) void rowgemm_x3s8_k(GemmArgs a, const char*
   else gemm_epilogue<NT, EPI>(a, acc, roww, 0, li, lh, row0 + GBM <= a.rows);
 }
 
-// 1 (default): plain launches whose output is eight column tiles wide run on rowgemm_x3s8_k; 0: two four-tile column blocks (round 3)
-inline int& gemm_wide8() { static int m = 1; return m; }
-
 template <int EPI>
 inline bool x3s8_eligible(const GemmArgs& a) {
   if (EPI == EPI_GATE) return false;                       // 55 register spills at eight tiles: keeps the two-block form
-  if (!(gemm_wide8() && a.grp.n == 0 && (a.K2 == 0 || !a.A2) && a.K1 >= 32 && x3s_eligible(a))) return false;
-  return (a.N > 224 && a.N <= 256) || (gemm_wide8() == 2 && a.N > 192 && a.N <= 224);   // 2 (lab): seven-tile outputs on the ring of two as well
+  if (!(gemm_switches().wide8 && a.grp.n == 0 && (a.K2 == 0 || !a.A2) && a.K1 >= 32 && x3s_eligible(a))) return false;
+  return (a.N > 224 && a.N <= 256) || (gemm_switches().wide8 == 2 && a.N > 192 && a.N <= 224);   // 2 (lab): seven-tile outputs on the ring of two as well
 }
 
 // Bp: the split of B prepared by launch_bsplit(..., nt = gemm_pick_nt(a.N) = 4, ...): [slab][8 tiles][plane][lane], the layout of one
@@ -176,17 +138,9 @@ inline int launch_rowgemm_x3s8(GemmArgs a, const void* Bp, hipStream_t st) {
   const int ntile = x3_tiles(a.N, gemm_pick_nt(a.N));      // 8 (7: the lab's seven-tile form)
   dim3 grid((unsigned)((a.rows + 127) / 128), 1);
   const size_t lds = (size_t)2 * ntile * 3 * 1024;
-  if (ntile == 8) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&rowgemm_x3s8_k<8, EPI>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    hipLaunchKernelGGL((rowgemm_x3s8_k<8, EPI>), grid, dim3(256), lds, st, a, (const char*)Bp, ntile);
-  } else if (ntile == 7) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&rowgemm_x3s8_k<7, EPI>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    hipLaunchKernelGGL((rowgemm_x3s8_k<7, EPI>), grid, dim3(256), lds, st, a, (const char*)Bp, ntile);
-  } else {
-    return MRG_E_SHAPE;
-  }
-  hipError_t e = hipGetLastError();
-  return e == hipSuccess ? MRG_OK : (int)e;
+  if (ntile == 8) return launch_kernel(rowgemm_x3s8_k<8, EPI>, grid, dim3(256), lds, st, a, Bp, ntile);
+  if (ntile == 7) return launch_kernel(rowgemm_x3s8_k<7, EPI>, grid, dim3(256), lds, st, a, Bp, ntile);
+  return MRG_E_SHAPE;
 }
 
 }  // namespace mrg

@@ -1,6 +1,9 @@
-// Dense linears on edge / node rows with exact-f32 MFMA (core: gemm.hpp).
+// Dense linears on edge / node rows: the C entry points of the row GEMMs and the weight-gradient kernels.
 //   nn.Linear inside a_max_op / a_mean_op: reference models/operations_lp.py:228,231,243,246
 //   W_O / W_I / W_S / W_R of CompGraphConv:  reference models/compgcn.py:36-41,77-78,100,103
+// Matrix cores: split bf16 by default (shared parts x3_parts.hpp, kernels gemm_x3*.hpp, which launch takes which kernel:
+// gemm_dispatch.hpp; weight gradient wgrad_x3v_k / wgrad_x3_k below), exact f32 (gemm.hpp; wgrad_dma_k / wgrad_k below) in mode 1
+// and for operands the split core cannot take.
 // forward / input-gradient use the pipelined row GEMM; the weight gradient is a split-over-rows
 // GEMM (each workgroup reduces a chunk of rows into register-resident output tiles, partial
 // tiles are combined in a fixed order), also software-pipelined, and optionally dual-source.
@@ -169,8 +172,6 @@ static __device__ float mrg_ones16[4] = {1.f, 0.f, 0.f, 0.f};
 template <int TPW, int NPF>
 __global__ __launch_bounds__(MRG_BLOCK, (TPW <= 7 ? 2 : 1)) void wgrad_dma_k(WgradArgs a) {
   extern __shared__ __align__(16) float smem[];
-  typedef __attribute__((address_space(3))) void* lds_ptr_t;
-  typedef const __attribute__((address_space(1))) void* gbl_ptr_t;
   const int tn0 = (int)(((int64_t)blockIdx.y * a.TN) / gridDim.y);
   const int tnb = (int)(((int64_t)(blockIdx.y + 1) * a.TN) / gridDim.y) - tn0;
   const int ldg = a.TM * 32, ldx = tnb * 32, stage = WBR * (ldg + a.TNB * 32);
@@ -294,6 +295,10 @@ __global__ __launch_bounds__(MRG_BLOCK, (TPW <= 7 ? 2 : 1)) void wgrad_dma_k(Wgr
 constexpr int WX_THREADS = 512;
 constexpr int WX_APITCH = 57 * 4;            // floats per A row in LDS (224 columns + one pad chunk)
 
+// wgrad_x3_k and wgrad_x3v_k share the arithmetic (x3_parts.hpp: split8, x3_chain, x3_chain2).  Their 40-line head (tile ownership,
+// accumulator clear, row range of a grouped launch) and their 12-line store tail stay spelled out in both: as helpers (a struct
+// returned by value, the accumulator array passed by reference) they compile to equivalent but not identical code, and
+// wgrad_x3v_k, at 255 registers, spilled with the clear alone moved out.
 template <int NG>
 __global__ __launch_bounds__(WX_THREADS, 1) void wgrad_x3_k(WgradArgs a) {
   constexpr int KP = 8 / NG, KT = 2 * KP;
@@ -302,8 +307,6 @@ __global__ __launch_bounds__(WX_THREADS, 1) void wgrad_x3_k(WgradArgs a) {
   constexpr int ACH = WBR * 57, BCH = WBR * (KT * 8 + 1), STAGE_CH = ACH + BCH;
   constexpr int NPF = (STAGE_CH + WX_THREADS - 1) / WX_THREADS;
   extern __shared__ __align__(16) float smem[];
-  typedef __attribute__((address_space(3))) void* lds_ptr_t;
-  typedef const __attribute__((address_space(1))) void* gbl_ptr_t;
   const int tn0 = (int)(((int64_t)blockIdx.y * a.TN) / gridDim.y);
   const int tnb = (int)(((int64_t)(blockIdx.y + 1) * a.TN) / gridDim.y) - tn0;
   const int tid = threadIdx.x, wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63, li = lane & 31, lh = lane >> 5;
@@ -392,12 +395,7 @@ __global__ __launch_bounds__(WX_THREADS, 1) void wgrad_x3_k(WgradArgs a) {
     asm volatile("ds_read_b32 %0, %1 offset:%2" : "=v"(v[7]) : "v"(addr), "n"(7 * PB));
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      unsigned h, m, l;
-      split_pair(v[2 * j], v[2 * j + 1], h, m, l);
-      H[j] = h; M[j] = m; L[j] = l;
-    }
+    split8(v, H, M, L);
   };
 
   if (r_begin < r_end) fetch(0, r_begin, 0);
@@ -428,25 +426,9 @@ __global__ __launch_bounds__(WX_THREADS, 1) void wgrad_x3_k(WgradArgs a) {
           const bf16x8 Bh0 = __builtin_bit_cast(bf16x8, bh[0]), Bm0 = __builtin_bit_cast(bf16x8, bm[0]), Bl0 = __builtin_bit_cast(bf16x8, bl[0]);
           if (kn > 1) {                                    // two accumulators interleaved: no back-to-back dependent MFMAs
             const bf16x8 Bh1 = __builtin_bit_cast(bf16x8, bh[1]), Bm1 = __builtin_bit_cast(bf16x8, bm[1]), Bl1 = __builtin_bit_cast(bf16x8, bl[1]);
-            acc[i][0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(Am, Bm0, acc[i][0], 0, 0, 0);
-            acc[i][1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(Am, Bm1, acc[i][1], 0, 0, 0);
-            acc[i][0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(Al, Bh0, acc[i][0], 0, 0, 0);
-            acc[i][1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(Al, Bh1, acc[i][1], 0, 0, 0);
-            acc[i][0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(Ah, Bl0, acc[i][0], 0, 0, 0);
-            acc[i][1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(Ah, Bl1, acc[i][1], 0, 0, 0);
-            acc[i][0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(Am, Bh0, acc[i][0], 0, 0, 0);
-            acc[i][1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(Am, Bh1, acc[i][1], 0, 0, 0);
-            acc[i][0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(Ah, Bm0, acc[i][0], 0, 0, 0);
-            acc[i][1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(Ah, Bm1, acc[i][1], 0, 0, 0);
-            acc[i][0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(Ah, Bh0, acc[i][0], 0, 0, 0);
-            acc[i][1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(Ah, Bh1, acc[i][1], 0, 0, 0);
+            x3_chain2(acc[i][0], acc[i][1], Ah, Am, Al, Bh0, Bm0, Bl0, Ah, Am, Al, Bh1, Bm1, Bl1);
           } else {
-            acc[i][0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(Am, Bm0, acc[i][0], 0, 0, 0);
-            acc[i][0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(Al, Bh0, acc[i][0], 0, 0, 0);
-            acc[i][0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(Ah, Bl0, acc[i][0], 0, 0, 0);
-            acc[i][0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(Am, Bh0, acc[i][0], 0, 0, 0);
-            acc[i][0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(Ah, Bm0, acc[i][0], 0, 0, 0);
-            acc[i][0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(Ah, Bh0, acc[i][0], 0, 0, 0);
+            x3_chain(acc[i][0], Ah, Am, Al, Bh0, Bm0, Bl0);
           }
         }
       }
@@ -486,7 +468,7 @@ __global__ __launch_bounds__(WX_THREADS, 1) void wgrad_x3v_k(WgradArgs a) {
   constexpr int NFRAG = ASLOTS + KT;
   constexpr int FPW = (NFRAG + 7) / 8;                    // fragments a wave produces per tile
   extern __shared__ __align__(16) float smem[];
-    const int tn0 = (int)(((int64_t)blockIdx.y * a.TN) / gridDim.y);
+  const int tn0 = (int)(((int64_t)blockIdx.y * a.TN) / gridDim.y);
   const int tnb = (int)(((int64_t)(blockIdx.y + 1) * a.TN) / gridDim.y) - tn0;
   const int tid = threadIdx.x, wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63, li = lane & 31, lh = lane >> 5;
   const int wg = wave / KP, wp = wave % KP;
@@ -507,7 +489,7 @@ __global__ __launch_bounds__(WX_THREADS, 1) void wgrad_x3v_k(WgradArgs a) {
   int64_t r_end = r_begin + a.rows_per_block;
   if (r_end > a.rows) r_end = a.rows;
   int64_t ws_off = 0;
-  if (a.ngrp > 0) {
+  if (a.ngrp > 0) {                                       // one row range per blockIdx.z (constant indices: no scratch copy of the arguments)
     const int z = blockIdx.z;
 #define MRG_PICKZ(F) (z == 0 ? a.F[0] : (z == 1 ? a.F[1] : a.F[2]))
     if ((int)blockIdx.x >= MRG_PICKZ(g_G)) return;          // workgroup-uniform, before any barrier
@@ -571,12 +553,7 @@ __global__ __launch_bounds__(WX_THREADS, 1) void wgrad_x3v_k(WgradArgs a) {
 #pragma unroll
         for (int j = 0; j < 8; ++j) x[j] = (!TAIL || kbase + j < nv_tail) ? raw[i][j] : 0.f;
         u32x4 H, M, L;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-          unsigned h, m, l;
-          split_pair(x[2 * j], x[2 * j + 1], h, m, l);
-          H[j] = h; M[j] = m; L[j] = l;
-        }
+        split8(x, H, M, L);
         const int f = wave + 8 * i;
         u32x4* dst = reinterpret_cast<u32x4*>(reinterpret_cast<char*>(smem) + buf * BUF_BYTES + f * 3072) + lane;
         dst[0] = H; dst[64] = M; dst[128] = L;
@@ -601,25 +578,9 @@ __global__ __launch_bounds__(WX_THREADS, 1) void wgrad_x3v_k(WgradArgs a) {
           const bf16x8 Ah = An[0], Am = An[1], Al = An[2];
           if (i + 1 < an) rdfrag(cur, m0 + i + 1, An[0], An[1], An[2]);
           if (kn > 1) {                                    // two accumulators interleaved: no back-to-back dependent MFMAs
-            acc[i][0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(Am, Bm0, acc[i][0], 0, 0, 0);
-            acc[i][1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(Am, Bm1, acc[i][1], 0, 0, 0);
-            acc[i][0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(Al, Bh0, acc[i][0], 0, 0, 0);
-            acc[i][1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(Al, Bh1, acc[i][1], 0, 0, 0);
-            acc[i][0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(Ah, Bl0, acc[i][0], 0, 0, 0);
-            acc[i][1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(Ah, Bl1, acc[i][1], 0, 0, 0);
-            acc[i][0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(Am, Bh0, acc[i][0], 0, 0, 0);
-            acc[i][1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(Am, Bh1, acc[i][1], 0, 0, 0);
-            acc[i][0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(Ah, Bm0, acc[i][0], 0, 0, 0);
-            acc[i][1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(Ah, Bm1, acc[i][1], 0, 0, 0);
-            acc[i][0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(Ah, Bh0, acc[i][0], 0, 0, 0);
-            acc[i][1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(Ah, Bh1, acc[i][1], 0, 0, 0);
+            x3_chain2(acc[i][0], acc[i][1], Ah, Am, Al, Bh0, Bm0, Bl0, Ah, Am, Al, Bh1, Bm1, Bl1);
           } else {
-            acc[i][0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(Am, Bm0, acc[i][0], 0, 0, 0);
-            acc[i][0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(Al, Bh0, acc[i][0], 0, 0, 0);
-            acc[i][0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(Ah, Bl0, acc[i][0], 0, 0, 0);
-            acc[i][0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(Am, Bh0, acc[i][0], 0, 0, 0);
-            acc[i][0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(Ah, Bm0, acc[i][0], 0, 0, 0);
-            acc[i][0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(Ah, Bh0, acc[i][0], 0, 0, 0);
+            x3_chain(acc[i][0], Ah, Am, Al, Bh0, Bm0, Bl0);
           }
         }
       }
@@ -669,23 +630,13 @@ __global__ __launch_bounds__(WX_THREADS, 1) void wgrad_x3v_k(WgradArgs a) {
       }
 }
 
-static int g_wgrad_variant = 1;           // 1: fragments split once per workgroup (wgrad_x3v_k), 0: per consuming wave (wgrad_x3_k)
-inline int wgrad_variant() { return g_wgrad_variant; }
-
 template <int NG>
-static void launch_wgrad_x3(dim3 grid, const WgradArgs& a, hipStream_t st) {
+static int launch_wgrad_x3(dim3 grid, const WgradArgs& a, hipStream_t st) {
   const int kt = 16 / NG;
-  bool v1 = wgrad_variant() == 1 && a.rows >= WBR;         // (its ragged last tile is the 16 rows ENDING at the range's end)
+  bool v1 = gemm_switches().wgrad_variant == 1 && a.rows >= WBR;         // (its ragged last tile is the 16 rows ENDING at the range's end)
   for (int i = 0; i < a.ngrp; ++i) v1 = v1 && !(a.g_hi[i] > a.g_lo[i] && a.g_hi[i] < WBR);
-  if (v1) {
-    const size_t lds = (size_t)2 * ((((NG == 2 ? 8 : 4) + kt) + 7) / 8 * 8) * 3 * 1024;
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&wgrad_x3v_k<NG>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    hipLaunchKernelGGL((wgrad_x3v_k<NG>), grid, dim3(WX_THREADS), lds, st, a);
-  } else {
-    const size_t ldsx = (size_t)(NG == 2 ? 4 : 3) * WBR * (57 + kt * 8 + 1) * 16;
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&wgrad_x3_k<NG>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsx);
-    hipLaunchKernelGGL((wgrad_x3_k<NG>), grid, dim3(WX_THREADS), ldsx, st, a);
-  }
+  if (v1) return launch_kernel(wgrad_x3v_k<NG>, grid, dim3(WX_THREADS), (size_t)2 * ((((NG == 2 ? 8 : 4) + kt) + 7) / 8 * 8) * 3 * 1024, st, a);
+  return launch_kernel(wgrad_x3_k<NG>, grid, dim3(WX_THREADS), (size_t)(NG == 2 ? 4 : 3) * WBR * (57 + kt * 8 + 1) * 16, st, a);
 }
 
 // gW[n][c] = sum_g ws[g][n][c] (c < K);  gbias[n] = sum_g ws[g][n][K]   -- fixed order:
@@ -828,9 +779,8 @@ static int launch_wgrad_one(const float* gY, int ldg, const float* X1, const flo
   if (vec && gemm_mode() != 1 && p.TM <= 7) {        // split-bf16 core
     const int ng = p.TM <= 4 ? 1 : 2, kt = 16 / ng;
     dim3 gridx(p.G, (p.TN + kt - 1) / kt);
-    if (ng == 1) launch_wgrad_x3<1>(gridx, a, st);
-    else launch_wgrad_x3<2>(gridx, a, st);
-    MRG_LAUNCH_CHECK();
+    const int rcx = ng == 1 ? launch_wgrad_x3<1>(gridx, a, st) : launch_wgrad_x3<2>(gridx, a, st);
+    if (rcx != MRG_OK) return rcx;
     WgradReduce3 red{};
     red.ws[0] = (const float*)ws; red.gW[0] = gW; red.gbias[0] = gbias; red.G[0] = p.G;
     hipLaunchKernelGGL(wgrad_reduce3_k, dim3((K + 1 + 63) / 64, Nout, 1), dim3(1024), 0, st, red, K, Nout, p.TM * 32, p.TN * 32);
@@ -953,38 +903,37 @@ extern "C" int64_t mrg_gemm_workspace_bytes(int K, int Nout) {
 
 extern "C" int mrg_gemm_set_mode(int mode) {
   if (mode < 0 || mode > 2) return MRG_E_ENUM;
-  gemm_mode() = mode;
+  gemm_switches().mode = mode;
   return MRG_OK;
 }
 
 extern "C" int mrg_wgrad_set_variant(int variant) {
   if (variant != 0 && variant != 1) return MRG_E_ENUM;
-  g_wgrad_variant = variant;
+  gemm_switches().wgrad_variant = variant;
   return MRG_OK;
 }
 
 extern "C" int mrg_gemm_set_wide8(int on) {
   if (on < 0 || on > 2) return MRG_E_ENUM;          // 2 (lab): seven-tile plain launches on the ring-of-two kernel as well
-  gemm_wide8() = on;
+  gemm_switches().wide8 = on;
   return MRG_OK;
 }
 
 extern "C" int mrg_gemm_set_small(int on) {
   if (on < 0) return MRG_E_ENUM;
-  gemm_small() = on == 1 ? X3N_MAX_ROWS : (int64_t)on;      // 0 off, 1 the default bound, > 1 (lab) that many rows
+  gemm_switches().small_rows = on == 1 ? X3N_MAX_ROWS : (int64_t)on;      // 0 off, 1 the default bound, > 1 (lab) that many rows
   return MRG_OK;
 }
 
 extern "C" int mrg_gemm_set_q(int on) {
   if (on < 0 || on > 2) return MRG_E_ENUM;          // 2 (lab, tests): every eligible K, not only K > 224
-  gemm_q() = on;
+  gemm_switches().q = on;
   return MRG_OK;
 }
 
 extern "C" int mrg_gemm_set_epilogue(int mode) {
   if (mode < 0 || mode > 2) return MRG_E_ENUM;
-  gemm_epi_lds() = mode == 1 ? 1 : 0;
-  gemm_epi_mode() = mode;
+  gemm_switches().epilogue = mode;
   return MRG_OK;
 }
 
@@ -1154,9 +1103,8 @@ extern "C" int mrg_linear_bwd_weight3(const float* gY, const float* X1, const fl
   if (maxG == 0) return MRG_OK;
   const int ng = a.TM <= 4 ? 1 : 2, kt = 16 / ng;
   dim3 gridx(maxG, (a.TN + kt - 1) / kt, 3);
-  if (ng == 1) launch_wgrad_x3<1>(gridx, a, st);
-  else launch_wgrad_x3<2>(gridx, a, st);
-  MRG_LAUNCH_CHECK();
+  const int rcx = ng == 1 ? launch_wgrad_x3<1>(gridx, a, st) : launch_wgrad_x3<2>(gridx, a, st);
+  if (rcx != MRG_OK) return rcx;
   hipLaunchKernelGGL(wgrad_reduce3_k, dim3((K + 1 + 63) / 64, Nout, 3), dim3(1024), 0, st, red, K, Nout, a.TM * 32, a.TN * 32);
   MRG_LAUNCH_CHECK();
   return MRG_OK;

@@ -40,12 +40,12 @@ int main(int argc, char** argv) {
     printf("%-28s %8.3f ms  %7.1f TF/s (f32-equivalent)  err=%s\n", name, ms, 2.0 * rows * K * N / ms * 1e-9, hipGetErrorString(hipGetLastError()));
   };
   timeit("x3 (split + gemm)", [&] { launch_bsplit(B, K, 1, N, K, nt, Bp, 0); launch_rowgemm_x3<EPI_BIAS_ACT>(a, Bp, 0); });
-  gemm_epi_lds() = 0;
+  gemm_switches().epilogue = 0;
   timeit("x3 (gemm only, acc-order stores)", [&] { launch_rowgemm_x3<EPI_BIAS_ACT>(a, Bp, 0); });
   std::vector<float> c0(rows * N);
   hipMemcpy(c0.data(), C, c0.size() * 4, hipMemcpyDeviceToHost);
   hipMemset(C, 0, rows * N * 4);
-  gemm_epi_lds() = 1;
+  gemm_switches().epilogue = 1;
   timeit("x3 (gemm only, row-order stores)", [&] { launch_rowgemm_x3<EPI_BIAS_ACT>(a, Bp, 0); });
   {
     std::vector<float> cx(rows * N);
@@ -57,21 +57,21 @@ int main(int argc, char** argv) {
   {   // accumulate epilogue (C += ...) both ways
     GemmArgs g = a; g.Cin = C2; g.ld_cin = N; g.bias = nullptr;
     hipMemset(C2, 0, rows * N * 4);
-    gemm_epi_lds() = 0;
+    gemm_switches().epilogue = 0;
     timeit("x3 accumulate, acc-order", [&] { launch_rowgemm_x3<EPI_ACCUM>(g, Bp, 0); });
-    gemm_epi_lds() = 1;
+    gemm_switches().epilogue = 1;
     timeit("x3 accumulate, row-order", [&] { launch_rowgemm_x3<EPI_ACCUM>(g, Bp, 0); });
     GemmArgs q = a; q.S = A1; q.ld_s = K1; q.aux = C2; q.scale = 1.f / 3; 
     if (K1 == N) {
-      gemm_epi_lds() = 0;
+      gemm_switches().epilogue = 0;
       timeit("x3 gate (+aux), acc-order", [&] { launch_rowgemm_x3<EPI_GATE>(q, Bp, 0); });
-      gemm_epi_lds() = 1;
+      gemm_switches().epilogue = 1;
       timeit("x3 gate (+aux), row-order", [&] { launch_rowgemm_x3<EPI_GATE>(q, Bp, 0); });
     }
     launch_rowgemm_x3<EPI_BIAS_ACT>(a, Bp, 0);      // C as the error check below expects it
   }
   {
-    gemm_epi_lds() = 0;
+    gemm_switches().epilogue = 0;
     launch_rowgemm_x3<EPI_BIAS_ACT>(a, Bp, 0);
     std::vector<float> cref(rows * N), cs(rows * N);
     hipMemcpy(cref.data(), C, cref.size() * 4, hipMemcpyDeviceToHost);
@@ -89,9 +89,9 @@ int main(int argc, char** argv) {
     }
     launch_rowgemm_x3<EPI_BIAS_ACT>(a, Bp, 0);
   }
-  if (getenv("MRG_LAB_RING2")) gemm_wide8() = 2;   // seven-tile outputs on the ring-of-two kernel as well
+  if (getenv("MRG_LAB_RING2")) gemm_switches().wide8 = 2;   // seven-tile outputs on the ring-of-two kernel as well
   if (x3s8_eligible<EPI_BIAS_ACT>(a)) {   // round 4: eight column tiles as ONE block (gemm_x3s8.hpp) against two four-tile blocks
-    gemm_epi_mode() = 0;
+    gemm_switches().epilogue = 0;
     launch_rowgemm_x3<EPI_BIAS_ACT>(a, Bp, 0);
     std::vector<float> cref(rows * N), cs(rows * N);
     hipMemcpy(cref.data(), C, cref.size() * 4, hipMemcpyDeviceToHost);
@@ -122,7 +122,7 @@ int main(int argc, char** argv) {
       if (e == 1) { g.Cin = C2; g.ld_cin = N; g.bias = nullptr; }
       if (e == 2 || e == 3) { g.S = A1; g.ld_s = K1; g.aux = AUX; g.scale = 1.f / 3; if (e == 3) g.C = nullptr; }
       for (int mode = 0; mode <= 2; mode += 2) {
-        gemm_epi_mode() = mode;
+        gemm_switches().epilogue = mode;
         hipMemset(C, 0, rows * N * 4); hipMemset(AUX, 0, rows * N * 4);
         char label[96]; snprintf(label, sizeof label, "x3s %s, %s", name, mode ? "transposed acc" : "acc-order");
         timeit(label, [&] {
@@ -135,7 +135,7 @@ int main(int argc, char** argv) {
       cmp(name, r0, r1);
       if (e >= 2) cmp("its gate", x0, x1);
     }
-    gemm_epi_mode() = 2;
+    gemm_switches().epilogue = 2;
     hipFree(AUX);
     launch_rowgemm_x3<EPI_BIAS_ACT>(a, Bp, 0);
   }

@@ -50,8 +50,6 @@ __global__ __launch_bounds__(X3_THREADS, 1) void rowgemm_x3p_k(GemmArgs a, const
   constexpr int PP = NT > 1 ? (NPAIR + NT - 2) / (NT - 1) : NPAIR;
   constexpr int RING_F = X3_SLOTS * SLOT_CH * 4;                 // floats per wave ring
   extern __shared__ __align__(16) float smem[];
-  typedef __attribute__((address_space(3))) void* lds_ptr_t;
-  typedef const __attribute__((address_space(1))) void* gbl_ptr_t;
   const int tid = threadIdx.x, wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63, li = lane & 31, lh = lane >> 5;
   const int wstride = gridDim.x * (X3_THREADS / 64);
   int t = blockIdx.x * (X3_THREADS / 64) + wave;
@@ -127,12 +125,7 @@ __global__ __launch_bounds__(X3_THREADS, 1) void rowgemm_x3p_k(GemmArgs a, const
   };
   u32x4 ch[MT], cm[MT], cl[MT], nh[MT], nm[MT], nl[MT];
   auto split_one = [&](int j, u32x4 (&H)[MT], u32x4 (&M)[MT], u32x4 (&L)[MT]) {
-    const int m = j >> 2, q = j & 3;
-    const v4f_t& v = x[m][q >> 1];
-    unsigned h, mm, l;
-    if (q & 1) split_pair(v.z, v.w, h, mm, l);
-    else split_pair(v.x, v.y, h, mm, l);
-    H[m][q] = h; M[m][q] = mm; L[m][q] = l;
+    split_pair_of(x[j >> 2], j & 3, H[j >> 2], M[j >> 2], L[j >> 2]);
   };
 
   int tn = t + wstride;
@@ -180,16 +173,7 @@ __global__ __launch_bounds__(X3_THREADS, 1) void rowgemm_x3p_k(GemmArgs a, const
       const bf16x8 Bh = __builtin_bit_cast(bf16x8, bq[n][0]), Bm = __builtin_bit_cast(bf16x8, bq[n][1]),
                    Bl = __builtin_bit_cast(bf16x8, bq[n][2]);
       // transposed product: the weight fragment is the A operand, the activation fragment the B operand
-#define MRG_X3P_TERM(AP, BP)                                                                            \
-  _Pragma("unroll") for (int m = 0; m < MT; ++m)                                                          \
-      acc[m][n] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(BP, __builtin_bit_cast(bf16x8, AP[m]), acc[m][n], 0, 0, 0)
-      MRG_X3P_TERM(cm, Bm);
-      MRG_X3P_TERM(cl, Bh);
-      MRG_X3P_TERM(ch, Bl);
-      MRG_X3P_TERM(cm, Bh);
-      MRG_X3P_TERM(ch, Bm);
-      MRG_X3P_TERM(ch, Bh);
-#undef MRG_X3P_TERM
+      x3_chain_rows<true>(acc, n, ch, cm, cl, Bh, Bm, Bl);
       if (n == NT - 1) {
 #pragma unroll
         for (int m = 0; m < MT; ++m) { ch[m] = nh[m]; cm[m] = nm[m]; cl[m] = nl[m]; }

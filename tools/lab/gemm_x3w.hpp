@@ -40,9 +40,6 @@ __device__ __forceinline__ void x3w_wave_tile(const GemmArgs& a, const char* __r
   constexpr int SLOT_CH = WROWS * 4;          // 16-byte chunks per ring slot
   constexpr int NA = SLOT_CH / 64;            // DMA instructions per slab (4)
   constexpr int NBL = 3 * NT;                 // B loads per slab
-  typedef __attribute__((address_space(3))) void* lds_ptr_t;
-  typedef const __attribute__((address_space(1))) void* gbl_ptr_t;
-  typedef float v4f __attribute__((ext_vector_type(4)));
   const int li = lane & 31, lh = lane >> 5;
   const int K = a.K1 + a.K2;
   const int nslab = (K + 15) >> 4;
@@ -136,13 +133,7 @@ __device__ __forceinline__ void x3w_wave_tile(const GemmArgs& a, const char* __r
 #pragma unroll
     for (int m = 0; m < MT; ++m)
 #pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        const v4f& v = x[m][q >> 1];
-        unsigned h, mm, l;
-        if (q & 1) split_pair(v.z, v.w, h, mm, l);
-        else split_pair(v.x, v.y, h, mm, l);
-        ch[m][q] = h; cm[m][q] = mm; cl[m][q] = l;
-      }
+      for (int q = 0; q < 4; ++q) split_pair_of(x[m], q, ch[m], cm[m], cl[m]);
 #pragma unroll
     for (int n = 0; n < NT; ++n) {
       // B(s) tile n: younger = rest of B(s), this slab's A DMA, the B(s+1) tiles issued so far
@@ -152,16 +143,7 @@ __device__ __forceinline__ void x3w_wave_tile(const GemmArgs& a, const char* __r
       __builtin_amdgcn_sched_barrier(0);
       const bf16x8 Bh = __builtin_bit_cast(bf16x8, bq[n][0]), Bm = __builtin_bit_cast(bf16x8, bq[n][1]),
                    Bl = __builtin_bit_cast(bf16x8, bq[n][2]);
-#define MRG_X3W_TERM(AP, BP)                                                                            \
-  _Pragma("unroll") for (int m = 0; m < MT; ++m)                                                          \
-      acc[m][n] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, AP[m]), BP, acc[m][n], 0, 0, 0)
-      MRG_X3W_TERM(cm, Bm);
-      MRG_X3W_TERM(cl, Bh);
-      MRG_X3W_TERM(ch, Bl);
-      MRG_X3W_TERM(cm, Bh);
-      MRG_X3W_TERM(ch, Bm);
-      MRG_X3W_TERM(ch, Bh);
-#undef MRG_X3W_TERM
+      x3_chain_rows(acc, n, ch, cm, cl, Bh, Bm, Bl);
       __builtin_amdgcn_sched_barrier(0);
       if (has_next && !((MRG_X3_DBG & 32) && s > 0)) load_b(n, s + 1);
     }
