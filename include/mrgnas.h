@@ -34,7 +34,7 @@
 extern "C" {
 #endif
 
-#define MRG_ABI_VERSION 19   /* 19: mrg_seg_std_workspace_bytes, mrg_seg_std_fwd, mrg_seg_std_bwd (a_std, the standard-deviation aggregator of the node-classification task); 18: mrg_conve_* (the ConvE feature path: BN0 statistics, conv, BN1, split-K fc and their gradients, stacked or interleaved image layout); 17: mrg_ccorr_rows, mrg_ccorr_matrix, mrg_ccorr_matrix_grad (standalone circular correlation: per-row kernel, and the circulant of a shared row with its gradient fold for the row GEMM); 16: mrg_set_stream_blocks, mrg_gate_collapse and mrg_gate_param_grad removed (the streaming grid bound is fixed; the three-segment forms remain); 15: mrg_gated_branch.valid_rows and the valid_rows argument of mrg_mix_finalize_bwd / mrg_zero_* except colstats (the device row count of a static step graph, passed per call instead of the process-wide registry of 13), mrg_linear_bwd_weight_share (the weight gradient of one range of a grouped launch, instead of the process-wide setter of 14); 14: mrg_clip_sgd_step, mrg_optim_chunk (clip_grad_norm_ + SGD with momentum over every parameter tensor in three launches), mrg_gated_branch.act (tanh behind the BatchNorm: CompGraphConv's tail on the epilogue kernels), mrg_gemm_set_small (few-row products on two-tile column blocks), a weight-gradient share setter, mrg_segmax_bwd_input (a_max's input gradient without a dense product); 13: a registry of device-side row counts (the sampled search step as one replayable HIP graph), mrg_seg_reduce_bwd_ordered (aggregator backward walked in destination order), mrg_gemm_set_q (the 16 x 16 x 32 row GEMM at three workgroups per CU for 129..224 output columns); 12: mrg_act_grad_transpose (the [B, N] scorer's output gradient, activation folded in, as [N, B] rows); 11: mrg_gemm_set_wide8 (eight-tile column block for D = 256); 10: mrg_gemm_set_epilogue(2) (transposed accumulators: a tested comparison point); 9: mrg_gated_branch (the MixedOp epilogue recomputes f_dense_comp's output from its gate and f_sparse_comp's from its row factor), mrg_gate_row_fwd / _bwd, mrg_sum_rows_gather, mrg_wgrad_set_variant, mrg_dense_filter_fwd3 out == NULL; 8: mrg_zero_* (cell-zero MixedOp recomputed from the tables), mrg_linear_bwd_input3_pair, mrg_sample_edge_neighborhood; 7: mrg_gemm_set_epilogue (row-order stores of the split-core row GEMM), mrg_set_stream_blocks, mrg_gemm_set_mode(2); 6: fused a_mean (run-sum epilogue, heads reducer, bit-mask backward), mrg_mix_stats_coef; 5: three-segment dense filter entry points; 4: mrg_linear_relu_segmax_fwd (fused a_max); 3: device graph / plan builders, samplers, [B, N] scorers, ranking; 2: GEMM workspaces, span_gcs ext_scal */
+#define MRG_ABI_VERSION 20   /* 20: BatchNorm sums formed by a candidate's producer: mrg_gated_branch.given / given_n / given_stride (mrg_mix_stats_coef skips the sweep over such a candidate), mrg_dense_filter3_colsum_blocks, mrg_dense_filter_fwd3_colsum, mrg_gate_row_colsum_blocks, mrg_gate_row_fwd_colsum; 19: mrg_seg_std_workspace_bytes, mrg_seg_std_fwd, mrg_seg_std_bwd (a_std, the standard-deviation aggregator of the node-classification task); 18: mrg_conve_* (the ConvE feature path: BN0 statistics, conv, BN1, split-K fc and their gradients, stacked or interleaved image layout); 17: mrg_ccorr_rows, mrg_ccorr_matrix, mrg_ccorr_matrix_grad (standalone circular correlation: per-row kernel, and the circulant of a shared row with its gradient fold for the row GEMM); 16: mrg_set_stream_blocks, mrg_gate_collapse and mrg_gate_param_grad removed (the streaming grid bound is fixed; the three-segment forms remain); 15: mrg_gated_branch.valid_rows and the valid_rows argument of mrg_mix_finalize_bwd / mrg_zero_* except colstats (the device row count of a static step graph, passed per call instead of the process-wide registry of 13), mrg_linear_bwd_weight_share (the weight gradient of one range of a grouped launch, instead of the process-wide setter of 14); 14: mrg_clip_sgd_step, mrg_optim_chunk (clip_grad_norm_ + SGD with momentum over every parameter tensor in three launches), mrg_gated_branch.act (tanh behind the BatchNorm: CompGraphConv's tail on the epilogue kernels), mrg_gemm_set_small (few-row products on two-tile column blocks), a weight-gradient share setter, mrg_segmax_bwd_input (a_max's input gradient without a dense product); 13: a registry of device-side row counts (the sampled search step as one replayable HIP graph), mrg_seg_reduce_bwd_ordered (aggregator backward walked in destination order), mrg_gemm_set_q (the 16 x 16 x 32 row GEMM at three workgroups per CU for 129..224 output columns); 12: mrg_act_grad_transpose (the [B, N] scorer's output gradient, activation folded in, as [N, B] rows); 11: mrg_gemm_set_wide8 (eight-tile column block for D = 256); 10: mrg_gemm_set_epilogue(2) (transposed accumulators: a tested comparison point); 9: mrg_gated_branch (the MixedOp epilogue recomputes f_dense_comp's output from its gate and f_sparse_comp's from its row factor), mrg_gate_row_fwd / _bwd, mrg_sum_rows_gather, mrg_wgrad_set_variant, mrg_dense_filter_fwd3 out == NULL; 8: mrg_zero_* (cell-zero MixedOp recomputed from the tables), mrg_linear_bwd_input3_pair, mrg_sample_edge_neighborhood; 7: mrg_gemm_set_epilogue (row-order stores of the split-core row GEMM), mrg_set_stream_blocks, mrg_gemm_set_mode(2); 6: fused a_mean (run-sum epilogue, heads reducer, bit-mask backward), mrg_mix_stats_coef; 5: three-segment dense filter entry points; 4: mrg_linear_relu_segmax_fwd (fused a_max); 3: device graph / plan builders, samplers, [B, N] scorers, ranking; 2: GEMM workspaces, span_gcs ext_scal */
 
 #define MRG_OK            0
 #define MRG_E_NULLPTR    -1   /* a required pointer is NULL */
@@ -134,6 +134,14 @@ int mrg_gate_bwd(const float *gout, const float *s, const float *s_in, const flo
  * s * fvec[r] equals its output bit for bit); hvec[r] = t_r * gate * (1 - gate).  fvec, hvec: [M]. */
 int mrg_gate_row_fwd(const float *s, const float *s_in, const float *norm, const float *uvc, float *fvec, float *hvec,
                      int64_t b0, int64_t b1, int64_t M, int D, float scale, void *stream);
+/* mrg_gate_row_fwd that also leaves the float64 column sums of the two MixedOp candidates that are functions of the rows it streams
+ * (f_identity: s; the row factor: the float32 product s[r][c] * fvec[r]) for mrg_gated_branch.given: colsum
+ * [blocks][2 (s, s * f)][2 (sum, sum of squares)][D], blocks = mrg_gate_row_colsum_blocks(b0, b1, M, D, vec4) with vec4 = (D % 4 == 0
+ * and s, s_in, uvc 16-byte aligned); 0 = not available (D beyond one 16-byte step per lane: the caller keeps the statistics pass).
+ * colsum_blocks: what the caller sized colsum for (MRG_E_SHAPE when the launch would write another number).  Deterministic. */
+int64_t mrg_gate_row_colsum_blocks(int64_t b0, int64_t b1, int64_t M, int D, int vec4);
+int mrg_gate_row_fwd_colsum(const float *s, const float *s_in, const float *norm, const float *uvc, float *fvec, float *hvec,
+                            int64_t b0, int64_t b1, int64_t M, int D, float scale, void *stream, double *colsum, int64_t colsum_blocks);
 /* q [M] (mrg_mix_bwd_apply's row_dq: the gradient w.r.t. fvec), dz_r = q_r * hvec[r] -> gs_in [M, D] = dz_r * v (s_in != NULL)
  * and d_uvc [3][MRG_GATE_LD(D)] for mrg_gate_param_grad3; the gradient w.r.t. s was added by the epilogue.
  * ws: mrg_gate_bwd_workspace_bytes(M, D). */
@@ -313,6 +321,7 @@ int mrg_clip_sgd_step(void *const *params, const void *const *grads, void *const
  * self rows once per graph (in float32, as the epilogue multiplies them).  One [rows, D] write per MixedOp and two reads of its
  * backward less; s is the MixedOp's input state.
  * In mrg_mix_bwd_apply, when rs_on[k] == 2 for this k, fold_s[k] must be `s` and fold_gate[k] must be y_host[k]. */
+#define MRG_MIX_MAX_CANDIDATES 8     /* K of the mrg_mix_* entry points is at most this */
 typedef struct mrg_gated_branch {
   int32_t k;               /* the gated candidate, < 0: none */
   const float *s;          /* [rows, D] device */
@@ -341,6 +350,16 @@ typedef struct mrg_gated_branch {
   /* ABI 15: the launch's device row count (valid_rows above), NULL = every row is valid.  Like act, it may be the only thing a
    * descriptor with k < 0 and row_k < 0 carries. */
   const int32_t *valid_rows;
+  /* ABI 20, mrg_mix_stats_coef only (mrg_mix_colstats: MRG_E_SHAPE; the other entry points ignore them): BatchNorm sums that the
+   * PRODUCER of candidate q formed while it had the values in registers (mrg_dense_filter_fwd3_colsum: f_dense_comp's and f_comp's
+   * output; mrg_gate_row_fwd_colsum: s itself and s * row_f[r]).  given[q]: NULL, or given_n[q] >= 1 partial sums
+   * [2][D] float64 (column sums, then column sums of squares, of the float32 values the candidate has -- all `rows` rows),
+   * given_stride[q] >= 2 D doubles apart.  The statistics kernel skips such a candidate -- when every non-zero candidate is given
+   * it does not run and no [rows, D] tensor is read -- and the partials are added in index order (deterministic).  Not with
+   * valid_rows (MRG_E_SHAPE).  Like act, they may be all a descriptor with k < 0 and row_k < 0 carries. */
+  const double *given[MRG_MIX_MAX_CANDIDATES];
+  int32_t given_n[MRG_MIX_MAX_CANDIDATES];
+  int64_t given_stride[MRG_MIX_MAX_CANDIDATES];
 } mrg_gated_branch;
 int mrg_mix_colstats(const float *const *y_host, int K, int64_t rows, int D, double *sums, void *ws,
                      const mrg_gated_branch *gated, void *stream);
@@ -537,6 +556,16 @@ int64_t mrg_dense_filter3_workspace_bytes(int D, int K);
 int mrg_dense_filter_fwd3(int kind, const float *s, const float *s_in, const float *const *W, const float *const *bias,
                           const float *norm, float scale_edge, float scale_self, float *out, float *gate, void *ws,
                           int64_t b0, int64_t b1, int64_t M, int D, void *stream);
+/* mrg_dense_filter_fwd3 that also leaves the float64 column sums of its output (kind 0: of gate * s * c, whether out is stored or
+ * not -- then the multiplicand s is read by the epilogue) for mrg_gated_branch.given: colsum [blocks][2 (sum, sum of squares)][D],
+ * one partial per workgroup, added inside the workgroup in a fixed order (no atomics).  blocks =
+ * mrg_dense_filter3_colsum_blocks(kind, b0, b1, M, D, K); 0 = the kernel this launch would take has no such form (exact-f32 core,
+ * few rows, D outside 132..224, a non-default epilogue switch): the caller keeps the statistics pass.  colsum_blocks: what the
+ * caller sized colsum for (MRG_E_SHAPE when the launch would write another number). */
+int64_t mrg_dense_filter3_colsum_blocks(int kind, int64_t b0, int64_t b1, int64_t M, int D, int K);
+int mrg_dense_filter_fwd3_colsum(int kind, const float *s, const float *s_in, const float *const *W, const float *const *bias,
+                                 const float *norm, float scale_edge, float scale_self, float *out, float *gate, void *ws,
+                                 int64_t b0, int64_t b1, int64_t M, int D, void *stream, double *colsum, int64_t colsum_blocks);
 /* dz (and the direct term of gs) for all M rows of the three segments in one launch: rows [0, b1) c = scale_edge * norm[row],
  * rows [b1, M) c = scale_self (see mrg_dense_filter_dz). */
 int mrg_dense_filter_dz3(int kind, const float *g, const float *s, const float *gate, const float *norm, float scale_edge,

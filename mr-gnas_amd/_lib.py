@@ -14,7 +14,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("MRG_LIB_PATH") or os.path.join(_HERE, "lib", "libmrgnas_hip.so")     # MRG_LIB_PATH: lab builds of the same ABI
 HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "mrgnas.h")
 
-ABI_VERSION = 19
+ABI_VERSION = 20
 
 
 class MrgnasLibraryError(RuntimeError):
@@ -51,6 +51,8 @@ SIGNATURES = {
     "mrg_sum_rows_gather": (_I, [_P, _I, _P, _P, _P, _L, _L, _I, _P, _P]),
     "mrg_distmult_score": (_I, [_P, _P, _P, _P, _P, _P, _L, _I, _P]),
     "mrg_gate_row_fwd": (_I, [_P, _P, _P, _P, _P, _P, _L, _L, _L, _I, _F, _P]),
+    "mrg_gate_row_colsum_blocks": (_L, [_L, _L, _L, _I, _I]),
+    "mrg_gate_row_fwd_colsum": (_I, [_P, _P, _P, _P, _P, _P, _L, _L, _L, _I, _F, _P, _P, _L]),
     "mrg_gate_row_bwd": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _L, _L, _L, _I, _P]),
     "mrg_mix_workspace_bytes": (_L, [_I, _I]),
     "mrg_mix_colstats": (_I, [_P, _I, _L, _I, _P, _P, _P, _P]),
@@ -86,6 +88,8 @@ SIGNATURES = {
     "mrg_linear_fwd": (_I, [_P, _P, _P, _P, _P, _L, _I, _I, _I, _P]),
     "mrg_dense_filter3_workspace_bytes": (_L, [_I, _I]),
     "mrg_dense_filter_fwd3": (_I, [_I, _P, _P, _P, _P, _P, _F, _F, _P, _P, _P, _L, _L, _L, _I, _P]),
+    "mrg_dense_filter3_colsum_blocks": (_L, [_I, _L, _L, _L, _I, _I]),
+    "mrg_dense_filter_fwd3_colsum": (_I, [_I, _P, _P, _P, _P, _P, _F, _F, _P, _P, _P, _L, _L, _L, _I, _P, _P, _L]),
     "mrg_dense_filter_dz3": (_I, [_I, _P, _P, _P, _P, _F, _F, _P, _P, _L, _L, _I, _P]),
     "mrg_linear_bwd_input3_workspace_bytes": (_L, [_I, _I]),
     "mrg_linear_bwd_input3": (_I, [_P, _P, _P, _P, _L, _L, _L, _I, _I, _I, _I, _P]),
@@ -209,11 +213,14 @@ def _trace(name, args):
     print(f"[mrg] {name} {shown}", file=sys.stderr, flush=True)
 
 
-def call(name, args, nbytes=0, flops=0):
-    """Invoke C-ABI function `name`; raise on a non-zero return code."""
-    fn = _FN.get(name)
+def call(name, args, nbytes=0, flops=0, symbol=None):
+    """Invoke C-ABI function `name`; raise on a non-zero return code.  symbol: the C function to call when it is a variant of `name`
+    with trailing arguments (mrg_dense_filter_fwd3_colsum, mrg_gate_row_fwd_colsum): traces, the meter and bench.py's tables
+    keep one logical name per entry point."""
+    sym = symbol or name
+    fn = _FN.get(sym)
     if fn is None:
-        fn = _FN[name] = getattr(load(), name)
+        fn = _FN[sym] = getattr(load(), sym)
     if TRACE:
         _trace(name, args)
         code = fn(*args)
@@ -257,25 +264,43 @@ class GatedBranch(ctypes.Structure):
     _fields_ = [("k", ctypes.c_int32), ("s", ctypes.c_void_p), ("rowscale", ctypes.c_void_p),
                 ("row_k", ctypes.c_int32), ("row_f", ctypes.c_void_p), ("row_h", ctypes.c_void_p), ("row_uvc", ctypes.c_void_p),
                 ("row_ld", ctypes.c_int32), ("b0", ctypes.c_int64), ("b1", ctypes.c_int64), ("row_dq", ctypes.c_void_p),
-                ("act", ctypes.c_int32), ("valid_rows", ctypes.c_void_p)]
+                ("act", ctypes.c_int32), ("valid_rows", ctypes.c_void_p),
+                ("given", ctypes.c_void_p * 8), ("given_n", ctypes.c_int32 * 8), ("given_stride", ctypes.c_int64 * 8)]
+
+
+class ColSums:
+    """BatchNorm sums of one MixedOp candidate as its producer left them (include/mrgnas.h: mrg_gated_branch.given): n partial [2][D]
+    float64 sums inside `buf` (a byte workspace from torch's allocator), the first at byte `offset`, `stride` doubles apart."""
+
+    __slots__ = ("buf", "offset", "n", "stride", "rows")
+
+    def __init__(self, buf, offset, n, stride, rows):
+        self.buf, self.offset, self.n, self.stride, self.rows = buf, int(offset), int(n), int(stride), int(rows)
 
 
 ACTS = {"relu": 0, "tanh": 1}
 
 
-def gated_branch(spec, row_dq=None, act=0, valid_rows=None):
+def gated_branch(spec, row_dq=None, act=0, valid_rows=None, given=None):
     """HOST mrg_gated_branch for spec = dict(k, s, c) and / or dict(row_k, s, row_f, row_h, row_uvc, row_ld, b0, b1) merged, or None.
-    row_dq: the [rows] output of mrg_mix_bwd_apply; valid_rows: the launch's int32 [1] device row count, or None.  Returns the
-    by-reference argument (which keeps the structure alive for the call)."""
+    row_dq: the [rows] output of mrg_mix_bwd_apply; valid_rows: the launch's int32 [1] device row count, or None; given (the
+    statistics launch only): per candidate None or the ColSums its producer formed.  Returns the by-reference argument (which keeps
+    the structure alive for the call)."""
     dp = lambda t: None if t is None else t.data_ptr()
+    if given is not None and not any(c is not None for c in given):
+        given = None
     if spec is None:
-        if not act and valid_rows is None:
+        if not act and valid_rows is None and given is None:
             return None
-        # the activation / row count alone
-        return ctypes.byref(GatedBranch(-1, None, None, -1, None, None, None, 0, 0, 0, None, int(act), dp(valid_rows)))
-    g = GatedBranch(int(spec.get("k", -1)), dp(spec["s"]), dp(spec.get("c")), int(spec.get("row_k", -1)), dp(spec.get("row_f")),
-                    dp(spec.get("row_h")), dp(spec.get("row_uvc")), int(spec.get("row_ld", 0)), int(spec.get("b0", 0)), int(spec.get("b1", 0)),
-                    dp(row_dq), int(act), dp(valid_rows))
+        # the activation / row count / producer sums alone
+        g = GatedBranch(-1, None, None, -1, None, None, None, 0, 0, 0, None, int(act), dp(valid_rows))
+    else:
+        g = GatedBranch(int(spec.get("k", -1)), dp(spec["s"]), dp(spec.get("c")), int(spec.get("row_k", -1)), dp(spec.get("row_f")),
+                        dp(spec.get("row_h")), dp(spec.get("row_uvc")), int(spec.get("row_ld", 0)), int(spec.get("b0", 0)), int(spec.get("b1", 0)),
+                        dp(row_dq), int(act), dp(valid_rows))
+    for k, c in enumerate(given or ()):
+        if c is not None:
+            g.given[k], g.given_n[k], g.given_stride[k] = c.buf.data_ptr() + c.offset, c.n, c.stride
     return ctypes.byref(g)
 
 

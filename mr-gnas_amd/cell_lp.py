@@ -54,6 +54,14 @@ def _tensor(y):
     return y.y if isinstance(y, K.Candidate) else y
 
 
+def _record_stream(y, stream):
+    """A candidate produced on a side stream is consumed on `stream`: its tensor and the sums its producer may have left with it."""
+    _tensor(y).record_stream(stream)
+    for c in (getattr(y, "sums", None), getattr(y, "s_sums", None)):
+        if c is not None:
+            c.buf.record_stream(stream)
+
+
 def _plain(h):
     if isinstance(h, K.Fan):
         h = h.take()
@@ -119,6 +127,12 @@ def fused_candidates(ops, bns, weights, g, h, h_in, addend=None, group=None, tot
     paired = {}
     # f_sparse_comp as a row factor: only next to the gate-only f_dense_comp, whose folded gradient store receives its gradient
     row_ok = pair is not None and K.switches.GATED_RECOMPUTE and K.switches.FOLD_ROW_SCALE
+    # `for_epilogue` carries the request for producer statistics: the row GEMMs / the row-factor gate also form their candidates'
+    # BatchNorm column sums -- when the epilogue will take its statistics from this launch's own rows (training mode, rows neither
+    # sharded nor capacity-padded), else today's statistics pass reads the candidates
+    bn0 = bns[0]
+    want = K.ForEpilogue(stats=K.switches.PRODUCER_STATS and group is None and (bn0.training or not bn0.track_running_stats)
+                         and _valid_rows(g, [fh.x]) is None)
     # The candidates are independent: they may run round-robin on a few HIP streams so that the tail of one
     # kernel is filled by another candidate's kernels.  Autograd replays each candidate's backward on the stream its
     # forward ran on.  (Launch-bound step graphs gain nothing from it and pay the event traffic: one stream below 128k rows.)
@@ -131,10 +145,10 @@ def fused_candidates(ops, bns, weights, g, h, h_in, addend=None, group=None, tot
                 ys.append(None)
             elif pair is not None and k in pair:
                 if not paired:
-                    paired[pair[0]], paired[pair[1]] = OPS.dense_pair_forward(ops[pair[0]], ops[pair[1]], g, fh.take(), fi.take(), for_epilogue=True)
+                    paired[pair[0]], paired[pair[1]] = OPS.dense_pair_forward(ops[pair[0]], ops[pair[1]], g, fh.take(), fi.take(), for_epilogue=want)
                 ys.append(paired[k])
             elif (row_ok and type(op) is OPS.f_sparse_op_comp) or type(op) in (OPS.f_dense_op_comp, OPS.f_comp_op):
-                ys.append(_run(op, g, fh.take(), fi.take(), for_epilogue=True))      # a functional.Candidate: consumed by the epilogue only
+                ys.append(_run(op, g, fh.take(), fi.take(), for_epilogue=want))      # a functional.Candidate: consumed by the epilogue only
             else:
                 ys.append(_run(op, g, fh.take(), fi.take()))
         prep = K.mixed_epilogue_prepare(ys, bns, group, total_rows, True, _identity_index(ops), valid_rows=_valid_rows(g, ys))
@@ -156,14 +170,14 @@ def fused_candidates(ops, bns, weights, g, h, h_in, addend=None, group=None, tot
             b.record_stream(side)                  # allocator must not recycle them before that stream is done
         with torch.cuda.stream(side):
             if pair is not None and k in pair:
-                paired[pair[0]], paired[pair[1]] = OPS.dense_pair_forward(ops[pair[0]], ops[pair[1]], g, a, b, for_epilogue=True)
+                paired[pair[0]], paired[pair[1]] = OPS.dense_pair_forward(ops[pair[0]], ops[pair[1]], g, a, b, for_epilogue=want)
                 y = paired[k]
-                _tensor(paired[pair[0] + pair[1] - k]).record_stream(fork.main)
+                _record_stream(paired[pair[0] + pair[1] - k], fork.main)
             elif (row_ok and type(op) is OPS.f_sparse_op_comp) or type(op) in (OPS.f_dense_op_comp, OPS.f_comp_op):
-                y = _run(op, g, a, b, for_epilogue=True)
+                y = _run(op, g, a, b, for_epilogue=want)
             else:
                 y = _run(op, g, a, b)
-        _tensor(y).record_stream(fork.main)        # consumed by the epilogue on the main stream
+        _record_stream(y, fork.main)               # consumed by the epilogue on the main stream
         ys.append(y)
     fork.join()
     prep = K.mixed_epilogue_prepare(ys, bns, group, total_rows, True, _identity_index(ops), valid_rows=_valid_rows(g, ys))

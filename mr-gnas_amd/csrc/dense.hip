@@ -82,9 +82,25 @@ extern "C" int64_t mrg_dense_filter3_workspace_bytes(int D, int K) {
   return 3 * (int64_t)(((int64_t)bsplit_bytes_any(D, K) + 255) / 256 * 256);
 }
 
-extern "C" int mrg_dense_filter_fwd3(int kind, const float* s, const float* s_in, const float* const* W_host, const float* const* bias_host,
-                                     const float* norm, float scale_edge, float scale_self, float* out, float* gate, void* ws,
-                                     int64_t b0, int64_t b1, int64_t M, int D, void* stream) {
+// the grouped launch's row ranges and per-range epilogue constants
+static void dense3_groups(GemmArgs& a, int64_t b0, int64_t b1, int64_t M, const float* const* bias_host, const float* norm, float scale_edge,
+                          float scale_self, size_t each) {
+  const int64_t lo[3] = {0, b0, b1}, hi[3] = {b0, b1, M};
+  a.grp.n = 3;
+  a.grp.bp_stride = (int64_t)each;
+  for (int i = 0; i < 3; ++i) {
+    a.grp.lo[i] = lo[i]; a.grp.hi[i] = hi[i] > lo[i] ? hi[i] : lo[i];
+    a.grp.bias[i] = bias_host ? bias_host[i] : nullptr;
+    a.grp.scale[i] = i < 2 ? scale_edge : scale_self;
+    a.grp.use_rowscale[i] = (i < 2 && norm) ? 1 : 0;
+  }
+}
+
+// colsum != NULL: the launch also leaves the column sums of its output (kind 0: of gate * s * c, stored or not), see
+// mrg_dense_filter3_colsum_blocks
+static int dense_filter_fwd3(int kind, const float* s, const float* s_in, const float* const* W_host, const float* const* bias_host,
+                             const float* norm, float scale_edge, float scale_self, float* out, float* gate, void* ws,
+                             int64_t b0, int64_t b1, int64_t M, int D, void* stream, double* colsum, int64_t colsum_blocks) {
   if (kind != 0 && kind != 1) return MRG_E_ENUM;
   if (D <= 0 || M < 0 || b0 < 0 || b1 < b0 || M < b1) return MRG_E_SHAPE;
   const int K = s_in ? 2 * D : D;
@@ -103,22 +119,44 @@ extern "C" int mrg_dense_filter_fwd3(int kind, const float* s, const float* s_in
   if (kind == 0) { a.S = s; a.ld_s = D; a.aux = gate; }
   if (!x3_eligible(a)) return MRG_E_SHAPE;
   const float* Bs[3]; void* outs[3];
-  a.grp.n = 3;
-  a.grp.bp_stride = (int64_t)each;
+  dense3_groups(a, b0, b1, M, bias_host, norm, scale_edge, scale_self, each);
   for (int i = 0; i < 3; ++i) {
     const bool live = hi[i] > lo[i];
     if (live && !W_host[i]) return MRG_E_NULLPTR;
     Bs[i] = live ? W_host[i] : nullptr;
     outs[i] = (char*)ws + i * each;
-    a.grp.lo[i] = lo[i]; a.grp.hi[i] = live ? hi[i] : lo[i];
-    a.grp.bias[i] = bias_host ? bias_host[i] : nullptr;
-    a.grp.scale[i] = i < 2 ? scale_edge : scale_self;
-    a.grp.use_rowscale[i] = (i < 2 && norm) ? 1 : 0;
   }
   launch_bsplit3_any(kind == 0 ? EPI_GATE : EPI_SCALE, M, Bs, K, 1, D, K, outs, st);
   MRG_LAUNCH_CHECK();
+  if (colsum) {
+    if (gemm_colsum_blocks(kind == 0 ? EPI_GATE : EPI_SCALE, a) != colsum_blocks) return MRG_E_SHAPE;   // the buffer was sized for another kernel
+    gemm_set_colsum(a, colsum);
+    if (kind == 0) return launch_rowgemm_x3_mode_colsum<EPI_GATE_SUMS>(a, outs[0], st);
+    return launch_rowgemm_x3_mode_colsum<EPI_SCALE_SUMS>(a, outs[0], st);
+  }
   if (kind == 0) return launch_rowgemm_x3_mode<EPI_GATE>(a, outs[0], st);
   return launch_rowgemm_x3_mode<EPI_SCALE>(a, outs[0], st);
+}
+
+extern "C" int mrg_dense_filter_fwd3(int kind, const float* s, const float* s_in, const float* const* W_host, const float* const* bias_host,
+                                     const float* norm, float scale_edge, float scale_self, float* out, float* gate, void* ws,
+                                     int64_t b0, int64_t b1, int64_t M, int D, void* stream) {
+  return dense_filter_fwd3(kind, s, s_in, W_host, bias_host, norm, scale_edge, scale_self, out, gate, ws, b0, b1, M, D, stream, nullptr, 0);
+}
+
+extern "C" int64_t mrg_dense_filter3_colsum_blocks(int kind, int64_t b0, int64_t b1, int64_t M, int D, int K) {
+  if ((kind != 0 && kind != 1) || !dense3_shape_ok(D, K) || b0 < 0 || b1 < b0 || M < b1 || M <= 0) return 0;
+  GemmArgs a{};
+  a.K1 = D; a.K2 = K - D; a.N = D; a.rows = M;
+  dense3_groups(a, b0, b1, M, nullptr, nullptr, 1.f, 1.f, 0);
+  return gemm_colsum_blocks(kind == 0 ? EPI_GATE : EPI_SCALE, a);
+}
+
+extern "C" int mrg_dense_filter_fwd3_colsum(int kind, const float* s, const float* s_in, const float* const* W_host, const float* const* bias_host,
+                                            const float* norm, float scale_edge, float scale_self, float* out, float* gate, void* ws,
+                                            int64_t b0, int64_t b1, int64_t M, int D, void* stream, double* colsum, int64_t colsum_blocks) {
+  if (!colsum) return MRG_E_NULLPTR;
+  return dense_filter_fwd3(kind, s, s_in, W_host, bias_host, norm, scale_edge, scale_self, out, gate, ws, b0, b1, M, D, stream, colsum, colsum_blocks);
 }
 
 // dz (and, for the gated kinds, the direct term of the gradient w.r.t. s):

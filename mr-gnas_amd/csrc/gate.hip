@@ -277,6 +277,81 @@ __global__ __launch_bounds__(MRG_BLOCK) void gate_row_fwd_k(const float* __restr
   }
 }
 
+// gate_row_fwd_k that also leaves the MixedOp epilogue's BatchNorm sums of the two candidates that are functions of the rows it
+// streams (producer statistics): f_identity (the value s) and the row factor (the float32 product s * fvec[r], mix_colstats_k's
+// expression), each converted to double as that kernel converts them.  colsum[block][{s, s * f}][{sum, sum of squares}][D]
+// float64: per lane over its rows in ascending order, then over the block's row groups in order -- no atomics, the same bits on
+// every run.  One step per lane and row (KMAX == 1): 8 KB of LDS at most.  The row loop is gate_row_fwd_k's with the s fragment
+// kept past the dot product (a kernel of its own: the plain one stays as it is for callers that want no sums).
+template <int VEC, int LPR, bool HAS_IN>
+__global__ __launch_bounds__(MRG_BLOCK) void gate_row_fwd_colsum_k(const float* __restrict__ s, const float* __restrict__ sin_,
+                                                                   const float* __restrict__ norm, const float* __restrict__ uvc,
+                                                                   float* __restrict__ fvec, float* __restrict__ hvec, SegPlan p, int D, float scale,
+                                                                   double* __restrict__ colsum) {
+  constexpr int RPB = MRG_BLOCK / LPR;
+  constexpr int WIDTH = LPR * VEC;                          // >= D
+  __shared__ double red[RPB * WIDTH];
+  const int b = blockIdx.x;
+  if (b >= p.blk[3]) return;
+  const int seg = (b >= p.blk[1]) + (b >= p.blk[2]);
+  const int jb = b - p.blk[seg], nb = p.blk[seg + 1] - p.blk[seg];
+  const int sl = threadIdx.x % LPR, rw = row_group_of_thread<LPR>();
+  const int dv = D / VEC;
+  const float* u = uvc + (int64_t)seg * MRG_GATE_LD(D);
+  const float cc = u[HAS_IN ? 2 * D : D];
+  const bool mine = sl < dv;
+  const Vec<VEC> uk = mine ? Vec<VEC>::load(u + sl * VEC) : Vec<VEC>::fill(0.f);
+  const Vec<VEC> vk = (HAS_IN && mine) ? Vec<VEC>::load(u + D + sl * VEC) : Vec<VEC>::fill(0.f);
+  const bool use_norm = norm != nullptr && seg < 2;
+  double st[4][VEC];                                        // sum s, sum s^2, sum s f, sum (s f)^2 of this lane's columns
+#pragma unroll
+  for (int q = 0; q < 4; ++q)
+#pragma unroll
+    for (int j = 0; j < VEC; ++j) st[q][j] = 0.0;
+  for (int64_t r = p.lo[seg] + (int64_t)jb * RPB + rw; r < p.hi[seg]; r += (int64_t)nb * RPB) {
+    float dot = 0.f;
+    Vec<VEC> sk = Vec<VEC>::fill(0.f);
+    if (mine) {
+      sk = Vec<VEC>::load(s + r * D + sl * VEC);
+#pragma unroll
+      for (int j = 0; j < VEC; ++j) dot += sk[j] * uk[j];
+      if (HAS_IN) {
+        Vec<VEC> x = Vec<VEC>::load(sin_ + r * D + sl * VEC);
+#pragma unroll
+        for (int j = 0; j < VEC; ++j) dot += x[j] * vk[j];
+      }
+    }
+    const float z = group_sum<LPR>(dot) + cc;
+    const float gt = sigmoidf_fast(z);
+    const float nv = use_norm ? norm[r] : 1.0f;
+    const float rf = gt * scale * nv;
+    if (sl == 0) {
+      fvec[r] = rf;
+      const float t = scale * nv;
+      hvec[r] = t * gt * (1.0f - gt);
+    }
+#pragma unroll
+    for (int j = 0; j < VEC; ++j) {                         // (a lane beyond the row's columns adds zeros)
+      double d = (double)sk[j]; st[0][j] += d; st[1][j] += d * d;
+      d = (double)(sk[j] * rf); st[2][j] += d; st[3][j] += d * d;
+    }
+  }
+  double* __restrict__ dst = colsum + (int64_t)b * 4 * D;
+#pragma unroll
+  for (int q = 0; q < 4; ++q) {                             // one statistic at a time: 8 KB of LDS, so that registers bound the occupancy
+#pragma unroll
+    for (int j = 0; j < VEC; ++j) red[rw * WIDTH + sl * VEC + j] = st[q][j];
+    __syncthreads();
+    for (int c = threadIdx.x; c < D; c += MRG_BLOCK) {
+      double acc = 0.0;
+#pragma unroll
+      for (int g = 0; g < RPB; ++g) acc += red[g * WIDTH + c];
+      dst[q * D + c] = acc;
+    }
+    __syncthreads();
+  }
+}
+
 // q[r] (the gradient w.r.t. fvec[r], from the epilogue's backward), dz_r = q_r * hvec[r] -> gs_in = dz_r * v (HAS_IN), per-block
 // partials of du = sum_r dz_r s_r, dv = sum_r dz_r s_in_r, dc = sum_r dz_r  (the block reduction and its order are gate_bwd_k's).
 // The gradient w.r.t. s (gy * f_r + dz_r * u) was added to the epilogue's gs_out.
@@ -555,27 +630,60 @@ extern "C" int mrg_gate_bwd(const float* gout, const float* s, const float* s_in
   return MRG_OK;
 }
 
-// f_sparse_op_comp as a row factor (see gate_row_fwd_k): fvec / hvec [M].
-extern "C" int mrg_gate_row_fwd(const float* s, const float* s_in, const float* norm, const float* uvc, float* fvec, float* hvec,
-                                int64_t b0, int64_t b1, int64_t M, int D, float scale, void* stream) {
+// f_sparse_op_comp as a row factor (see gate_row_fwd_k): fvec / hvec [M].  colsum != NULL: the column sums of s and of s * fvec[r]
+// as well (gate_row_fwd_colsum_k; mrg_gate_row_colsum_blocks partials).
+static int gate_row_plan(int64_t b0, int64_t b1, int64_t M, int lpr, SegPlan* p) {
+  int grid = grid_for(M, (MRG_BLOCK / lpr) * 4);
+  if (grid < 3) grid = 3;
+  *p = make_plan(b0, b1, M, grid);
+  return p->blk[3];
+}
+
+static int gate_row_fwd(const float* s, const float* s_in, const float* norm, const float* uvc, float* fvec, float* hvec,
+                        int64_t b0, int64_t b1, int64_t M, int D, float scale, void* stream, double* colsum, int64_t colsum_blocks) {
   if (D <= 0 || M < 0 || b0 < 0 || b1 < b0 || M < b1) return MRG_E_SHAPE;
   if (M == 0) return MRG_OK;
   if (!s || !uvc || !fvec || !hvec) return MRG_E_NULLPTR;
   RowGeom g = row_geom(D, aligned16(s) && aligned16(s_in) && aligned16(uvc));
   if (!g.ok) return MRG_E_SHAPE;
+  if (colsum && g.kmax != 1) return MRG_E_SHAPE;             // (the query answered 0)
   hipStream_t st = (hipStream_t)stream;
 #define CALL(V, L, K)                                                                                                   \
   do {                                                                                                                  \
-    int grid = grid_for(M, (MRG_BLOCK / L) * 4);                                                                        \
-    if (grid < 3) grid = 3;                                                                                             \
-    SegPlan p = make_plan(b0, b1, M, grid);                                                                             \
-    if (s_in) hipLaunchKernelGGL((gate_row_fwd_k<V, L, K, true>), dim3(p.blk[3]), dim3(MRG_BLOCK), 0, st, s, s_in, norm, uvc, fvec, hvec, p, D, scale); \
+    SegPlan p;                                                                                                          \
+    gate_row_plan(b0, b1, M, L, &p);                                                                                    \
+    if (colsum && p.blk[3] != colsum_blocks) return MRG_E_SHAPE;   /* the buffer was sized for another lane geometry */  \
+    if (colsum) {                                                                                                       \
+      if (s_in) hipLaunchKernelGGL((gate_row_fwd_colsum_k<V, L, true>), dim3(p.blk[3]), dim3(MRG_BLOCK), 0, st, s, s_in, norm, uvc, fvec, hvec, p, D, scale, colsum); \
+      else hipLaunchKernelGGL((gate_row_fwd_colsum_k<V, L, false>), dim3(p.blk[3]), dim3(MRG_BLOCK), 0, st, s, s_in, norm, uvc, fvec, hvec, p, D, scale, colsum); \
+    } else if (s_in) hipLaunchKernelGGL((gate_row_fwd_k<V, L, K, true>), dim3(p.blk[3]), dim3(MRG_BLOCK), 0, st, s, s_in, norm, uvc, fvec, hvec, p, D, scale); \
     else hipLaunchKernelGGL((gate_row_fwd_k<V, L, K, false>), dim3(p.blk[3]), dim3(MRG_BLOCK), 0, st, s, s_in, norm, uvc, fvec, hvec, p, D, scale); \
   } while (0)
   MRG_DISPATCH_GEOM(g, CALL);
 #undef CALL
   MRG_LAUNCH_CHECK();
   return MRG_OK;
+}
+
+extern "C" int mrg_gate_row_fwd(const float* s, const float* s_in, const float* norm, const float* uvc, float* fvec, float* hvec,
+                                int64_t b0, int64_t b1, int64_t M, int D, float scale, void* stream) {
+  return gate_row_fwd(s, s_in, norm, uvc, fvec, hvec, b0, b1, M, D, scale, stream, nullptr, 0);
+}
+
+// blocks (= [2][2][D] float64 partials) of mrg_gate_row_fwd_colsum, 0: not available for this shape.  The lane geometry, and with it
+// the grid, depends on whether the rows can be read 16 bytes at a time: `vec4` = D % 4 == 0 and every pointer 16-byte aligned.
+extern "C" int64_t mrg_gate_row_colsum_blocks(int64_t b0, int64_t b1, int64_t M, int D, int vec4) {
+  if (D <= 0 || M <= 0 || b0 < 0 || b1 < b0 || M < b1) return 0;
+  RowGeom g = row_geom(D, vec4 != 0);
+  if (!g.ok || g.kmax != 1 || (vec4 && g.vec != 4)) return 0;
+  SegPlan p;
+  return gate_row_plan(b0, b1, M, g.lpr, &p);
+}
+
+extern "C" int mrg_gate_row_fwd_colsum(const float* s, const float* s_in, const float* norm, const float* uvc, float* fvec, float* hvec,
+                                       int64_t b0, int64_t b1, int64_t M, int D, float scale, void* stream, double* colsum, int64_t colsum_blocks) {
+  if (!colsum) return MRG_E_NULLPTR;
+  return gate_row_fwd(s, s_in, norm, uvc, fvec, hvec, b0, b1, M, D, scale, stream, colsum, colsum_blocks);
 }
 
 // q [M] (written by mrg_mix_bwd_apply, mrg_gated_branch.row_dq), hvec [M] (mrg_gate_row_fwd) -> gs_in [M, D] (s_in != NULL) and

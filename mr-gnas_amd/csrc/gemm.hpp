@@ -32,6 +32,11 @@ typedef const __attribute__((address_space(1))) void* gbl_ptr_t;       // LDS-DM
 constexpr int GBM_MAX = 256;      // rows per workgroup = 128 * MT (MT row tiles of 32 per wave)
 
 enum { EPI_BIAS_ACT = 0, EPI_GATE = 1, EPI_SCALE = 2, EPI_ACCUM = 3, EPI_SEGMAX = 4, EPI_SEGSUM = 5 };
+// EPI_GATE / EPI_SCALE that also leave the column sums of the values they form (gemm_colsum(GemmArgs); gemm_epilogue's SUMS): kernel
+// instances of their own, so that the plain ones stay what they are.  Split core, rowgemm_x3s_k<7, ...> and rowgemm_x3q_k only.
+enum { EPI_GATE_SUMS = 6, EPI_SCALE_SUMS = 7 };
+constexpr bool epi_sums(int epi) { return epi == EPI_GATE_SUMS || epi == EPI_SCALE_SUMS; }
+constexpr int epi_base(int epi) { return epi == EPI_GATE_SUMS ? EPI_GATE : (epi == EPI_SCALE_SUMS ? EPI_SCALE : epi); }
 
 // Up to three row ranges of ONE launch of the split-core row GEMM that share every tensor but differ in the weight matrix
 // (the in / out / self direction segments of a dense filter: one launch instead of three).  Workgroup blocks
@@ -73,12 +78,19 @@ struct GemmArgs {
   const int32_t* row_seg;
   unsigned long long* seg_out;
   // EPI_SEGSUM (no C): run sums of ReLU(acc + bias) at seg_part[head position * N + col], ReLU bit mask at relu_bits, see gemm_epilogue_segsum
+  // (EPI_GATE_SUMS / EPI_SCALE_SUMS have no run sums: their colsum pointer travels in this slot, gemm_colsum below)
   float* seg_part;
   unsigned* relu_bits; int bits_ld;
   // split core, one-wave kernel: stores in row order through a wave-private LDS strip (gemm_epilogue_lds); set by the launcher
   int epi_lds; int wave_lds_floats;
   GemmGroups grp;                     // split core, one-wave kernel only
 };
+
+// EPI_GATE_SUMS / EPI_SCALE_SUMS: colsum[workgroup along x][2][N] float64, the workgroup's column sums and column sums of squares of
+// its output values.  The pointer shares the slot of seg_part (EPI_SEGSUM only), so the argument block -- and with it the code of
+// every other kernel instance -- stays what it was.
+inline void gemm_set_colsum(GemmArgs& a, double* colsum) { a.seg_part = reinterpret_cast<float*>(colsum); }
+__host__ __device__ __forceinline__ double* gemm_colsum(const GemmArgs& a) { return reinterpret_cast<double*>(a.seg_part); }
 
 // The 4 floats at column k of the concatenated row [r1 (K1 floats) | r2 (K2 floats)] (DUAL) or of r1 alone (K floats), clamped
 // into the row: beyond the end a chunk re-reads the row's last 4 floats -- any finite values, the weight's rows there are zero.
@@ -266,10 +278,22 @@ __device__ __forceinline__ float4 gemm_mask_a(float4 v, const GemmArgs& a, int64
 // Every load (bias, row scale, gate multiplicand, accumulate input) is issued unconditionally from a
 // clamped address BEFORE the stores, and a full tile stores without per-element branches: a store inside
 // a data-dependent branch makes hipcc wait vmcnt(0) per store, which serialises the 16*NT stores of a lane.
-template <int NT, int EPI>
+// SUMS (EPI_GATE / EPI_SCALE, producer statistics of the MixedOp epilogue): the lane also adds the values v it forms -- of valid
+// rows, in register order, each converted to double as mix_colstats_k converts them -- into one sum and one sum of squares per
+// column tile and leaves them in LDS at sums[(lh * 2 + {0, 1}) * NT * 32 + n * 32 + li] (this wave's [2][2][NT * 32] doubles;
+// columns beyond N and a strip beyond the rows leave zeros).  The caller adds the waves' slots in a fixed order
+// (gemm_colsum_flush).  The gate-only form then reads its multiplicand S, which it otherwise does not need.
+template <int NT, int EPI, bool SUMS = false>
 __device__ __forceinline__ void gemm_epilogue(const GemmArgs& a, f32x16 (&acc)[NT], int64_t rowbase, int col0, int li, int lh,
-                                              bool full) {
-  if (rowbase >= a.rows) return;                           // wave-uniform: the whole 32-row strip is out of range
+                                              bool full, double* __restrict__ sums = nullptr) {
+  static_assert(!SUMS || EPI == EPI_GATE || EPI == EPI_SCALE, "column sums: gate and scale epilogues only");
+  if (rowbase >= a.rows) {                                 // wave-uniform: the whole 32-row strip is out of range
+    if constexpr (SUMS) {
+#pragma unroll
+      for (int n = 0; n < NT; ++n) { sums[(lh * 2 + 0) * NT * 32 + n * 32 + li] = 0.0; sums[(lh * 2 + 1) * NT * 32 + n * 32 + li] = 0.0; }
+    }
+    return;
+  }
   // One pointer per accumulator row (clamped to the last valid row) and per array, set up once; a column tile is then
   // a constant 128-byte offset from it, i.e. an immediate of the load / store.  (Per-tile 64-bit address arithmetic
   // made hipcc spill hundreds of addresses of the 224-accumulator kernels to scratch memory.)
@@ -305,7 +329,7 @@ __device__ __forceinline__ void gemm_epilogue(const GemmArgs& a, f32x16 (&acc)[N
     float in[16], v[16], g[16];
 #pragma unroll
     for (int r = 0; r < 16; ++r) in[r] = 0.f;
-    if ((EPI == EPI_GATE && cstore) || EPI == EPI_ACCUM) {     // (gate only: the multiplicand is not read at all)
+    if ((EPI == EPI_GATE && (cstore || SUMS)) || EPI == EPI_ACCUM) {     // (gate only, no sums: the multiplicand is not read at all)
 #pragma unroll
       for (int r = 0; r < 16; ++r) in[r] = srow[r][off];
     }
@@ -322,6 +346,16 @@ __device__ __forceinline__ void gemm_epilogue(const GemmArgs& a, f32x16 (&acc)[N
       } else {
         v[r] = x + in[r];
       }
+    }
+    if constexpr (SUMS) {
+      double s1 = 0.0, s2 = 0.0;
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        const double d = (full || rok[r]) ? (double)v[r] : 0.0;
+        s1 += d; s2 += d * d;
+      }
+      sums[(lh * 2 + 0) * NT * 32 + n * 32 + li] = cok ? s1 : 0.0;
+      sums[(lh * 2 + 1) * NT * 32 + n * 32 + li] = cok ? s2 : 0.0;
     }
     if (full) {
       if (cok) {
@@ -343,6 +377,23 @@ __device__ __forceinline__ void gemm_epilogue(const GemmArgs& a, f32x16 (&acc)[N
         }
       }
     }
+  }
+}
+
+// The workgroup's column sums from its waves' LDS slots (gemm_epilogue<..., SUMS = true>: NSLOT = waves x two lane halves slots of
+// [2][W] doubles each, wave w's at lds + w * 4 * W), added in slot order -- no atomics, the same bits on every run -- into the
+// workgroup's own partial colsum[blockIdx.x][2][N] (float64).  Every thread of the workgroup calls it, behind a barrier that
+// follows the epilogue.
+template <int W, int NSLOT>
+__device__ __forceinline__ void gemm_colsum_flush(const double* __restrict__ lds, double* __restrict__ colsum, int N, int col0) {
+  double* __restrict__ dst = colsum + (int64_t)blockIdx.x * 2 * N;
+  for (int t = threadIdx.x; t < 2 * W; t += blockDim.x) {
+    const int which = t / W, c = t - which * W;
+    if (col0 + c >= N) continue;
+    double acc = 0.0;
+#pragma unroll
+    for (int q = 0; q < NSLOT; ++q) acc += lds[(q * 2 + which) * W + c];
+    dst[which * N + col0 + c] = acc;
   }
 }
 

@@ -96,6 +96,33 @@ inline int launch_rowgemm_x3_mode(GemmArgs a, const void* Bp, hipStream_t st) {
   return launch_rowgemm_x3<EPI>(a, Bp, st);
 }
 
+// ---- column sums of the output as a by-product (EPI_GATE / EPI_SCALE: the MixedOp epilogue's BatchNorm statistics) ---------------
+// The workgroups (= [2][N] float64 partials) a launch of `a` would leave, or 0 when the kernel it would take has no such form: the
+// exact-f32 core and mode 2, the row-order / transposed epilogues, few-row launches on rowgemm_x3_k, and outputs that are not
+// one seven-tile column block (129..224 columns, N % 4 == 0).  The caller then keeps the statistics pass.
+inline int64_t gemm_colsum_blocks(int epi, GemmArgs a) {
+  const int K = a.K1 + a.K2;
+  if ((epi != EPI_GATE && epi != EPI_SCALE) || gemm_mode() != 0 || gemm_switches().epilogue != 0) return 0;
+  if (a.N % 4 != 0 || a.N <= 128 || a.N > 224 || a.rows <= 0 || !x3_eligible(a)) return 0;
+  int gbm = 128;
+  if (x3q_shape(epi, a.N, K)) {
+    if (!x3q_eligible(a)) return 0;
+    gbm = X3Q_ROWS;
+  } else if (x3n_shape(epi, a.rows, a.N, K)) {
+    return 0;
+  }
+  return a.grp.n > 0 ? gemm_group_tiles(a.grp, gbm) : (a.rows + gbm - 1) / gbm;
+}
+
+// the launch itself (the weight split prepared by launch_bsplit_any / launch_bsplit3_any for the plain epilogue, as for
+// launch_rowgemm_x3_mode); EPI = EPI_GATE_SUMS / EPI_SCALE_SUMS, gemm_set_colsum(a, .): gemm_colsum_blocks(epi_base(EPI), a) partials
+template <int EPI>
+inline int launch_rowgemm_x3_mode_colsum(GemmArgs a, const void* Bp, hipStream_t st) {
+  if (!gemm_colsum(a) || gemm_colsum_blocks(epi_base(EPI), a) <= 0) return MRG_E_SHAPE;
+  if (x3q_shape(epi_base(EPI), a.N, a.K1 + a.K2)) return launch_rowgemm_x3q<EPI>(a, Bp, st);
+  return launch_rowgemm_x3s_colsum<EPI>(a, Bp, st);
+}
+
 inline size_t gemm_workspace_bytes(int K, int N) {
   const size_t split = bsplit_bytes_any(N, K);
   const size_t transp = (size_t)K * N * sizeof(float);

@@ -44,9 +44,19 @@ inline size_t x3q_bsplit_bytes(int K) { return (size_t)x3q_slabs(K) * 2 * X3Q_CH
 // i.e. with li = lane & 31, lh = lane >> 5 a lane holds column 32 j + li of rows i + 8 lh, i = r (a') or 4 + r (b'): one store
 // instruction writes two 128-byte row pieces.  Arithmetic per element is gemm_epilogue's (bias add, activation / gate / scale /
 // accumulate in the same order).
-template <int EPI>
-__device__ __forceinline__ void gemm_epilogue_q(const GemmArgs& a, f32x4v (&acc)[X3Q_NT], int64_t rowbase, int li, int lh, bool full) {
-  if (rowbase >= a.rows) return;                           // wave-uniform: the whole 16-row strip is out of range
+// SUMS: as gemm_epilogue's -- the lane's sums over its eight rows of pair j go to sums[(lh * 2 + {0, 1}) * X3Q_HT * 32 + j * 32 + li].
+template <int EPI, bool SUMS = false>
+__device__ __forceinline__ void gemm_epilogue_q(const GemmArgs& a, f32x4v (&acc)[X3Q_NT], int64_t rowbase, int li, int lh, bool full,
+                                                double* __restrict__ sums = nullptr) {
+  static_assert(!SUMS || EPI == EPI_GATE || EPI == EPI_SCALE, "column sums: gate and scale epilogues only");
+  constexpr int W = X3Q_HT * 32;
+  if (rowbase >= a.rows) {                                 // wave-uniform: the whole 16-row strip is out of range
+    if constexpr (SUMS) {
+#pragma unroll
+      for (int j = 0; j < X3Q_HT; ++j) { sums[(lh * 2 + 0) * W + j * 32 + li] = 0.0; sums[(lh * 2 + 1) * W + j * 32 + li] = 0.0; }
+    }
+    return;
+  }
   const int last = (int)((a.rows - 1 - rowbase) < 15 ? (a.rows - 1 - rowbase) : 15);
   const int colw = li < a.N ? li : a.N - 1;
   float* crow[8];
@@ -91,7 +101,7 @@ __device__ __forceinline__ void gemm_epilogue_q(const GemmArgs& a, f32x4v (&acc)
     float in[8], v[8], g[8];
 #pragma unroll
     for (int i = 0; i < 8; ++i) in[i] = 0.f;
-    if ((EPI == EPI_GATE && cstore) || EPI == EPI_ACCUM) {
+    if ((EPI == EPI_GATE && (cstore || SUMS)) || EPI == EPI_ACCUM) {
 #pragma unroll
       for (int i = 0; i < 8; ++i) in[i] = srow[i][off];
     }
@@ -108,6 +118,16 @@ __device__ __forceinline__ void gemm_epilogue_q(const GemmArgs& a, f32x4v (&acc)
       } else {
         v[i] = x + in[i];
       }
+    }
+    if constexpr (SUMS) {
+      double s1 = 0.0, s2 = 0.0;
+#pragma unroll
+      for (int i = 0; i < 8; ++i) {
+        const double d = (full || rok[i]) ? (double)v[i] : 0.0;
+        s1 += d; s2 += d * d;
+      }
+      sums[(lh * 2 + 0) * W + j * 32 + li] = cok ? s1 : 0.0;
+      sums[(lh * 2 + 1) * W + j * 32 + li] = cok ? s2 : 0.0;
     }
     if (full) {
       if (cok) {
@@ -238,7 +258,17 @@ __global__ __launch_bounds__(256, X3Q_WPS) void rowgemm_x3q_k(GemmArgs a, const 
   asm volatile("" :: "v"(xr[0][0]), "v"(xr[0][1]), "v"(xr[1][0]), "v"(xr[1][1]));
 
   const int li = lane & 31, lh = lane >> 5;
-  gemm_epilogue_q<EPI>(a, acc, roww, li, lh, row0 + X3Q_ROWS <= a.rows);
+  if constexpr (epi_sums(EPI)) {
+    // the weight half-slabs are done with: once every wave has read its last fragments, LDS holds the waves' sums
+    // ([4 waves][2 lane halves][2][224] doubles: 28 KB of the 42)
+    double* sums = reinterpret_cast<double*>(smem_q);
+    __syncthreads();
+    gemm_epilogue_q<epi_base(EPI), true>(a, acc, roww, li, lh, row0 + X3Q_ROWS <= a.rows, sums + wave * (4 * X3Q_HT * 32));
+    __syncthreads();
+    gemm_colsum_flush<X3Q_HT * 32, 8>(sums, gemm_colsum(a), a.N, 0);
+  } else {
+    gemm_epilogue_q<EPI>(a, acc, roww, li, lh, row0 + X3Q_ROWS <= a.rows);
+  }
 }
 
 inline bool x3q_eligible(const GemmArgs& a) { return x3_eligible(a) && a.rows > 0 && a.N <= X3Q_NT * 16 && !a.row_seg; }

@@ -155,7 +155,16 @@ __global__ __launch_bounds__(256, 2) void rowgemm_x3s_k(GemmArgs a, const char* 
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");            // the tail's unused A fills: their registers must stay until they land
   asm volatile("" :: "v"(xr[0][0]), "v"(xr[0][1]), "v"(xr[1][0]), "v"(xr[1][1]), "v"(xr[2][0]), "v"(xr[2][1]));
 
-  if constexpr (EPI == EPI_SEGMAX) gemm_epilogue_segmax<NT>(a, acc, roww, col0, li, lh);
+  if constexpr (epi_sums(EPI)) {
+    // the weight slabs are done with: once every wave has read its last fragments, LDS holds the waves' sums
+    // ([4 waves][2 lane halves][2][NT * 32] doubles: 28 KB of the 63 for seven tiles)
+    double* sums = reinterpret_cast<double*>(smem_b);
+    __syncthreads();
+    gemm_epilogue<NT, epi_base(EPI), true>(a, acc, roww, col0, li, lh, row0 + GBM <= a.rows, sums + wave * (4 * NT * 32));
+    __syncthreads();
+    gemm_colsum_flush<NT * 32, 8>(sums, gemm_colsum(a), a.N, col0);
+  }
+  else if constexpr (EPI == EPI_SEGMAX) gemm_epilogue_segmax<NT>(a, acc, roww, col0, li, lh);
   else if constexpr (EPI == EPI_SEGSUM) gemm_epilogue_segsum<NT>(a, acc, roww, col0, li, lh);
   else if constexpr (TR) gemm_epilogue_tr<NT, EPI>(a, acc, roww, col0, li, lh);
   else gemm_epilogue<NT, EPI>(a, acc, roww, col0, li, lh, row0 + GBM <= a.rows);
@@ -192,6 +201,22 @@ inline int launch_rowgemm_x3s(GemmArgs a, const void* Bp, hipStream_t st) {
 #undef MRG_GOS
 #undef MRG_GOS2
 #undef MRG_GOS3
+}
+
+// EPI_GATE_SUMS / EPI_SCALE_SUMS: the seven-tile column block (129..224 columns), accumulator-order epilogue; gemm_set_colsum(a, ...) done
+template <int EPI>
+inline int launch_rowgemm_x3s_colsum(GemmArgs a, const void* Bp, hipStream_t st) {
+  static_assert(epi_sums(EPI), "the column-sum epilogues");
+  if (a.rows <= 0) return MRG_OK;
+  if (!a.A2 || a.K2 == 0) { a.A2 = a.A1; a.K2 = 0; }
+  const int nt = gemm_pick_nt(a.N);
+  if (nt != 7 || a.N > 7 * 32 || !gemm_colsum(a)) return MRG_E_SHAPE;
+  const int ntile = x3_tiles(a.N, nt);
+  if (a.grp.n > 0 && gemm_group_tiles(a.grp, 128) == 0) return MRG_OK;
+  dim3 grid((unsigned)(a.grp.n > 0 ? a.grp.tile0[3] : (a.rows + 127) / 128), 1);
+  const size_t lds = (size_t)3 * nt * 3 * 1024;
+  if (a.K2 > 0) return launch_kernel(rowgemm_x3s_k<7, EPI, true, false>, grid, dim3(256), lds, st, a, Bp, ntile);
+  return launch_kernel(rowgemm_x3s_k<7, EPI, false, false>, grid, dim3(256), lds, st, a, Bp, ntile);
 }
 
 }  // namespace mrg

@@ -10,6 +10,7 @@
 #include "common.hpp"
 
 #define MRG_MIX_MAXK 8
+static_assert(MRG_MIX_MAXK == MRG_MIX_MAX_CANDIDATES, "mrg_gated_branch.given is sized by the header's constant");
 
 namespace mrg {
 
@@ -198,6 +199,37 @@ __global__ __launch_bounds__(MRG_BLOCK) void mix_colstats_k(PtrPack ys, int K, i
       }
     }
     colstats_flush<VEC, LPR, KMAX>(s1, s2, red, ws + ((int64_t)blockIdx.x * K + k) * 2 * D, D, sl, rw);
+  }
+}
+
+// ---- statistics that a candidate's PRODUCER formed (mrg_gated_branch.given): no sweep over the candidate ------------------------
+// The producer (the row GEMM's gate / scale epilogue, gate_row_fwd_colsum_k) left n partial [2][D] float64 sums, `stride` doubles
+// apart.  Block (b, k) of a G x K grid adds candidate k's partials [n b / G, n (b + 1) / G) in order (four interleaved
+// accumulators, fixed association) into ws[b][k][2][D] -- the layout mix_colstats_k's blocks write, so mix_reduce_finalize_fwd_k
+// finishes both alike.  zero_absent: no statistics kernel ran; the slots of candidates without given sums (all-zero
+// candidates) are zeroed here.
+struct GivenPack { const double* p[MRG_MIX_MAXK]; int n[MRG_MIX_MAXK]; int64_t stride[MRG_MIX_MAXK]; };
+
+__global__ __launch_bounds__(MRG_BLOCK) void mix_given_reduce_k(GivenPack gv, int K, int D, double* __restrict__ ws, int zero_absent) {
+  const int b = blockIdx.x, k = blockIdx.y, G = gridDim.x;
+  double* __restrict__ dst = ws + ((int64_t)b * K + k) * 2 * D;
+  const double* __restrict__ src = gv.p[k];
+  if (src == nullptr) {
+    if (zero_absent)
+      for (int t = threadIdx.x; t < 2 * D; t += MRG_BLOCK) dst[t] = 0.0;
+    return;
+  }
+  const int64_t n = gv.n[k], stride = gv.stride[k];
+  const int64_t lo = n * b / G, hi = n * (b + 1) / G;
+  for (int t = threadIdx.x; t < 2 * D; t += MRG_BLOCK) {
+    double a0 = 0.0, a1 = 0.0, a2 = 0.0, a3 = 0.0;
+    int64_t i = lo;
+    for (; i + 3 < hi; i += 4) {
+      const double v0 = src[i * stride + t], v1 = src[(i + 1) * stride + t], v2 = src[(i + 2) * stride + t], v3 = src[(i + 3) * stride + t];
+      a0 += v0; a1 += v1; a2 += v2; a3 += v3;
+    }
+    for (; i < hi; ++i) a0 += src[i * stride + t];
+    dst[t] = (a0 + a1) + (a2 + a3);
   }
 }
 
@@ -1023,8 +1055,42 @@ extern "C" int mrg_mix_stats_coef(const float* const* y_host, const float* const
   if (!coef || !gamma_host || !beta_host) return MRG_E_NULLPTR;
   hipStream_t st = (hipStream_t)stream;
   int grid = 1;
-  const int rc = mix_colstats_blocks(y_host, K, rows, D, ws, st, &grid, gated);
-  if (rc != MRG_OK) return rc;
+  bool any_given = false;
+  for (int k = 0; gated && k < K; ++k) any_given = any_given || gated->given[k] != nullptr;
+  if (!any_given) {
+    const int rc = mix_colstats_blocks(y_host, K, rows, D, ws, st, &grid, gated);
+    if (rc != MRG_OK) return rc;
+  } else {
+    // Candidates whose producers formed their sums are hidden from the statistics kernel (an absent candidate costs it nothing);
+    // when none is left to read, it does not run.
+    if (valid_rows) return MRG_E_SHAPE;                      // a producer counts every row
+    if (!pack_ok((const void* const*)y_host, K) || rows < 0) return MRG_E_SHAPE;
+    if (!ws) return MRG_E_WORKSPACE;
+    const float* y2[MRG_MIX_MAXK];
+    mrg_gated_branch g2 = *gated;
+    GivenPack gv{};
+    bool any_read = false;
+    int64_t n_max = 1;
+    for (int k = 0; k < K; ++k) {
+      y2[k] = y_host[k];
+      if (!gated->given[k]) { any_read = any_read || y_host[k] != nullptr; continue; }
+      if (gated->given_n[k] < 1 || gated->given_stride[k] < 2 * (int64_t)D) return MRG_E_SHAPE;
+      gv.p[k] = gated->given[k]; gv.n[k] = gated->given_n[k]; gv.stride[k] = gated->given_stride[k];
+      if (gv.n[k] > n_max) n_max = gv.n[k];
+      y2[k] = nullptr;
+      if (g2.k == k) g2.k = -1;
+      if (g2.row_k == k) g2.row_k = -1;
+    }
+    if (any_read) {
+      const int rc = mix_colstats_blocks(y2, K, rows, D, ws, st, &grid, &g2);
+      if (rc != MRG_OK) return rc;
+    } else {
+      const int64_t g = (n_max + 15) / 16;
+      grid = (int)(g < 256 ? g : 256);
+    }
+    hipLaunchKernelGGL(mix_given_reduce_k, dim3(grid, K), dim3(MRG_BLOCK), 0, st, gv, K, D, (double*)ws, any_read ? 0 : 1);
+    MRG_LAUNCH_CHECK();
+  }
   PtrPack ga{}, be{};
   MutPack rm{}, rv{};
   for (int k = 0; k < K; ++k) {
@@ -1044,6 +1110,8 @@ extern "C" int mrg_mix_colstats(const float* const* y_host, int K, int64_t rows,
                                 const mrg_gated_branch* gated, void* stream) {
   if (!sums) return MRG_E_NULLPTR;
   if (gated && gated->valid_rows) return MRG_E_SHAPE;
+  for (int k = 0; gated && k < MRG_MIX_MAXK; ++k)
+    if (gated->given[k]) return MRG_E_SHAPE;                 // producer sums are this launch's rows, finished by mrg_mix_stats_coef only
   hipStream_t st = (hipStream_t)stream;
   int grid = 1;
   const int rc = mix_colstats_blocks(y_host, K, rows, D, ws, st, &grid, gated);

@@ -29,7 +29,7 @@ from ._base import (  # noqa: F401
     COMPOSE, REDUCE, ACT, gate_ld, same_rows, _same_memory, _cnt, _ws, _WS_BYTES, _ws_bytes, _SIDE_STREAMS, Fork,
 )
 from .candidates import (  # noqa: F401
-    Link, Candidate,
+    Link, Candidate, ForEpilogue, wants_stats,
 )
 from .gcs import (  # noqa: F401
     GCS, fused_gcs, span_gcs, ComposePlan, _ComposeAggregate, compose_aggregate,

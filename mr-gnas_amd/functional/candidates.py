@@ -44,6 +44,25 @@ class Link:
         return True
 
 
+class ForEpilogue:
+    """What a fused caller passes as an operator's `for_epilogue` argument instead of True (it is true): the request travels with the
+    call.  stats: the producer should also form the candidate's BatchNorm column sums while it has the values in registers
+    (Candidate.sums) -- asked for only when the epilogue will take its statistics from this launch's own rows (training mode, rows
+    neither sharded nor capacity-padded)."""
+
+    __slots__ = ("stats",)
+
+    def __init__(self, stats=False):
+        self.stats = bool(stats)
+
+    def __bool__(self):
+        return True
+
+
+def wants_stats(for_epilogue):
+    return bool(getattr(for_epilogue, "stats", False))
+
+
 class Candidate:
     """What an operator's `for_epilogue=True` path hands to mixed_epilogue_prepare instead of a bare [rows, D] tensor.
 
@@ -52,12 +71,15 @@ class Candidate:
       kind "gate"       y = f_dense_comp's GATE; the candidate gate * s * c_r is recomputed wherever it is read (never stored)
       kind "rowfactor"  y = f_sparse_comp's gate as ONE factor per row, [rows]; the candidate is s * y[:, None]
 
-    `y` is the tensor that takes part in autograd; `link` the producer's mailbox; `slot` the producer's output index."""
+    `y` is the tensor that takes part in autograd; `link` the producer's mailbox; `slot` the producer's output index.
+    `sums`: None, or the _lib.ColSums of the candidate's VALUE that its producer formed (ForEpilogue.stats); `s_sums` (row factor):
+    those of the rows s themselves -- the value of an f_identity candidate over the same rows."""
 
-    __slots__ = ("kind", "y", "s", "c", "rowscale", "link", "slot", "b0", "b1")
+    __slots__ = ("kind", "y", "s", "c", "rowscale", "link", "slot", "b0", "b1", "sums", "s_sums")
 
-    def __init__(self, kind, y, link=None, slot=0, s=None, c=None, rowscale=None, b0=0, b1=0):
+    def __init__(self, kind, y, link=None, slot=0, s=None, c=None, rowscale=None, b0=0, b1=0, sums=None, s_sums=None):
         self.kind, self.y, self.link, self.slot, self.s, self.c, self.rowscale, self.b0, self.b1 = kind, y, link, slot, s, c, rowscale, b0, b1
+        self.sums, self.s_sums = sums, s_sums
 
     def materialize(self):
         """The candidate as a plain [rows, D] tensor (for consumers other than the fused epilogue)."""

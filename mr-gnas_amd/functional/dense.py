@@ -10,7 +10,7 @@ from .. import _lib
 from .._lib import ptr_array, call, f32c, ptr, require_hip, stream_of
 from . import switches as SW
 from ._base import Fork, _ws, _ws_bytes, same_rows
-from .candidates import Candidate, Link
+from .candidates import Candidate, Link, wants_stats
 
 
 class _DenseFilter(torch.autograd.Function):
@@ -200,7 +200,7 @@ class _DensePair(torch.autograd.Function):
     params: W_in, b_in, W_out, b_out, W_self, b_self of f_dense_comp, then W_in, W_out, W_self of f_comp (no biases)."""
 
     @staticmethod
-    def forward(ctx, link, s, s_in, norm, b0, b1, gate_only, *params):
+    def forward(ctx, link, sums, s, s_in, norm, b0, b1, gate_only, *params):
         s, s_in, norm = f32c(s), f32c(s_in), f32c(norm)
         params = tuple(f32c(p) for p in params)
         require_hip(s, s_in, norm, *params)
@@ -214,11 +214,26 @@ class _DensePair(torch.autograd.Function):
         out_d = gate if gate_only else torch.empty_like(s)
         dW, dB, cW = [params[0], params[2], params[4]], [params[1], params[3], params[5]], list(params[6:9])
         work = dict(flops=2 * M * K_ * D)
-        call("mrg_dense_filter_fwd3", (0, ptr(s), ptr(s_in), ptr_array(dW), ptr_array(dB), ptr(norm), 1.0 / 3.0, 1.0 / 3.0,
-                                       None if gate_only else ptr(out_d), ptr(gate), ptr(_ws(ws3, s)), b0, b1, M, D, st),
-             nbytes=4 * M * (K_ + (1 if gate_only else 2) * D), **work)
-        call("mrg_dense_filter_fwd3", (1, ptr(s), ptr(s_in), ptr_array(cW), ptr_array([None, None, None]), ptr(norm), 1.0 / 3.0, 1.0, ptr(out_c), None,
-                                       ptr(_ws(ws3, s)), b0, b1, M, D, st), nbytes=4 * M * (K_ + D), **work)
+        wsp = _ws(ws3, s)                                  # the weight-split workspace of both launches, one after the other on this stream; held
+        #                                                    by name until both are enqueued (an allocation in between must not land on it)
+        args_d = (0, ptr(s), ptr(s_in), ptr_array(dW), ptr_array(dB), ptr(norm), 1.0 / 3.0, 1.0 / 3.0,
+                  None if gate_only else ptr(out_d), ptr(gate), ptr(wsp), b0, b1, M, D, st)
+        args_c = (1, ptr(s), ptr(s_in), ptr_array(cW), ptr_array([None, None, None]), ptr(norm), 1.0 / 3.0, 1.0, ptr(out_c), None,
+                  ptr(wsp), b0, b1, M, D, st)
+        # sums (a list the caller reads back, or None): the two row GEMMs also leave the BatchNorm column sums of their outputs --
+        # of gate * s * c whether it is stored or not -- as per-workgroup float64 partials (0 blocks: this shape has no such kernel)
+        for kind, args, nb in ((0, args_d, 4 * M * (K_ + (1 if gate_only else 2) * D)), (1, args_c, 4 * M * (K_ + D))):
+            blocks = int(_lib.load().mrg_dense_filter3_colsum_blocks(kind, b0, b1, M, D, K_)) if sums is not None else 0     # (not cached: follows the GEMM switches)
+            if blocks > 0:
+                part = _ws(blocks * 2 * D * 8, s)
+                call("mrg_dense_filter_fwd3", args + (ptr(part), blocks), nbytes=nb + part.numel() + (4 * M * D if kind == 0 and gate_only else 0),
+                     symbol="mrg_dense_filter_fwd3_colsum", **work)
+                sums.append(_lib.ColSums(part, 0, blocks, 2 * D, M))
+            else:
+                call("mrg_dense_filter_fwd3", args, nbytes=nb, **work)
+                if sums is not None:
+                    sums.append(None)
+        del wsp
         ctx.cfg = (b0, b1)
         ctx.save_for_backward(s, s_in, norm, gate, *params)
         ctx.link = link
@@ -272,7 +287,7 @@ class _DensePair(torch.autograd.Function):
         call("mrg_linear_bwd_weight3", (ptr(dz_c), ptr(s), ptr(s_in), ptr_array(g_cW), ptr_array([None, None, None]), ptr(_ws(wsw, s)), b0, b1, M, D, K_ - D, D, st),
              **wwork)
         grads_d = [t for pair in zip(g_dW, g_dB) for t in pair]
-        return (None, gs, gs_in, None, None, None, None, *grads_d, *g_cW)
+        return (None, None, gs, gs_in, None, None, None, None, *grads_d, *g_cW)
 
 
 def dense_pair_available(D, tied):
@@ -311,7 +326,8 @@ def _gated_rowscale(norm, b1, M, scale_edge, scale_self, device):
 def dense_filter_pair(s, s_in, norm, b0, b1, dense_params, comp_weights, gate_only=False, for_epilogue=False):
     """(f_dense_comp(s, s_in), f_comp(s, s_in)) as one autograd node; dense_params = (W_in, b_in, W_out, b_out, W_self, b_self),
     comp_weights = (W_in, W_out, W_self).  Operands that are the same rows use the folded [D, D] weights.
-    for_epilogue: both results go to mixed_epilogue_prepare and nowhere else: two Candidates sharing the node's Link.
+    for_epilogue: both results go to mixed_epilogue_prepare and nowhere else: two Candidates sharing the node's Link; a
+    candidates.ForEpilogue(stats=True) also asks the two row GEMMs for the candidates' BatchNorm column sums (Candidate.sums).
     gate_only (with for_epilogue): the first is Candidate("gate") around f_dense_comp's GATE -- the epilogue recomputes the
     candidate's value gate * s * c wherever it reads it (the [rows, D] output is never written or re-read)."""
     dW, dB = list(dense_params[0::2]), list(dense_params[1::2])
@@ -327,17 +343,20 @@ def dense_filter_pair(s, s_in, norm, b0, b1, dense_params, comp_weights, gate_on
     gate_only = bool(gate_only and for_epilogue and s.is_cuda)
     fold = for_epilogue and SW.FOLD_ROW_SCALE and s.is_cuda and torch.is_grad_enabled()
     link = Link(2) if fold else None
-    y_d, y_c = _DensePair.apply(link, s, s_in, norm, int(b0), int(b1), gate_only, dW[0], dB[0], dW[1], dB[1], dW[2], dB[2], *cW)
+    sums = [] if (wants_stats(for_epilogue) and s.is_cuda) else None          # filled by the node's forward: [f_dense_comp's, f_comp's]
+    y_d, y_c = _DensePair.apply(link, sums, s, s_in, norm, int(b0), int(b1), gate_only, dW[0], dB[0], dW[1], dB[1], dW[2], dB[2], *cW)
     if not for_epilogue:
         return y_d, y_c
     fold = fold and y_d.requires_grad
     rs_d = (norm, int(b1), 1.0 / 3.0, 1.0 / 3.0, True) if fold else None
     rs_c = (norm, int(b1), 1.0 / 3.0, 1.0, False) if fold else None
+    sums_d, sums_c = sums if sums else (None, None)
     if gate_only:
-        c_d = Candidate("gate", y_d, link=link, slot=0, s=s, c=_gated_rowscale(norm, int(b1), s.shape[0], 1.0 / 3.0, 1.0 / 3.0, s.device), rowscale=rs_d)
+        c_d = Candidate("gate", y_d, link=link, slot=0, s=s, c=_gated_rowscale(norm, int(b1), s.shape[0], 1.0 / 3.0, 1.0 / 3.0, s.device), rowscale=rs_d,
+                        sums=sums_d)
     else:
-        c_d = Candidate("stored", y_d, link=link, slot=0, rowscale=rs_d)
-    return c_d, Candidate("stored", y_c, link=link, slot=1, rowscale=rs_c)
+        c_d = Candidate("stored", y_d, link=link, slot=0, rowscale=rs_d, sums=sums_d)
+    return c_d, Candidate("stored", y_c, link=link, slot=1, rowscale=rs_c, sums=sums_c)
 
 
 def dense_filter_single(s, s_in, W, b):

@@ -7,7 +7,7 @@ import torch
 from .. import _lib
 from .._lib import ptr_array, call, f32c, ptr, require_hip, stream_of
 from ._base import _ws, _ws_bytes, gate_ld, same_rows
-from .candidates import Candidate, Link
+from .candidates import Candidate, Link, wants_stats
 
 
 class _Gate(torch.autograd.Function):
@@ -80,7 +80,7 @@ class _GateRow(torch.autograd.Function):
     (Link.row_written), and formed here otherwise.  Arguments: the Link (or None), then as _Gate."""
 
     @staticmethod
-    def forward(ctx, link, s, s_in, norm, b0, b1, scale, *params):
+    def forward(ctx, link, sums, s, s_in, norm, b0, b1, scale, *params):
         tied = s_in is not None and same_rows(s, s_in)
         s, s_in, norm = f32c(s), (None if tied else f32c(s_in)), f32c(norm)
         params = tuple(f32c(p) for p in params)
@@ -95,7 +95,17 @@ class _GateRow(torch.autograd.Function):
         fvec = torch.empty(M, dtype=torch.float32, device=s.device)
         hvec = torch.empty(M, dtype=torch.float32, device=s.device)
         nb = 4 * D * M * (2 if s_in is not None else 1) + (4 * b1 if norm is not None else 0) + 8 * M
-        call("mrg_gate_row_fwd", (ptr(s), ptr(s_in), ptr(norm), ptr(uvc), ptr(fvec), ptr(hvec), b0, b1, M, D, scale, st), nbytes=nb)
+        args = (ptr(s), ptr(s_in), ptr(norm), ptr(uvc), ptr(fvec), ptr(hvec), b0, b1, M, D, scale, st)
+        # sums (a list the caller reads back, or None): the kernel also leaves the BatchNorm column sums of s (an f_identity candidate
+        # over the same rows) and of s * fvec[r] (this candidate) as per-block float64 partials [blocks][2][2][D]
+        vec4 = D % 4 == 0 and all(t is None or t.data_ptr() % 16 == 0 for t in (s, s_in, uvc))
+        blocks = int(_lib.load().mrg_gate_row_colsum_blocks(b0, b1, M, D, int(vec4))) if sums is not None else 0
+        if blocks > 0:
+            part = _ws(blocks * 4 * D * 8, s)
+            call("mrg_gate_row_fwd", args + (ptr(part), blocks), nbytes=nb + part.numel(), symbol="mrg_gate_row_fwd_colsum")
+            sums += [_lib.ColSums(part, 0, blocks, 4 * D, M), _lib.ColSums(part, 2 * D * 8, blocks, 4 * D, M)]
+        else:
+            call("mrg_gate_row_fwd", args, nbytes=nb)
         ctx.save_for_backward(s, s_in, norm, uvc, hvec, *params)
         ctx.cfg = (b0, b1, scale, in_dim, tied)
         ctx.link = link
@@ -140,13 +150,17 @@ class _GateRow(torch.autograd.Function):
             for seg, (lo, hi) in enumerate(((0, b0), (b0, b1), (b1, M))):
                 if hi > lo:
                     torch.mul(dz[lo:hi, None], uvc[seg, :D][None, :], out=gs[lo:hi])
-        return (None, gs, gs_in, None, None, None, None, *gparams)
+        return (None, None, gs, gs_in, None, None, None, None, *gparams)
 
 
-def gate_comp_row_factor(s, s_in, norm, b0, b1, W_in, b_in, a_in, W_out, b_out, a_out, W_self, b_self, a_self):
+def gate_comp_row_factor(s, s_in, norm, b0, b1, W_in, b_in, a_in, W_out, b_out, a_out, W_self, b_self, a_self, for_epilogue=True):
     """f_sparse_comp as a row factor for mixed_epilogue: Candidate("rowfactor") around the [M] factor; the candidate is
-    s * fvec[:, None] (mixed_epilogue_prepare multiplies it out itself when it cannot recompute it in its kernels)."""
+    s * fvec[:, None] (mixed_epilogue_prepare multiplies it out itself when it cannot recompute it in its kernels).
+    for_epilogue: a candidates.ForEpilogue(stats=True) also asks the kernel for the BatchNorm column sums of the candidate
+    (Candidate.sums) and of the rows s themselves (Candidate.s_sums)."""
     s = f32c(s)
     link = Link()
-    fvec = _GateRow.apply(link, s, s_in, norm, int(b0), int(b1), 1.0 / 3.0, W_in, b_in, a_in, W_out, b_out, a_out, W_self, b_self, a_self)
-    return Candidate("rowfactor", fvec, link=link, s=s, b0=int(b0), b1=int(b1))
+    sums = [] if (wants_stats(for_epilogue) and s.is_cuda) else None          # filled by the node's forward: [of s, of s * fvec]
+    fvec = _GateRow.apply(link, sums, s, s_in, norm, int(b0), int(b1), 1.0 / 3.0, W_in, b_in, a_in, W_out, b_out, a_out, W_self, b_self, a_self)
+    s_sums, f_sums = sums if sums else (None, None)
+    return Candidate("rowfactor", fvec, link=link, s=s, b0=int(b0), b1=int(b1), sums=f_sums, s_sums=s_sums)

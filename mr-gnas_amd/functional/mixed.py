@@ -17,8 +17,11 @@ class _MixCfg:
     updated in place like torch does), which branches are all-zero, sharding info, the valid-row count."""
 
     def __init__(self, bns, present, group=None, total_rows=None, has_addend=False, rowscale=None, identity=None, gated=None, act=0,
-                 valid_rows=None):
+                 valid_rows=None, given=None):
         self.bns, self.present, self.group, self.total_rows, self.has_addend = bns, present, group, total_rows, has_addend
+        # per candidate None or the _lib.ColSums its producer formed (mrg_gated_branch.given): the statistics launch skips the sweep over
+        # such a candidate.  Consumed (and its buffers released) by the forward.
+        self.given = given
         self.act = act                 # 0 ReLU, 1 tanh behind the BatchNorm (_lib.ACTS)
         # int32 [1] device tensor: rows at and beyond *valid_rows are capacity padding (a static step graph, RelGraph.valid_rows) --
         # out of every statistic, written as zeros.  None: every row is valid.  Held here for the backward's launches too.
@@ -73,8 +76,22 @@ class _MixedEpilogue(torch.autograd.Function):
             rv = ptr_array([b.running_var if track else None for b in cfg.bns])
             mom = bn0.momentum if bn0.momentum is not None else 0.1
             if cfg.group is None:                          # no collective between statistics and coefficients: two launches, not three
-                call("mrg_mix_stats_coef", (ypa, ptr_array(gam), ptr_array(bet), rm, rv, K_, rows, total, D, bn0.eps, mom, ptr(coef), ptr(ws), gb, st),
-                     nbytes=4 * D * rows * nz_rd)
+                given, cfg.given = cfg.given, None
+                if given is not None and cfg.valid_rows is None and all(c is None or c.rows == rows for c in given):
+                    # producer sums: only the candidates without them are swept (none, for a first-stage MixedOp of the search space)
+                    swept = set()
+                    for k, y in enumerate(ys):
+                        if y is not None and given[k] is None:
+                            swept.add(y.data_ptr())
+                            if cfg.gated is not None and k == cfg.gated.get("k"):
+                                swept.add(cfg.gated["s"].data_ptr())
+                    gb_stats = _lib.gated_branch(cfg.gated, act=cfg.act, given=given)
+                    nb_stats = 4 * D * rows * len(swept) + sum(c.n * 2 * D * 8 for c in given if c is not None)
+                else:
+                    gb_stats, nb_stats = gb, 4 * D * rows * nz_rd
+                call("mrg_mix_stats_coef", (ypa, ptr_array(gam), ptr_array(bet), rm, rv, K_, rows, total, D, bn0.eps, mom, ptr(coef), ptr(ws), gb_stats, st),
+                     nbytes=nb_stats)
+                del given
             else:
                 import torch.distributed as dist
                 if cfg.chain is not None and cfg.chain[0].sums is not None:
@@ -397,5 +414,16 @@ def mixed_epilogue_prepare(ys, bns, group=None, total_rows=None, fold_row_scales
             gated.update(row_k=k, row_f=y, b0=rb0, b1=rb1, row_link=c.link if wants_grad else None)
         else:
             ys[k] = c.materialize()
-    cfg = _MixCfg(list(bns), present, group, total_rows, False, rowscale, identity, gated, _lib.ACTS[act], valid_rows)
+    # BatchNorm sums that the producers formed (Candidate.sums; the row factor's producer also has those of s itself, the value of an
+    # f_identity candidate over the same rows): used when the statistics are this launch's own rows in training mode
+    given = None
+    if group is None and valid_rows is None and bns and (bns[0].training or not bns[0].track_running_stats):
+        given = [c.sums if c is not None else None for c in cands]
+        if identity is not None and cands[identity] is None and ys[identity] is not None:
+            for c in cands:
+                if c is not None and c.kind == "rowfactor" and c.s_sums is not None and _same_memory(c.s, ys[identity]):
+                    given[identity] = c.s_sums
+        if not any(c is not None for c in given):
+            given = None
+    cfg = _MixCfg(list(bns), present, group, total_rows, False, rowscale, identity, gated, _lib.ACTS[act], valid_rows, given)
     return PreparedEpilogue(cfg, [y for y in ys if y is not None], list(bns))

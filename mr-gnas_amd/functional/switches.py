@@ -24,6 +24,9 @@ FOLD_ROW_SCALE = os.environ.get("MRG_FOLD_ROW_SCALE", "1") == "1"          # lab
 GROUPED_SEGMENTS = os.environ.get("MRG_GROUPED_SEGMENTS", "1") == "1"    # lab switch: 0 = one launch per direction segment
 DENSE_PAIR = os.environ.get("MRG_DENSE_PAIR", "1") == "1"       # lab switch: 0 = f_dense_comp and f_comp of a MixedOp as two autograd nodes
 GATED_RECOMPUTE = os.environ.get("MRG_GATED_RECOMPUTE", "1") == "1"     # lab switch: 0 = f_dense_comp's output is stored for the epilogue
+# lab switch: 0 = the BatchNorm sums of a first-stage MixedOp's candidates come from the statistics pass over the stored tensors instead
+# of from the kernels that produce them (row GEMM epilogues, the row-factor gate)
+PRODUCER_STATS = os.environ.get("MRG_PRODUCER_STATS", "1") == "1"
 COMPGCN_TAIL = os.environ.get("MRG_COMPGCN_TAIL", "1") == "1"     # lab switch: 0 = CompGraphConv's BatchNorm -> tanh tail on torch kernels
 SPARSE_AMAX_BWD = os.environ.get("MRG_SPARSE_AMAX_BWD", "1") == "1"   # lab switch: 0 = a_max's input gradient as seg_bwd_k + the dense row GEMM
 # ccorr (functional/ccorr.py): None = a shared row takes the matrix path from ccorr.MATRIX_MIN_ROWS rows on; "rows" / "matrix" force

@@ -135,7 +135,7 @@ class f_sparse_op_comp(_Operator):
             W, a = getattr(self, "W_" + x), getattr(self, "a_" + x)
             p += [W.weight, W.bias, a.weight]
         if for_epilogue and K.switches.ROW_FACTOR and src_emb.is_cuda:
-            return K.gate_comp_row_factor(src_emb, src_emb_in, g.norm_flat(), b0, b1, *p)
+            return K.gate_comp_row_factor(src_emb, src_emb_in, g.norm_flat(), b0, b1, *p, for_epilogue=for_epilogue)
         return K.gate_comp(src_emb, src_emb_in, g.norm_flat(), b0, b1, *p)
 
 

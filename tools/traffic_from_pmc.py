@@ -69,6 +69,15 @@ ENTRY_KERNELS.update({
     "mrg_gate_row_bwd": ["gate_row_bwd_k"],
     "mrg_sum_rows_gather": ["sum_rows_gather_k"],
 })
+# producer statistics: the first-stage MixedOps' row GEMMs are the EPI 6 / 7 instances (gate / scale with column sums), their row-factor
+# gate is gate_row_fwd_colsum_k, and mrg_mix_stats_coef launches mix_given_reduce_k in front of the finalizer (with mix_colstats_k only
+# where a candidate came without sums; the node-row MixedOps keep mix_colstats_k alone).  "missing kernels are skipped" covers both.
+ENTRY_KERNELS.update({
+    "mrg_dense_filter_fwd3": ["rowgemm_x3q_k<6, true>@max|rowgemm_x3q_k<7, true>@max|rowgemm_x3s_k<7, 6,@max|rowgemm_x3s_k<7, 7,@max|"
+                              "rowgemm_x3q_k<1, true>@max|rowgemm_x3q_k<2, true>@max|rowgemm_x3s_k<7, 1,@max|rowgemm_x3s_k<7, 2,@max"],
+    "mrg_gate_row_fwd": ["gate_row_fwd_colsum_k|gate_row_fwd_k"],
+    "mrg_mix_stats_coef": ["mix_colstats_k", "mix_given_reduce_k", "mix_reduce_finalize_fwd_k"],
+})
 NORTH_STAR = "span_gcs_k<4, 64, 1, 0,"            # MODE = SUB only runs in bench.py's north-star passes (last parameter: prefetch-depth override)
 
 
