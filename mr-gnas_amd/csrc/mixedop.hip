@@ -510,16 +510,135 @@ __global__ void mix_finalize_bwd_k(const float* __restrict__ red, int K, double 
 }
 
 // ---- backward apply: gy_k = (gr - c1 - xhat*c2) * scale      (skipped where gy_k is NULL)
-// The row-scaled candidate gp.rk (GATED variant; f_sparse_op_comp, y = s * f_r with f_r = sigmoid(u.s + v.s_in + c0) * t_r) has no
-// gradient tensor of its own: with gy its gradient w.r.t. y, this kernel forms the row dot q_r = sum_c gy * s (the lanes of the
-// row, same order as gate_bwd_k) -> gp.rdq[r], the gradient w.r.t. f_r, from which mrg_gate_row_bwd derives the candidate's
+// The row-scaled candidate gp.rk (f_sparse_op_comp, y = s * f_r with f_r = sigmoid(u.s + v.s_in + c0) * t_r) has no gradient
+// tensor of its own: with gy its gradient w.r.t. y, this kernel forms the row dot q_r = sum_c gy * s (the lanes of the
+// row, same order as gate_bwd_k) -> rdq[r], the gradient w.r.t. f_r, from which mrg_gate_row_bwd derives the candidate's
 // parameter / s_in gradients; and with dz_r = q_r * h_r (h_r = t_r * gate * (1 - gate), saved by the forward) it ADDS the candidate's
 // whole gradient w.r.t. s, gy * f_r + dz_r * u[c], into the gated candidate's direct term gs_out (gradients w.r.t. the same rows s).
-template <int VEC, int LPR, int KMAX, bool GATED, int KB, int ACT = 0>
-__global__ __launch_bounds__(MRG_BLOCK) void mix_bwd_apply_k(const float* __restrict__ g, PtrPack ys, MutPack gys, int K,
-                                                             const float* __restrict__ coef, const float* __restrict__ coef2,
-                                                             const float* __restrict__ w, int64_t rows, int D, RowScalePack rsp,
-                                                             GatedPack gp) {
+//
+// ROLES.  The launcher knows before the launch what each candidate is, and hands the kernel one field per role instead of
+// per-candidate arrays that the row loop indexes (1056 bytes of by-value packs against 102 scalar registers per wave: 153 to 759
+// spilled SGPRs per instance, read back through v_readlane on every row -- profiles/mix_apply_asm.txt):
+//   gated  the recomputed candidate (ys holds its GATE, its value is gate * s * c_r) whose folded store writes dz and gs_out,
+//   row    the row-scaled candidate (value s * f_r; no gradient tensor: rdq and a term of gs_out),
+//   add    the candidate whose output IS s (f_identity) and whose gradient is added into gs_out instead of being stored,
+//   other  a stored candidate: gy_k, times a full-row multiplier where one is folded in.
+// Which roles exist is a property of the instance: the row loop has no branch or select on a role.  All three s-valued roles take s
+// from ONE load.  Anything else (more than five candidates, the edge/self form of a row scale, a stored gated candidate, ...)
+// runs on mix_bwd_apply_any_k below.
+//
+// ROUNDING.  Every expression is the one the by-index kernel compiled to, spelled out: which products are fused into an fma and
+// which are rounded on their own is part of the results (tests/golden/mix_apply_*.npz pin them), so contraction is OFF in
+// these functions and the fused ones are written as __builtin_fmaf.
+// gy of one candidate at one lane: v its value, gv the upstream gradient, cf its six coefficient rows in LDS.
+//   z = v c0 + c1 (fma);  xh = v c2 - c3;  gr = [z > 0] w g  (tanh: w g (1 - th^2));  gy = ((gr - c4) - xh c5 (fma)) c0 live
+// The by-index kernel's vectorizer paired some of these operations across elements, which decided what was contracted, and the
+// pairs are part of the bits (`first`: the candidate is candidate 0 of the MixedOp, the first one the unrolled loop met):
+//   xh   one fma -- but a rounded product minus c3 in scalar lanes (VEC == 1), and for the odd elements of candidate 0;
+//   tanh gr - c4 is one fma of w g and (1 - th^2) = fma(-th, th, 1) -- but element 3 of candidate 0 rounds w g (1 - th^2), the
+//        difference and xh c5 one by one.
+template <int VEC, int ACT>
+__device__ __forceinline__ Vec<VEC> apply_gy(const Vec<VEC>& v, const Vec<VEC>& gv, const float* cf, int D, float wk, float live, bool first) {
+#pragma clang fp contract(off)
+  const Vec<VEC> c0 = Vec<VEC>::load(cf), c1 = Vec<VEC>::load(cf + D), c2 = Vec<VEC>::load(cf + 2 * D),
+                 c3 = Vec<VEC>::load(cf + 3 * D), c4 = Vec<VEC>::load(cf + 4 * D), c5 = Vec<VEC>::load(cf + 5 * D);
+  Vec<VEC> o;
+#pragma unroll
+  for (int j = 0; j < VEC; ++j) {
+    const float z = __builtin_fmaf(v[j], c0[j], c1[j]);
+    float xh = __builtin_fmaf(v[j], c2[j], -c3[j]);
+    if (VEC == 1 && ACT == 0) xh = v[j] * c2[j] - c3[j];
+    else if (ACT == 0 && (j & 1)) xh = first ? v[j] * c2[j] - c3[j] : xh;
+    float t;
+    if constexpr (ACT == 0) {
+      const float gr = z > 0.f ? wk * gv[j] : 0.f;
+      t = __builtin_fmaf(-xh, c5[j], gr - c4[j]);
+    } else {
+      const float th = tanhf(z);
+      const float wg = wk * gv[j], om = __builtin_fmaf(-th, th, 1.f);
+      t = __builtin_fmaf(-xh, c5[j], __builtin_fmaf(wg, om, -c4[j]));
+      if (VEC == 4 && j == 3) t = first ? (wg * om - c4[j]) - xh * c5[j] : t;
+    }
+    o[j] = t * c0[j] * live;
+  }
+  return o;
+}
+
+// the gated candidate's folded store (same expressions, same order as dense_dz_k<.., 0>): gc = gy * ck;
+// dz = gc * s * gate * (1 - gate);  o2 = gc * gate, the direct term of the gradient w.r.t. s
+template <int VEC>
+__device__ __forceinline__ void apply_gated(const Vec<VEC>& gy, float ck, const Vec<VEC>& sv, const Vec<VEC>& ga, Vec<VEC>& dzv, Vec<VEC>& o2) {
+#pragma clang fp contract(off)
+#pragma unroll
+  for (int j = 0; j < VEC; ++j) {
+    const float gc = gy[j] * ck;
+    o2[j] = gc * ga[j];
+    dzv[j] = gc * sv[j] * ga[j] * (1.0f - ga[j]);
+  }
+}
+
+// the row-scaled candidate's share of gs_out: o2 + (gy * f_r + dz_r * u)
+template <int VEC>
+__device__ __forceinline__ void apply_row_term(Vec<VEC>& o2, const Vec<VEC>& orv, float rfv, float dzr, const Vec<VEC>& guv) {
+#pragma clang fp contract(off)
+#pragma unroll
+  for (int j = 0; j < VEC; ++j) o2[j] = o2[j] + __builtin_fmaf(orv[j], rfv, dzr * guv[j]);
+}
+
+// this lane's part of the row dot sum_c gy * s: each product rounded, added in column order
+template <int VEC>
+__device__ __forceinline__ float apply_row_dot(const Vec<VEC>& orv, const Vec<VEC>& sv) {
+#pragma clang fp contract(off)
+  float dq = 0.f;
+#pragma unroll
+  for (int j = 0; j < VEC; ++j) dq = dq + orv[j] * sv[j];
+  return dq;
+}
+
+template <int VEC>
+__device__ __forceinline__ Vec<VEC> apply_scaled(const Vec<VEC>& a, float x) {
+#pragma clang fp contract(off)
+  Vec<VEC> o;
+#pragma unroll
+  for (int j = 0; j < VEC; ++j) o[j] = a[j] * x;
+  return o;
+}
+
+template <int VEC>
+__device__ __forceinline__ Vec<VEC> apply_sum(const Vec<VEC>& a, const Vec<VEC>& b) {
+#pragma clang fp contract(off)
+  Vec<VEC> o;
+#pragma unroll
+  for (int j = 0; j < VEC; ++j) o[j] = a[j] + b[j];
+  return o;
+}
+
+// the recomputed gated candidate's value gate * s * c_r (the row GEMM's gate epilogue: g * in * cs)
+template <int VEC>
+__device__ __forceinline__ Vec<VEC> apply_gate_value(const Vec<VEC>& ga, const Vec<VEC>& sv, float gck) {
+#pragma clang fp contract(off)
+  Vec<VEC> o;
+#pragma unroll
+  for (int j = 0; j < VEC; ++j) o[j] = ga[j] * sv[j] * gck;
+  return o;
+}
+
+constexpr int APPLY_NO = 5;                     // stored candidates of a role-resolved launch
+struct ApplySlots { int g, r, a, o[APPLY_NO]; };      // the candidate index (coefficient / weight slot) behind each role
+struct ApplyOther { const float* y; float* gy; const float* full; };
+template <int NO> struct ApplyOthers { ApplyOther o[NO]; };
+
+// HG / HR / HA: the gated, row and add roles exist.  NO: stored candidates -- exactly NO with a gated role, n_oth <= NO without.
+template <int VEC, int LPR, int KMAX, int ACT, bool HG, bool HR, bool HA, int NO>
+__global__ __launch_bounds__(MRG_BLOCK) void mix_bwd_apply_k(
+    const float* __restrict__ g, const float* __restrict__ coef, const float* __restrict__ coef2, const float* __restrict__ w, int K,
+    int64_t rows, int D, const int32_t* __restrict__ vrows, ApplySlots slot, int n_oth, ApplyOthers<NO> oth,
+    const float* __restrict__ gate, const float* __restrict__ s, const float* __restrict__ c, const float* __restrict__ ck,
+    float* __restrict__ dz, float* __restrict__ gs_out,
+    const float* __restrict__ rf, const float* __restrict__ rh, const float* __restrict__ uvc, int uld, int64_t b0, int64_t b1,
+    float* __restrict__ rdq) {
+  static_assert(!HR || (HG && KMAX == 1), "the row dot is one group_sum over the row's lanes; its gradient goes into gs_out");
+  static_assert(!HA || HG, "the added candidate goes into the gated candidate's gs_out");
   extern __shared__ float lds[];                 // [K][6][D]: scale, shift, invstd, mean*invstd, c1, c2
   constexpr int RPB = MRG_BLOCK / LPR;
   const int sl = threadIdx.x % LPR, rw = row_group_of_thread<LPR>();
@@ -529,138 +648,185 @@ __global__ __launch_bounds__(MRG_BLOCK) void mix_bwd_apply_k(const float* __rest
     lds[t] = rem < 4 * D ? coef[(int64_t)k * 4 * D + rem] : coef2[(int64_t)k * 2 * D + rem - 4 * D];
   }
   __syncthreads();
-  float wk[KB];
-  bool need[KB];                                 // gy_k is wanted: stored, or added into a gated candidate's gs_out
+  const int n = HG ? NO : n_oth;
+  const bool first0 = slot.o[0] == 0;           // candidate 0 (apply_gy): only the first stored one of a launch without a gated role can be it
+  float wg = 0.f, wr = 0.f, wa = 0.f, wo[NO];
+  const float* cfo[NO];
+  if constexpr (HG) wg = w[slot.g];
+  if constexpr (HR) wr = w[slot.r];
+  if constexpr (HA) wa = w[slot.a];
 #pragma unroll
-  for (int k = 0; k < KB; ++k) {
-    wk[k] = k < K ? w[k] : 0.f;
-    need[k] = k < K && (gys.p[k] != nullptr || (GATED && k == gp.rk));
+  for (int i = 0; i < NO; ++i) {
+    wo[i] = i < n ? w[slot.o[i]] : 0.f;
+    cfo[i] = lds + (i < n ? slot.o[i] : 0) * 6 * D;
   }
-#pragma unroll
-  for (int k = 0; k < KB; ++k)
-    if (k < K && rsp.on[k] == 2 && rsp.add_from[k] >= 0) {
-#pragma unroll
-      for (int q = 0; q < KB; ++q) if (q == rsp.add_from[k]) need[q] = true;
-    }
-  const bool hasr = GATED && gp.rk >= 0;
-  const int64_t nvalid = valid_rows(gp.vrows, rows);
-  for (int64_t r = (int64_t)blockIdx.x * RPB + rw; r < rows; r += (int64_t)gridDim.x * RPB) {
+  const float* cfg = lds + (HG ? slot.g : 0) * 6 * D;
+  const float* cfr = lds + (HR ? slot.r : 0) * 6 * D;
+  const float* cfa = lds + (HA ? slot.a : 0) * 6 * D;
+  const int64_t nvalid = valid_rows(vrows, rows);
+  const int64_t step = (int64_t)gridDim.x * RPB;
+  for (int64_t r = (int64_t)blockIdx.x * RPB + rw; r < rows; r += step) {
     const float live = r < nvalid ? 1.0f : 0.0f;             // capacity padding: every gradient row written there is zero
+    const int64_t ro = r * D;
+    // row-uniform values (with LPR == 64 the row is the wave's: scalar loads)
+    float gck = 1.f, ckv = 1.f, rfv = 1.f, rhv = 0.f, fo[NO];
+    const float* urow = uvc;
+    if constexpr (HG) { gck = c[r]; ckv = ck[r]; }
+    if constexpr (HR) {
+      rfv = rf[r];
+      rhv = rh[r];
+      urow = uvc + (int64_t)((r >= b0) + (r >= b1)) * uld;
+    }
+#pragma unroll
+    for (int i = 0; i < NO; ++i) fo[i] = (HG && i < n && oth.o[i].full) ? oth.o[i].full[r] : 1.f;     // (folded multipliers: next to a gated role only)
 #pragma unroll
     for (int q = 0; q < KMAX; ++q) {
-      const int c = sl + q * LPR;
-      const bool act = c < dv;
-      float gck = 1.f, rfv = 1.f, rhv = 0.f;               // the recomputed candidates' row multipliers and s (see mix_fwd_k)
-      Vec<VEC> gsv = Vec<VEC>::fill(0.f), gga = Vec<VEC>::fill(0.f), guv = Vec<VEC>::fill(0.f);
-      Vec<VEC> ov[KB];                           // every wanted gy_k first: a gated candidate may add another one's
-      Vec<VEC> orv = Vec<VEC>::fill(0.f);                  // gy of the row-scaled candidate
+      const int cc = sl + q * LPR;
+      const bool act = cc < dv;
+      const int off = cc * VEC;
+      Vec<VEC> gsv, gga, guv, ovg, ova, orv, ovo[NO];        // (set and read by the active lanes only)
       float dq = 0.f;
-      float ckv[KB];                                       // folded row multipliers (RowScalePack.full)
-#pragma unroll
-      for (int k = 0; k < KB; ++k) ckv[k] = 1.f;
       if (act) {
-        if constexpr (GATED) {                             // (unconditional: the host hands safe pointers for what is absent)
-          gck = gated_rowscale(gp, r);
+        // every load first
+        if constexpr (HG) { gsv = Vec<VEC>::load(s + ro + off); gga = Vec<VEC>::load(gate + ro + off); }
+        if constexpr (HR) guv = Vec<VEC>::load(urow + off);
+        const Vec<VEC> gv = Vec<VEC>::load(g + ro + off);
+        Vec<VEC> vo[NO];
+#pragma unroll
+        for (int i = 0; i < NO; ++i) {
+          vo[i] = Vec<VEC>::fill(0.f);
+          if (i < n && oth.o[i].y) vo[i] = Vec<VEC>::load(oth.o[i].y + ro + off);
+        }
+        if constexpr (HG) ovg = apply_gy<VEC, ACT>(apply_gate_value<VEC>(gga, gsv, gck), gv, cfg + off, D, wg, live, false);
+        if constexpr (HA) ova = apply_gy<VEC, ACT>(gsv, gv, cfa + off, D, wa, live, false);
+        if constexpr (HR) {
+          orv = apply_gy<VEC, ACT>(apply_scaled<VEC>(gsv, rfv), gv, cfr + off, D, wr, live, false);
+          dq = apply_row_dot<VEC>(orv, gsv);
+        }
+#pragma unroll
+        for (int i = 0; i < NO; ++i)
+          if (i < n) ovo[i] = apply_gy<VEC, ACT>(vo[i], gv, cfo[i] + off, D, wo[i], live, !HG && i == 0 && first0);
+      }
+      float dzr = 0.f;
+      if constexpr (HR) {                                  // all lanes of the row (inactive ones carry 0)
+        const float qr = group_sum<LPR>(dq);                // (one row per wave: DPP + scalar registers, no LDS round trips)
+        dzr = qr * rhv;
+        if (sl == 0) rdq[r] = qr;
+      }
+      if (act) {
+#pragma unroll
+        for (int i = 0; i < NO; ++i)
+          if (i < n) {
+            Vec<VEC> o = ovo[i];
+            if (HG && oth.o[i].full) o = apply_scaled<VEC>(o, fo[i]);     // f_comp: dz = g * c
+            o.store(oth.o[i].gy + ro + off);
+          }
+        if constexpr (HG) {
+          Vec<VEC> dzv, o2;
+          apply_gated<VEC>(ovg, ckv, gsv, gga, dzv, o2);
+          if constexpr (HA) o2 = apply_sum<VEC>(o2, ova);   // + the gradient of the candidate whose output IS s
+          if constexpr (HR) apply_row_term<VEC>(o2, orv, rfv, dzr, guv);
+          o2.store(gs_out + ro + off);
+          dzv.store(dz + ro + off);
+        }
+      }
+    }
+  }
+}
+
+// ---- backward apply, any layout: the candidates one after the other (a loop that is NOT unrolled: the per-candidate arrays stay
+// in the argument block and each trip loads the few fields it needs), the row-scaled and the added candidate first.  Same
+// expressions as above.
+template <int VEC>
+struct ApplyAny {
+  const PtrPack& ys; const RowScalePack& rsp; const GatedPack& gp;
+  const float* lds; const float* w; int D; int act;
+  // gy of candidate k at (row offset ro, column offset off); *raw: what its slot of ys holds (the gate of the gated candidate)
+  __device__ __forceinline__ Vec<VEC> gy(int k, int64_t r, int64_t ro, int off, const Vec<VEC>& gv, const Vec<VEC>& gsv, float live, Vec<VEC>* raw) const {
+    Vec<VEC> v = Vec<VEC>::fill(0.f);
+    const float* y = ys.p[k];
+    if (y) v = Vec<VEC>::load(y + ro + off);
+    *raw = v;
+    if (k == gp.k) v = apply_gate_value<VEC>(v, gsv, gp.c[r]);
+    if (k == gp.rk) v = apply_scaled<VEC>(v, gp.rf[r]);
+    const float* cf = lds + k * 6 * D + off;
+    return act == 1 ? apply_gy<VEC, 1>(v, gv, cf, D, w[k], live, k == 0) : apply_gy<VEC, 0>(v, gv, cf, D, w[k], live, k == 0);
+  }
+};
+
+template <int VEC, int LPR, int KMAX>
+__global__ __launch_bounds__(MRG_BLOCK) void mix_bwd_apply_any_k(const float* __restrict__ g, PtrPack ys, MutPack gys, int K,
+                                                                 const float* __restrict__ coef, const float* __restrict__ coef2,
+                                                                 const float* __restrict__ w, int64_t rows, int D, RowScalePack rsp,
+                                                                 GatedPack gp) {
+  extern __shared__ float lds[];                 // [K][6][D]: scale, shift, invstd, mean*invstd, c1, c2
+  constexpr int RPB = MRG_BLOCK / LPR;
+  const int sl = threadIdx.x % LPR, rw = row_group_of_thread<LPR>();
+  const int dv = D / VEC;
+  for (int t = threadIdx.x; t < K * 6 * D; t += MRG_BLOCK) {
+    int k = t / (6 * D), rem = t - k * 6 * D;
+    lds[t] = rem < 4 * D ? coef[(int64_t)k * 4 * D + rem] : coef2[(int64_t)k * 2 * D + rem - 4 * D];
+  }
+  __syncthreads();
+  const ApplyAny<VEC> any{ys, rsp, gp, lds, w, D, gp.act};
+  const bool hass = gp.k >= 0 || gp.rk >= 0, hasr = KMAX == 1 && gp.rk >= 0;      // (a row role: KMAX == 1, host-checked)
+  const int64_t nvalid = valid_rows(gp.vrows, rows);
+  for (int64_t r = (int64_t)blockIdx.x * RPB + rw; r < rows; r += (int64_t)gridDim.x * RPB) {
+    const float live = r < nvalid ? 1.0f : 0.0f;
+    const int64_t ro = r * D;
+#pragma unroll 1
+    for (int q = 0; q < KMAX; ++q) {
+      const int cc = sl + q * LPR;
+      const bool act = cc < dv;
+      const int off = cc * VEC;
+      Vec<VEC> gsv = Vec<VEC>::fill(0.f), guv, gv, orv, raw;
+      float rfv = 1.f, rhv = 0.f, dq = 0.f;
+      if (act) {
+        gv = Vec<VEC>::load(g + ro + off);
+        if (hass) gsv = Vec<VEC>::load(gp.s + ro + off);
+        if (hasr) {
           rfv = gp.rf[r];
           rhv = gp.rh[r];
-          gsv = Vec<VEC>::load(gp.s + r * D + c * VEC);
-          const int seg = (r >= gp.b0) + (r >= gp.b1);
-          guv = Vec<VEC>::load(gp.uvc + (int64_t)seg * gp.uld + c * VEC);
-        }
-        Vec<VEC> gv = Vec<VEC>::load(g + r * D + c * VEC);
-        Vec<VEC> vin[KB];                        // all loads first (see mix_fwd_k)
-#pragma unroll
-        for (int k = 0; k < KB; ++k) {
-          vin[k] = Vec<VEC>::fill(0.f);
-          if (k < K && need[k] && ys.p[k]) vin[k] = Vec<VEC>::load(ys.p[k] + r * D + c * VEC);
-          if (k < K && rsp.on[k] && rsp.full[k]) ckv[k] = rsp.full[k][r];
-        }
-        if constexpr (GATED) {
-#pragma unroll
-          for (int k = 0; k < KB; ++k) {
-            if (k == gp.k) {
-              gga = vin[k];
-#pragma unroll
-              for (int j = 0; j < VEC; ++j) vin[k][j] = vin[k][j] * gsv[j] * gck;
-            }
-            if (k == gp.rk) {
-#pragma unroll
-              for (int j = 0; j < VEC; ++j) vin[k][j] = vin[k][j] * rfv;
-            }
-          }
-        }
-#pragma unroll
-        for (int k = 0; k < KB; ++k) {
-          ov[k] = Vec<VEC>::fill(0.f);
-          if (k < K && need[k]) {
-            const Vec<VEC> v = vin[k];
-            const float* cf = lds + k * 6 * D + c * VEC;
-            const Vec<VEC> c0 = Vec<VEC>::load(cf), c1 = Vec<VEC>::load(cf + D), c2 = Vec<VEC>::load(cf + 2 * D),
-                           c3 = Vec<VEC>::load(cf + 3 * D), c4 = Vec<VEC>::load(cf + 4 * D), c5 = Vec<VEC>::load(cf + 5 * D);
-#pragma unroll
-            for (int j = 0; j < VEC; ++j) {
-              float z = v[j] * c0[j] + c1[j];
-              float xh = v[j] * c2[j] - c3[j];
-              float gr;
-              if constexpr (ACT == 0) gr = z > 0.f ? wk[k] * gv[j] : 0.f;
-              else { const float th = tanhf(z); gr = wk[k] * gv[j] * (1.f - th * th); }
-              ov[k][j] = (gr - c4[j] - xh * c5[j]) * c0[j] * live;
-            }
-          }
-        }
-        if (hasr) {
-#pragma unroll
-          for (int k = 0; k < KB; ++k) if (k == gp.rk) orv = ov[k];
-#pragma unroll
-          for (int j = 0; j < VEC; ++j) dq += orv[j] * gsv[j];
+          guv = Vec<VEC>::load(gp.uvc + (int64_t)((r >= gp.b0) + (r >= gp.b1)) * gp.uld + off);
+          orv = any.gy(gp.rk, r, ro, off, gv, gsv, live, &raw);
+          dq = apply_row_dot<VEC>(orv, gsv);
         }
       }
       float dzr = 0.f;
-      if (hasr) {                                          // all lanes of the row (inactive ones carry 0): KMAX == 1 (host-checked)
-        const float qr = group_sum<LPR>(dq);                // (one row per wave: DPP + scalar registers, no LDS round trips)
-        dzr = qr * rhv;                                    // (used by the active lanes only, which loaded rhv)
+      if (hasr) {                                          // KMAX == 1 (host-checked)
+        const float qr = group_sum<LPR>(dq);
+        dzr = qr * rhv;
         if (sl == 0) gp.rdq[r] = qr;
       }
       if (act) {
-#pragma unroll
-        for (int k = 0; k < KB; ++k) {
-          if (k < K && gys.p[k] != nullptr) {
-            Vec<VEC> o = ov[k];
-            if (rsp.on[k]) {                               // the consumer's first backward pass (mrg_dense_filter_dz) folded into this store
-              const float ck = rsp.full[k] ? ckv[k]
-                                           : (r < rsp.edge_rows[k] ? rsp.scale[k] * (rsp.rs[k] ? rsp.rs[k][r] : 1.0f) : rsp.self_scale[k]);
-              if (rsp.on[k] == 2) {                        // f_dense_comp: same expressions, same order as dense_dz_k<.., 0>
-                // (the recomputed candidate holds both already: the host checks rsp.s[k] == gp.s and rsp.gate[k] == ys.p[k])
-                const Vec<VEC> sv = (GATED && k == gp.k) ? gsv : Vec<VEC>::load(rsp.s[k] + r * D + c * VEC);
-                const Vec<VEC> ga = (GATED && k == gp.k) ? gga : Vec<VEC>::load(rsp.gate[k] + r * D + c * VEC);
-                Vec<VEC> o2;
-#pragma unroll
-                for (int j = 0; j < VEC; ++j) {
-                  const float gc = o[j] * ck;
-                  o2[j] = gc * ga[j];
-                  o[j] = gc * sv[j] * ga[j] * (1.0f - ga[j]);
-                }
-                const int af = rsp.add_from[k];
-                if (af >= 0) {                             // + the gradient of the candidate whose output IS this one's operand s
-#pragma unroll
-                  for (int qq = 0; qq < KB; ++qq)
-                    if (qq == af) {
-#pragma unroll
-                      for (int j = 0; j < VEC; ++j) o2[j] += ov[qq][j];
-                    }
-                }
-                if (hasr && k == gp.k) {                   // + the row-scaled candidate's gradient w.r.t. s: gy * f_r + dz_r * u
-#pragma unroll
-                  for (int j = 0; j < VEC; ++j) o2[j] += orv[j] * rfv + dzr * guv[j];
-                }
-                o2.store(rsp.gs_out[k] + r * D + c * VEC);
-              } else {                                     // f_comp: dz = g * c
-#pragma unroll
-                for (int j = 0; j < VEC; ++j) o[j] = o[j] * ck;
-              }
+#pragma unroll 1
+        for (int k = 0; k < K; ++k) {
+          float* dst = gys.p[k];
+          if (dst == nullptr) continue;
+          Vec<VEC> o = any.gy(k, r, ro, off, gv, gsv, live, &raw);
+          const int on = rsp.on[k];
+          if (on) {                                        // the consumer's first backward pass (mrg_dense_filter_dz) folded into this store
+            const float* full = rsp.full[k];
+            float ckv;
+            if (full) ckv = full[r];
+            else if (r < rsp.edge_rows[k]) { const float* rs = rsp.rs[k]; ckv = rsp.scale[k] * (rs ? rs[r] : 1.0f); }
+            else ckv = rsp.self_scale[k];
+            if (on == 2) {
+              // (the recomputed candidate holds both already: the host checks rsp.s[k] == gp.s and rsp.gate[k] == ys.p[k])
+              const Vec<VEC> sv = k == gp.k ? gsv : Vec<VEC>::load(rsp.s[k] + ro + off);
+              const Vec<VEC> ga = k == gp.k ? raw : Vec<VEC>::load(rsp.gate[k] + ro + off);
+              Vec<VEC> dzv, o2;
+              apply_gated<VEC>(o, ckv, sv, ga, dzv, o2);
+              const int af = rsp.add_from[k];
+              if (af >= 0) o2 = apply_sum<VEC>(o2, any.gy(af, r, ro, off, gv, gsv, live, &raw));
+              if (hasr && k == gp.k) apply_row_term<VEC>(o2, orv, rfv, dzr, guv);
+              o2.store(rsp.gs_out[k] + ro + off);
+              o = dzv;
+            } else {                                       // f_comp: dz = g * c
+              o = apply_scaled<VEC>(o, ckv);
             }
-            o.store(gys.p[k] + r * D + c * VEC);
           }
+          o.store(dst + ro + off);
         }
       }
     }
@@ -1315,21 +1481,51 @@ extern "C" int mrg_mix_bwd_apply(const float* g, const float* const* y_host, flo
   if (gp.rk >= 0 && gm.kmax != 1) return MRG_E_SHAPE;               // the row dot is one group_sum over the row's lanes
   size_t lds = (size_t)K * 6 * D * sizeof(float);
   if (lds > 64 * 1024) return MRG_E_SHAPE;
+  // Roles (see mix_bwd_apply_k).  resolved: every candidate is one of gated / row / add / other in a form the role kernel has.
+  ApplySlots slot{-1, -1, -1, {0, 0, 0, 0, 0}};
+  ApplyOthers<APPLY_NO> oth{};
+  int n_oth = 0;
+  const int G = gp.k, R = gp.rk, A = G >= 0 ? rsp.add_from[G] : -1;
+  bool resolved = K <= 5;
+  if (G >= 0) resolved = resolved && rsp.on[G] == 2 && rsp.full[G] && gy_host[G];     // recomputed AND folded (the host checked s / gate above)
+  if (A >= 0) resolved = resolved && gy_host[A] == nullptr;
+  for (int k = 0; k < K && resolved; ++k) {
+    if (k == G || k == R || k == A) continue;
+    if (rsp.on[k] == 2 || (rsp.on[k] == 1 && (!rsp.full[k] || G < 0))) resolved = false;
+    else if (gy_host[k]) {
+      slot.o[n_oth] = k;
+      oth.o[n_oth++] = ApplyOther{y_host[k], gy_host[k], rsp.on[k] ? rsp.full[k] : nullptr};
+    }
+  }
+  slot.g = G; slot.r = R; slot.a = A;
+  // (candidate 0 next to a gated role -- f_zero in the search space, absent here -- would need apply_gy's `first` in every role)
+  if (G >= 0 && (G == 0 || R == 0 || A == 0 || (n_oth > 0 && slot.o[0] == 0))) resolved = false;
+  // the instances the library's callers reach: a last-stage / tail MixedOp (no gated role), and the first stage with its row-factor
+  // candidate and folded f_identity (default), without the row factor (above 256 columns, or switched off), without the fold
+  const int layout = !resolved ? -1 : G < 0 ? 0 : (R >= 0 && A >= 0 && n_oth == 1) ? 1 : (R < 0 && A >= 0 && n_oth == 2) ? 2
+                                                  : (R >= 0 && A < 0 && n_oth == 2) ? 3 : -1;
+#define ROLE(V, L, KM, ACT, HG, HR, HA, NO)                                                                                        \
+  do {                                                                                                                             \
+    ApplyOthers<NO> o_{};                                                                                                          \
+    for (int i = 0; i < NO; ++i) o_.o[i] = oth.o[i];                                                                                \
+    hipLaunchKernelGGL((mix_bwd_apply_k<V, L, KM, ACT, HG, HR, HA, NO>), grid_, dim3(MRG_BLOCK), lds, st, g, coef, coef2, w, K, rows, D, \
+                       gp.vrows, slot, n_oth, o_, G >= 0 ? y_host[G] : nullptr, gp.s, gp.c, G >= 0 ? rsp.full[G] : nullptr,          \
+                       G >= 0 ? gy_host[G] : nullptr, G >= 0 ? rsp.gs_out[G] : nullptr, gp.rf, gp.rh, gp.uvc, gp.uld, gp.b0, gp.b1,    \
+                       gp.rdq);                                                                                                    \
+  } while (0)
 #define CALL(V, L, KM)                                                                                    \
   do {                                                                                                    \
     const dim3 grid_(mix_apply_grid(rows, L));                                                             \
-    if (gp.act == 1) {                                                                                    \
-      hipLaunchKernelGGL((mix_bwd_apply_k<V, L, KM, false, 5, 1>), grid_, dim3(MRG_BLOCK), lds, st, g, ys, gys, K, coef, coef2, w, rows, D, rsp, gp); \
-    } else if (gp.k >= 0 || gp.rk >= 0) {                                                                        \
-      if (K <= 5) hipLaunchKernelGGL((mix_bwd_apply_k<V, L, KM, true, 5>), grid_, dim3(MRG_BLOCK), lds, st, g, ys, gys, K, coef, coef2, w, rows, D, rsp, gp); \
-      else hipLaunchKernelGGL((mix_bwd_apply_k<V, L, KM, true, MRG_MIX_MAXK>), grid_, dim3(MRG_BLOCK), lds, st, g, ys, gys, K, coef, coef2, w, rows, D, rsp, gp); \
-    } else {                                                                                              \
-      if (K <= 5) hipLaunchKernelGGL((mix_bwd_apply_k<V, L, KM, false, 5>), grid_, dim3(MRG_BLOCK), lds, st, g, ys, gys, K, coef, coef2, w, rows, D, rsp, gp); \
-      else hipLaunchKernelGGL((mix_bwd_apply_k<V, L, KM, false, MRG_MIX_MAXK>), grid_, dim3(MRG_BLOCK), lds, st, g, ys, gys, K, coef, coef2, w, rows, D, rsp, gp); \
-    }                                                                                                     \
+    if (layout == 0 && gp.act == 1) ROLE(V, L, KM, 1, false, false, false, APPLY_NO);                      \
+    else if (layout == 0) ROLE(V, L, KM, 0, false, false, false, APPLY_NO);                                \
+    else if (layout == 2) ROLE(V, L, KM, 0, true, false, true, 2);                                         \
+    else if (layout == 1) ROLE(V, L, 1, 0, true, true, true, 1);          /* (a row role: KMAX == 1, checked above) */ \
+    else if (layout == 3) ROLE(V, L, 1, 0, true, true, false, 2);                                          \
+    else hipLaunchKernelGGL((mix_bwd_apply_any_k<V, L, KM>), grid_, dim3(MRG_BLOCK), lds, st, g, ys, gys, K, coef, coef2, w, rows, D, rsp, gp); \
   } while (0)
   MRG_DISPATCH_GEOM(gm, CALL);
 #undef CALL
+#undef ROLE
   MRG_LAUNCH_CHECK();
   return MRG_OK;
 }
