@@ -34,7 +34,7 @@
 extern "C" {
 #endif
 
-#define MRG_ABI_VERSION 20   /* 20: BatchNorm sums formed by a candidate's producer: mrg_gated_branch.given / given_n / given_stride (mrg_mix_stats_coef skips the sweep over such a candidate), mrg_dense_filter3_colsum_blocks, mrg_dense_filter_fwd3_colsum, mrg_gate_row_colsum_blocks, mrg_gate_row_fwd_colsum; 19: mrg_seg_std_workspace_bytes, mrg_seg_std_fwd, mrg_seg_std_bwd (a_std, the standard-deviation aggregator of the node-classification task); 18: mrg_conve_* (the ConvE feature path: BN0 statistics, conv, BN1, split-K fc and their gradients, stacked or interleaved image layout); 17: mrg_ccorr_rows, mrg_ccorr_matrix, mrg_ccorr_matrix_grad (standalone circular correlation: per-row kernel, and the circulant of a shared row with its gradient fold for the row GEMM); 16: mrg_set_stream_blocks, mrg_gate_collapse and mrg_gate_param_grad removed (the streaming grid bound is fixed; the three-segment forms remain); 15: mrg_gated_branch.valid_rows and the valid_rows argument of mrg_mix_finalize_bwd / mrg_zero_* except colstats (the device row count of a static step graph, passed per call instead of the process-wide registry of 13), mrg_linear_bwd_weight_share (the weight gradient of one range of a grouped launch, instead of the process-wide setter of 14); 14: mrg_clip_sgd_step, mrg_optim_chunk (clip_grad_norm_ + SGD with momentum over every parameter tensor in three launches), mrg_gated_branch.act (tanh behind the BatchNorm: CompGraphConv's tail on the epilogue kernels), mrg_gemm_set_small (few-row products on two-tile column blocks), a weight-gradient share setter, mrg_segmax_bwd_input (a_max's input gradient without a dense product); 13: a registry of device-side row counts (the sampled search step as one replayable HIP graph), mrg_seg_reduce_bwd_ordered (aggregator backward walked in destination order), mrg_gemm_set_q (the 16 x 16 x 32 row GEMM at three workgroups per CU for 129..224 output columns); 12: mrg_act_grad_transpose (the [B, N] scorer's output gradient, activation folded in, as [N, B] rows); 11: mrg_gemm_set_wide8 (eight-tile column block for D = 256); 10: mrg_gemm_set_epilogue(2) (transposed accumulators: a tested comparison point); 9: mrg_gated_branch (the MixedOp epilogue recomputes f_dense_comp's output from its gate and f_sparse_comp's from its row factor), mrg_gate_row_fwd / _bwd, mrg_sum_rows_gather, mrg_wgrad_set_variant, mrg_dense_filter_fwd3 out == NULL; 8: mrg_zero_* (cell-zero MixedOp recomputed from the tables), mrg_linear_bwd_input3_pair, mrg_sample_edge_neighborhood; 7: mrg_gemm_set_epilogue (row-order stores of the split-core row GEMM), mrg_set_stream_blocks, mrg_gemm_set_mode(2); 6: fused a_mean (run-sum epilogue, heads reducer, bit-mask backward), mrg_mix_stats_coef; 5: three-segment dense filter entry points; 4: mrg_linear_relu_segmax_fwd (fused a_max); 3: device graph / plan builders, samplers, [B, N] scorers, ranking; 2: GEMM workspaces, span_gcs ext_scal */
+#define MRG_ABI_VERSION 21   /* 21: mrg_adam_step (multi-tensor Adam over the pointer tables of mrg_clip_sgd_step, two launches; per-tensor step counts and lr in device memory); 20: BatchNorm sums formed by a candidate's producer: mrg_gated_branch.given / given_n / given_stride (mrg_mix_stats_coef skips the sweep over such a candidate), mrg_dense_filter3_colsum_blocks, mrg_dense_filter_fwd3_colsum, mrg_gate_row_colsum_blocks, mrg_gate_row_fwd_colsum; 19: mrg_seg_std_workspace_bytes, mrg_seg_std_fwd, mrg_seg_std_bwd (a_std, the standard-deviation aggregator of the node-classification task); 18: mrg_conve_* (the ConvE feature path: BN0 statistics, conv, BN1, split-K fc and their gradients, stacked or interleaved image layout); 17: mrg_ccorr_rows, mrg_ccorr_matrix, mrg_ccorr_matrix_grad (standalone circular correlation: per-row kernel, and the circulant of a shared row with its gradient fold for the row GEMM); 16: mrg_set_stream_blocks, mrg_gate_collapse and mrg_gate_param_grad removed (the streaming grid bound is fixed; the three-segment forms remain); 15: mrg_gated_branch.valid_rows and the valid_rows argument of mrg_mix_finalize_bwd / mrg_zero_* except colstats (the device row count of a static step graph, passed per call instead of the process-wide registry of 13), mrg_linear_bwd_weight_share (the weight gradient of one range of a grouped launch, instead of the process-wide setter of 14); 14: mrg_clip_sgd_step, mrg_optim_chunk (clip_grad_norm_ + SGD with momentum over every parameter tensor in three launches), mrg_gated_branch.act (tanh behind the BatchNorm: CompGraphConv's tail on the epilogue kernels), mrg_gemm_set_small (few-row products on two-tile column blocks), a weight-gradient share setter, mrg_segmax_bwd_input (a_max's input gradient without a dense product); 13: a registry of device-side row counts (the sampled search step as one replayable HIP graph), mrg_seg_reduce_bwd_ordered (aggregator backward walked in destination order), mrg_gemm_set_q (the 16 x 16 x 32 row GEMM at three workgroups per CU for 129..224 output columns); 12: mrg_act_grad_transpose (the [B, N] scorer's output gradient, activation folded in, as [N, B] rows); 11: mrg_gemm_set_wide8 (eight-tile column block for D = 256); 10: mrg_gemm_set_epilogue(2) (transposed accumulators: a tested comparison point); 9: mrg_gated_branch (the MixedOp epilogue recomputes f_dense_comp's output from its gate and f_sparse_comp's from its row factor), mrg_gate_row_fwd / _bwd, mrg_sum_rows_gather, mrg_wgrad_set_variant, mrg_dense_filter_fwd3 out == NULL; 8: mrg_zero_* (cell-zero MixedOp recomputed from the tables), mrg_linear_bwd_input3_pair, mrg_sample_edge_neighborhood; 7: mrg_gemm_set_epilogue (row-order stores of the split-core row GEMM), mrg_set_stream_blocks, mrg_gemm_set_mode(2); 6: fused a_mean (run-sum epilogue, heads reducer, bit-mask backward), mrg_mix_stats_coef; 5: three-segment dense filter entry points; 4: mrg_linear_relu_segmax_fwd (fused a_max); 3: device graph / plan builders, samplers, [B, N] scorers, ranking; 2: GEMM workspaces, span_gcs ext_scal */
 
 #define MRG_OK            0
 #define MRG_E_NULLPTR    -1   /* a required pointer is NULL */
@@ -307,11 +307,27 @@ int64_t mrg_mix_workspace_bytes(int K, int D);
  * tensor (and its momentum buffer) untouched, like torch's skip of parameters without a gradient.  Momentum buffers start at zero
  * (torch initialises buf = g on the first step: the same value).  The tensors are cut into chunks of mrg_optim_chunk() elements by
  * the caller: chunk b covers elements [chunk_off[b], chunk_off[b] + chunk_len[b]) of tensor chunk_tensor[b] (device arrays; shapes
- * never change, so they are built once).  partial: n_chunks doubles of workspace.  Deterministic. */
+ * never change, so they are built once).  partial: n_chunks doubles of workspace.  Deterministic.  MRG_E_NULLPTR for a missing
+ * table, MRG_E_SHAPE for more than 2^31 - 1 chunks. */
 int mrg_optim_chunk(void);
 int mrg_clip_sgd_step(void *const *params, const void *const *grads, void *const *bufs, const int32_t *chunk_tensor,
                       const int64_t *chunk_off, const int32_t *chunk_len, int64_t n_chunks, double *partial, float *norm_coef,
                       float max_norm, float lr, float momentum, float weight_decay, void *stream);
+/* ABI 21.  torch.optim.Adam(betas, eps, weight_decay, amsgrad False, maximize False).step() (the reference's architect,
+ * models/architect_lp.py:20-22, and its training driver, train/mr_lp_train.py:140) over ALL tensors of a parameter list in two
+ * launches, through the pointer tables and chunks of mrg_clip_sgd_step (exp_avg / exp_avg_sq: DEVICE arrays of n_tensors pointers).
+ *   tick (one thread per tensor with a gradient): s = ++step[t];  scal[2t] = lr[0] / (1 - beta1^s);  scal[2t+1] = 1 / sqrt(1 - beta2^s)
+ *        -- formed in double.  step [n_tensors] float32 (torch's state['step']), scal [n_tensors][2] float32, lr [1] float32: DEVICE
+ *        memory, so a step captured into a HIP graph advances its own bias correction on every replay and follows a schedule.
+ *   update (one chunk per workgroup): g += weight_decay * p;  m = beta1 m + (1 - beta1) g;  v = beta2 v + (1 - beta2) g^2;
+ *        p -= scal[2t] * m / (sqrt(v) * scal[2t+1] + eps).
+ * Step counts are per tensor, as torch's are per parameter: a tensor with a null gradient pointer is left untouched -- parameter,
+ * moments and count -- and lags behind the others afterwards.  A chunk whose four addresses are 16-byte aligned is read and written
+ * 16 bytes per lane (pad each tensor's moment slot to a multiple of 64 elements), any other chunk and every tail 4 bytes per lane.
+ * Nothing to do (n_chunks or n_tensors <= 0): MRG_OK.  MRG_E_NULLPTR, MRG_E_SHAPE (a count beyond 2^31 - 1).  Deterministic. */
+int mrg_adam_step(void *const *params, const void *const *grads, void *const *exp_avg, void *const *exp_avg_sq, int64_t n_tensors,
+                  const int32_t *chunk_tensor, const int64_t *chunk_off, const int32_t *chunk_len, int64_t n_chunks, float *step,
+                  float *scal, const float *lr, double beta1, double beta2, float eps, float weight_decay, void *stream);
 /* `gated` (HOST pointer, NULL or k < 0 = none) of the five entry points that read the candidates: candidate k is the gated
  * filter f_dense_op_comp (reference models/operations_lp.py:356-390) and is NOT stored -- y_host[k] holds its gate
  * sigmoid(W [s ; s_in] + b) (mrg_dense_filter_fwd3 with out == NULL) and its value is recomputed wherever it is read as
