@@ -34,7 +34,7 @@
 extern "C" {
 #endif
 
-#define MRG_ABI_VERSION 21   /* 21: mrg_adam_step (multi-tensor Adam over the pointer tables of mrg_clip_sgd_step, two launches; per-tensor step counts and lr in device memory); 20: BatchNorm sums formed by a candidate's producer: mrg_gated_branch.given / given_n / given_stride (mrg_mix_stats_coef skips the sweep over such a candidate), mrg_dense_filter3_colsum_blocks, mrg_dense_filter_fwd3_colsum, mrg_gate_row_colsum_blocks, mrg_gate_row_fwd_colsum; 19: mrg_seg_std_workspace_bytes, mrg_seg_std_fwd, mrg_seg_std_bwd (a_std, the standard-deviation aggregator of the node-classification task); 18: mrg_conve_* (the ConvE feature path: BN0 statistics, conv, BN1, split-K fc and their gradients, stacked or interleaved image layout); 17: mrg_ccorr_rows, mrg_ccorr_matrix, mrg_ccorr_matrix_grad (standalone circular correlation: per-row kernel, and the circulant of a shared row with its gradient fold for the row GEMM); 16: mrg_set_stream_blocks, mrg_gate_collapse and mrg_gate_param_grad removed (the streaming grid bound is fixed; the three-segment forms remain); 15: mrg_gated_branch.valid_rows and the valid_rows argument of mrg_mix_finalize_bwd / mrg_zero_* except colstats (the device row count of a static step graph, passed per call instead of the process-wide registry of 13), mrg_linear_bwd_weight_share (the weight gradient of one range of a grouped launch, instead of the process-wide setter of 14); 14: mrg_clip_sgd_step, mrg_optim_chunk (clip_grad_norm_ + SGD with momentum over every parameter tensor in three launches), mrg_gated_branch.act (tanh behind the BatchNorm: CompGraphConv's tail on the epilogue kernels), mrg_gemm_set_small (few-row products on two-tile column blocks), a weight-gradient share setter, mrg_segmax_bwd_input (a_max's input gradient without a dense product); 13: a registry of device-side row counts (the sampled search step as one replayable HIP graph), mrg_seg_reduce_bwd_ordered (aggregator backward walked in destination order), mrg_gemm_set_q (the 16 x 16 x 32 row GEMM at three workgroups per CU for 129..224 output columns); 12: mrg_act_grad_transpose (the [B, N] scorer's output gradient, activation folded in, as [N, B] rows); 11: mrg_gemm_set_wide8 (eight-tile column block for D = 256); 10: mrg_gemm_set_epilogue(2) (transposed accumulators: a tested comparison point); 9: mrg_gated_branch (the MixedOp epilogue recomputes f_dense_comp's output from its gate and f_sparse_comp's from its row factor), mrg_gate_row_fwd / _bwd, mrg_sum_rows_gather, mrg_wgrad_set_variant, mrg_dense_filter_fwd3 out == NULL; 8: mrg_zero_* (cell-zero MixedOp recomputed from the tables), mrg_linear_bwd_input3_pair, mrg_sample_edge_neighborhood; 7: mrg_gemm_set_epilogue (row-order stores of the split-core row GEMM), mrg_set_stream_blocks, mrg_gemm_set_mode(2); 6: fused a_mean (run-sum epilogue, heads reducer, bit-mask backward), mrg_mix_stats_coef; 5: three-segment dense filter entry points; 4: mrg_linear_relu_segmax_fwd (fused a_max); 3: device graph / plan builders, samplers, [B, N] scorers, ranking; 2: GEMM workspaces, span_gcs ext_scal */
+#define MRG_ABI_VERSION 22   /* 22: mrg_cand_linear_fwd, mrg_cand_linear_bwd_input, mrg_cand_linear_colsum_blocks, mrg_cand_linear_workspace_bytes (the candidate Linears of one node-classification MixedOp in one launch, BatchNorm sums included); 21: mrg_adam_step (multi-tensor Adam over the pointer tables of mrg_clip_sgd_step, two launches; per-tensor step counts and lr in device memory); 20: BatchNorm sums formed by a candidate's producer: mrg_gated_branch.given / given_n / given_stride (mrg_mix_stats_coef skips the sweep over such a candidate), mrg_dense_filter3_colsum_blocks, mrg_dense_filter_fwd3_colsum, mrg_gate_row_colsum_blocks, mrg_gate_row_fwd_colsum; 19: mrg_seg_std_workspace_bytes, mrg_seg_std_fwd, mrg_seg_std_bwd (a_std, the standard-deviation aggregator of the node-classification task); 18: mrg_conve_* (the ConvE feature path: BN0 statistics, conv, BN1, split-K fc and their gradients, stacked or interleaved image layout); 17: mrg_ccorr_rows, mrg_ccorr_matrix, mrg_ccorr_matrix_grad (standalone circular correlation: per-row kernel, and the circulant of a shared row with its gradient fold for the row GEMM); 16: mrg_set_stream_blocks, mrg_gate_collapse and mrg_gate_param_grad removed (the streaming grid bound is fixed; the three-segment forms remain); 15: mrg_gated_branch.valid_rows and the valid_rows argument of mrg_mix_finalize_bwd / mrg_zero_* except colstats (the device row count of a static step graph, passed per call instead of the process-wide registry of 13), mrg_linear_bwd_weight_share (the weight gradient of one range of a grouped launch, instead of the process-wide setter of 14); 14: mrg_clip_sgd_step, mrg_optim_chunk (clip_grad_norm_ + SGD with momentum over every parameter tensor in three launches), mrg_gated_branch.act (tanh behind the BatchNorm: CompGraphConv's tail on the epilogue kernels), mrg_gemm_set_small (few-row products on two-tile column blocks), a weight-gradient share setter, mrg_segmax_bwd_input (a_max's input gradient without a dense product); 13: a registry of device-side row counts (the sampled search step as one replayable HIP graph), mrg_seg_reduce_bwd_ordered (aggregator backward walked in destination order), mrg_gemm_set_q (the 16 x 16 x 32 row GEMM at three workgroups per CU for 129..224 output columns); 12: mrg_act_grad_transpose (the [B, N] scorer's output gradient, activation folded in, as [N, B] rows); 11: mrg_gemm_set_wide8 (eight-tile column block for D = 256); 10: mrg_gemm_set_epilogue(2) (transposed accumulators: a tested comparison point); 9: mrg_gated_branch (the MixedOp epilogue recomputes f_dense_comp's output from its gate and f_sparse_comp's from its row factor), mrg_gate_row_fwd / _bwd, mrg_sum_rows_gather, mrg_wgrad_set_variant, mrg_dense_filter_fwd3 out == NULL; 8: mrg_zero_* (cell-zero MixedOp recomputed from the tables), mrg_linear_bwd_input3_pair, mrg_sample_edge_neighborhood; 7: mrg_gemm_set_epilogue (row-order stores of the split-core row GEMM), mrg_set_stream_blocks, mrg_gemm_set_mode(2); 6: fused a_mean (run-sum epilogue, heads reducer, bit-mask backward), mrg_mix_stats_coef; 5: three-segment dense filter entry points; 4: mrg_linear_relu_segmax_fwd (fused a_max); 3: device graph / plan builders, samplers, [B, N] scorers, ranking; 2: GEMM workspaces, span_gcs ext_scal */
 
 #define MRG_OK            0
 #define MRG_E_NULLPTR    -1   /* a required pointer is NULL */
@@ -775,6 +775,28 @@ int mrg_conve_finish_bwd(int layout, const float *sub, const float *rel, int64_t
  * (functional._Linear.backward; replaces torch's mul / rsub / mul / strided copy).  act: MRG_ACT_NONE (y may be NULL) / _RELU /
  * _SIGMOID, y = the forward's output.  B <= 64 * 65535. */
 int mrg_act_grad_transpose(const float *g, const float *y, float *gT, int64_t B, int64_t N, int act, void *stream);
+
+/* ---- the candidate Linears of one node-classification MixedOp ------------------------------------
+ * MixedOp.__init__ / op_forward   reference models/cell.py:17-31: every candidate k of a MixedOp carries its own
+ * nn.Linear(D, D, bias=True) between the operator and the BatchNorm.  One launch serves n <= 4 candidates ("members") of the same
+ * rows and the same square D:   Y[k] = X[k] W[k]^T + bias[k]   (mrg_cand_linear_fwd)   gX[k] = gY[k] W[k]   (mrg_cand_linear_bwd_input,
+ * the same product with the weight read through transposed strides, no bias).  X / W / bias / Y: HOST arrays of n device pointers
+ * (bias, or any of its entries, may be NULL; two members may read the same X; the outputs are distinct), X[k], Y[k]: [rows][D],
+ * W[k]: [D][D], all 16-byte aligned.  Exact-f32 matrix core (v_mfma_f32_32x32x2_f32), the weight staged in LDS: no global
+ * workspace -- mrg_cand_linear_workspace_bytes(n, D) is 0 for every shape of this core, and ws may then be NULL
+ * (MRG_E_WORKSPACE when it returns > 0 and ws is NULL).  Shapes: D % 4 == 0 and 16 <= D <= 128, any rows >= 0; another D, or a
+ * pointer that is not 16-byte aligned: MRG_E_SHAPE (the caller runs mrg_linear_fwd / mrg_linear_bwd_input per member).
+ * colsum (reference models/cell.py:19, the BatchNorm1d that reads Y[k]): NULL, or [n][blocks][2 (sum, sum of squares)][D] float64,
+ * the column sums of the float32 values stored in Y[k], one partial per workgroup formed from the registers that hold the output
+ * and added in a fixed order (no atomics) -- the layout of mrg_gated_branch.given with given_n = blocks, given_stride = 2 D.
+ * blocks = mrg_cand_linear_colsum_blocks(rows, D), 0 = the shape has no grouped form; colsum_blocks: what the caller sized
+ * colsum for (MRG_E_SHAPE when the launch would write another number).  Y is the same bits with and without colsum. */
+int64_t mrg_cand_linear_colsum_blocks(int64_t rows, int D);
+int64_t mrg_cand_linear_workspace_bytes(int n, int D);
+int mrg_cand_linear_fwd(int n, const float *const *X, const float *const *W, const float *const *bias, float *const *Y, void *ws,
+                        int64_t rows, int D, void *stream, double *colsum, int64_t colsum_blocks);
+int mrg_cand_linear_bwd_input(int n, const float *const *gY, const float *const *W, float *const *gX, void *ws, int64_t rows, int D,
+                              void *stream);
 
 #ifdef __cplusplus
 }

@@ -14,7 +14,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("MRG_LIB_PATH") or os.path.join(_HERE, "lib", "libmrgnas_hip.so")     # MRG_LIB_PATH: lab builds of the same ABI
 HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "mrgnas.h")
 
-ABI_VERSION = 21
+ABI_VERSION = 22
 
 
 class MrgnasLibraryError(RuntimeError):
@@ -138,6 +138,10 @@ SIGNATURES = {
     "mrg_conve_bn1_bwd": (_I, [_P, _P, _P, _P, _P, _P, _I, _L, _I, _I, _P, _P, _P]),
     "mrg_conve_conv_bwd": (_I, [_I, _P, _P, _L, _I, _I, _I, _P, _P, _P, _P, _I, _I, _P, _P, _P]),
     "mrg_conve_finish_bwd": (_I, [_I, _P, _P, _L, _I, _I, _I, _P, _P, _I, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "mrg_cand_linear_colsum_blocks": (_L, [_L, _I]),
+    "mrg_cand_linear_workspace_bytes": (_L, [_I, _I]),
+    "mrg_cand_linear_fwd": (_I, [_I, _P, _P, _P, _P, _P, _L, _I, _P, _P, _L]),
+    "mrg_cand_linear_bwd_input": (_I, [_I, _P, _P, _P, _P, _L, _I, _P]),
 }
 
 _lib = None

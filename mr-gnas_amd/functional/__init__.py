@@ -22,6 +22,7 @@ This package re-exports every name of its modules, so callers keep writing ``fro
   ccorr       Standalone circular correlation ccorr(a, b): per-row kernel, or a shared row's circulant on the row GEMM (csrc/ccorr.hip).
   conve       ConvE feature path: BN0 -> conv -> BN1 -> ReLU -> fc of the (subject, relation) image, and the ConvE scorer (csrc/conve.hip).
   nc          Node-classification aggregators on a block: a_std (csrc/segstd.hip) and a_sum / a_mean / a_max without self rows.
+  cand_linear The candidate Linears of one node-classification MixedOp in one launch, BatchNorm sums included (csrc/cand_linear.hip).
 """
 from . import switches                                   # noqa: F401
 from ._base import (  # noqa: F401
@@ -72,5 +73,8 @@ from .conve import (  # noqa: F401
 )
 from .nc import (  # noqa: F401
     _SegStd, aggregate_std, inv_in_degree, aggregate_nc, linear_relu_aggregate_nc,
+)
+from .cand_linear import (  # noqa: F401
+    _CandLinears, _BiasRows, candidate_linears, constant_candidate,
 )
 from .._lib import ptr_array, call, f32c, ptr, require_hip, stream_of   # noqa: F401  (part of the module's historical surface)

@@ -29,6 +29,9 @@ GATED_RECOMPUTE = os.environ.get("MRG_GATED_RECOMPUTE", "1") == "1"     # lab sw
 PRODUCER_STATS = os.environ.get("MRG_PRODUCER_STATS", "1") == "1"
 COMPGCN_TAIL = os.environ.get("MRG_COMPGCN_TAIL", "1") == "1"     # lab switch: 0 = CompGraphConv's BatchNorm -> tanh tail on torch kernels
 SPARSE_AMAX_BWD = os.environ.get("MRG_SPARSE_AMAX_BWD", "1") == "1"   # lab switch: 0 = a_max's input gradient as seg_bwd_k + the dense row GEMM
+# lab switch: 0 = the candidate Linears of a node-classification MixedOp run one mrg_linear_fwd / mrg_linear_bwd_input per candidate instead
+# of one grouped launch per MixedOp (functional/cand_linear.py), and their BatchNorm sums come from the statistics pass
+CAND_LINEAR_GROUP = os.environ.get("MRG_CAND_LINEAR_GROUP", "1") == "1"
 # ccorr (functional/ccorr.py): None = a shared row takes the matrix path from ccorr.MATRIX_MIN_ROWS rows on; "rows" / "matrix" force
 # one path wherever the matrix path applies (tests cross-check the two with monkeypatch.setattr).  A plain attribute, no variable.
 CCORR_PATH = None
