@@ -693,6 +693,36 @@ int mrg_relabel_nodes(const int64_t *src, const int64_t *dst, int64_t n, int64_t
 int mrg_multi_hot_labels(const int64_t *keys, const int32_t *rowptr, const int32_t *objs, const int64_t *query,
                          int64_t B, int64_t U, int64_t num_ent, float v_zero, float v_one, float *out, void *stream);
 
+/* ---- node-classification blocks with per-layer fan-outs (sampler.NeighborSampler, csrc/blocks.hip) ------------------
+ * One layer of one minibatch from a RESIDENT in-edge index of the graph: rowptr [N + 1] over destinations, in_eid / in_src /
+ * in_type [E_graph] = edge id, global source and type of the in-edges in stable destination order (edge ids ascending inside a
+ * destination; in_type may be NULL with etype NULL).  dst_nodes [n_dst] int64: the layer's destinations (unique; an id outside
+ * [0, N) has no edges and is never used as an index).  k: the fan-out, 0 = every in-edge, else 1..64 (another k: MRG_E_SHAPE).
+ * No launch or memset of these entry points grows with N or E_graph: the work is O(n_dst max(k, 1) + E).
+ *   mrg_block_sizes: first [n_dst + 1] = exclusive sums of cnt[i] = min(deg(dst_nodes[i]), k) (deg when k == 0);
+ *     first[n_dst] = E, which the caller reads.  ws: mrg_block_sizes_workspace_bytes(n_dst).
+ *   mrg_block_emit: the block's E edges, grouped by destination in destination order, edge ids ascending inside one: eid / etype /
+ *     ldst [E] int64 (etype may be NULL), gsrc [E] int32 = the global sources.  A destination with deg <= k (or k == 0) keeps its
+ *     whole in-list; one with deg > k keeps the k positions that Floyd's algorithm picks from its row of u [n_dst][k] (float64 in
+ *     [0, 1)): for i = 0 .. k - 1, j = deg - k + i, t = min(floor(u_i (j + 1)), j), pick j if t is already picked, else t.
+ *     Also enters the layer into the tables: local[dst_nodes[i]] = i, firstpos[s] = the lowest block edge with source s.
+ *   mrg_block_relabel: src_nodes [n_dst + E] int64 = dst_nodes, then the n_new sources that are no destination in the order of
+ *     their first edge (entries past n_dst + n_new are not written); lsrc [E] int64 = every edge's index into it; n_new [1]
+ *     (device).  Restores both tables at the entries mrg_block_emit touched.  ws: mrg_block_relabel_workspace_bytes(E).
+ * local / firstpos [N] int32 are the caller's: -1 / INT32_MAX everywhere before mrg_block_emit and again after mrg_block_relabel;
+ * the three calls of a layer go to ONE stream, in this order, and one pair of tables serves one stream at a time.
+ * n_dst == 0 or E == 0: MRG_OK, nothing launched (and the tables untouched).  Integer atomics only; deterministic.
+ * MRG_E_NULLPTR, MRG_E_SHAPE (a negative size, k outside 0..64, n_dst + E beyond 2^31 - 2), MRG_E_WORKSPACE. */
+int64_t mrg_block_sizes_workspace_bytes(int64_t n_dst);
+int mrg_block_sizes(const int32_t *rowptr, const int64_t *dst_nodes, int64_t n_dst, int64_t N, int k, int32_t *first, void *ws,
+                    int64_t ws_bytes, void *stream);
+int mrg_block_emit(const int32_t *rowptr, const int32_t *in_eid, const int32_t *in_src, const int32_t *in_type,
+                   const int64_t *dst_nodes, const int32_t *first, int64_t n_dst, int64_t N, int k, const double *u, int64_t E,
+                   int64_t *eid, int64_t *etype, int64_t *ldst, int32_t *gsrc, int32_t *local, int32_t *firstpos, void *stream);
+int64_t mrg_block_relabel_workspace_bytes(int64_t E);
+int mrg_block_relabel(const int32_t *gsrc, const int64_t *dst_nodes, int64_t n_dst, int64_t N, int64_t E, int32_t *local,
+                      int32_t *firstpos, int64_t *src_nodes, int64_t *lsrc, int32_t *n_new, void *ws, int64_t ws_bytes, void *stream);
+
 /* ---- f3: filtered ranking and the [B, N] score functions ---------------------------------------------
  * predict(), reference train/mr_lp_train.py:290-299: entries with a non-zero label are pushed to -1e7, the target keeps
  * its score; ranks[b] = 1 + #(greater) + #(equal at a lower index)  (the position in a stable descending sort). */

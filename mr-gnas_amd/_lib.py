@@ -142,6 +142,11 @@ SIGNATURES = {
     "mrg_cand_linear_workspace_bytes": (_L, [_I, _I]),
     "mrg_cand_linear_fwd": (_I, [_I, _P, _P, _P, _P, _P, _L, _I, _P, _P, _L]),
     "mrg_cand_linear_bwd_input": (_I, [_I, _P, _P, _P, _P, _L, _I, _P]),
+    "mrg_block_sizes_workspace_bytes": (_L, [_L]),
+    "mrg_block_sizes": (_I, [_P, _P, _L, _L, _I, _P, _P, _L, _P]),
+    "mrg_block_emit": (_I, [_P, _P, _P, _P, _P, _P, _L, _L, _I, _P, _L, _P, _P, _P, _P, _P, _P, _P]),
+    "mrg_block_relabel_workspace_bytes": (_L, [_L]),
+    "mrg_block_relabel": (_I, [_P, _P, _L, _L, _L, _P, _P, _P, _P, _P, _P, _L, _P]),
 }
 
 _lib = None

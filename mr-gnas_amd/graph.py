@@ -498,7 +498,10 @@ class Block(RelGraph):
     Edges run from ``n_src`` source rows to ``n_dst`` destination rows; ``src`` / ``dst`` are LOCAL indices.  The graph's node
     count, ``number_of_nodes()``, is ``n_dst``: what the aggregator kernels size their [n_dst, D] output by.  ``srcdata`` and
     ``dstdata`` are separate frames, each holding the global node ids under ``NID``; ``ndata`` is ``dstdata``.  ``edata`` holds
-    the global edge ids (int64) under ``EID`` and the relation types under ``ETYPE``."""
+    the global edge ids (int64) under ``EID`` and the relation types under ``ETYPE``.  ``draws``: the uniforms a sampled block
+    was picked from (sampler.NeighborSampler), None otherwise."""
+
+    draws = None
 
     def __init__(self, src_nodes, dst_nodes, src, dst, eid, etype=None):
         super().__init__(int(dst_nodes.numel()), src, dst, device=dst_nodes.device)
@@ -545,6 +548,7 @@ class Block(RelGraph):
         b.edata.update({k: v.to(device) for k, v in self.edata.items()})
         b._srcdata.update({k: v.to(device) for k, v in self._srcdata.items()})
         b._dstdata.update({k: v.to(device) for k, v in self._dstdata.items()})
+        b.draws = None if self.draws is None else self.draws.to(device)
         return b
 
 

@@ -12,6 +12,9 @@ possible across generators), but every function takes the draws as optional argu
 reference for the same draws -- that is what the tests replay.  The neighbourhood-expansion sampler
 (``sample_edge_neighborhood``, utils_rgcn.py:30-71, ``--edge_sampler neighbor``) is ``sample_size`` dependent picks: one
 launch of one persistent workgroup (``mrg_sample_edge_neighborhood``) over an adjacency CSR in the reference's append order.
+
+Node classification: ``full_neighbor_blocks`` (torch ops, every in-edge) and ``NeighborSampler`` (per-layer fan-outs over a resident
+in-edge index; the kernels of ``csrc/blocks.hip``) build the blocks of a minibatch.
 """
 import numpy as np
 import torch
@@ -278,3 +281,166 @@ def full_neighbor_blocks(graph, seeds, num_layers):
         blocks.append(G.Block(src_nodes, dst_nodes, local[s], ldst, eid, etype[eid].long() if etype is not None else None))
         dst_nodes = src_nodes
     return blocks[::-1]
+
+
+MAX_FANOUT = 64          # csrc/blocks.hip: one lane of a wave per pick
+_I32_MAX = 2 ** 31 - 1
+
+
+def _check_fanout(f):
+    """None (every in-edge; -1 says the same) or the integer fan-out 1..MAX_FANOUT."""
+    if f is None:
+        return None
+    if isinstance(f, bool) or not isinstance(f, (int, np.integer)):
+        raise ValueError(f"a fan-out is None, -1 or an integer in 1..{MAX_FANOUT}, got {f!r}")
+    f = int(f)
+    if f == -1:
+        return None
+    if not 1 <= f <= MAX_FANOUT:
+        raise ValueError(f"a fan-out is None, -1 or an integer in 1..{MAX_FANOUT} (the limit is {MAX_FANOUT}), got {f}")
+    return f
+
+
+class NeighborSampler:
+    """DGL's ``MultiLayerNeighborSampler(fanouts, return_eids=True)`` (reference search/mr_nc_search.py:39-44, 231: ``--fanout``)
+    over a resident in-edge index of ``graph``: ``sample(seeds)`` returns the blocks of a minibatch, outermost first, with the
+    conventions of ``full_neighbor_blocks`` (destinations of the last block = ``seeds`` in order; block j's destinations = block
+    j + 1's sources; sources = destinations first, then new sources in order of first appearance over the edge list; edges grouped
+    by destination in destination order, edge ids ascending within one; ``EID`` / ``ETYPE`` / ``NID`` filled).
+
+    ``fanouts[j]`` belongs to ``blocks[j]`` (DGL's order: the last entry is the seeds' block).  ``None`` / ``-1``: every in-edge.
+    An integer k in 1..64: a destination of in-degree d <= k keeps all its in-edges, one with d > k a uniformly random k-subset
+    of the positions 0..d-1 of its in-list (ascending edge id), chosen by Floyd's algorithm from its row of uniforms ``u[v, 0..k-1]``
+    (float64 in [0, 1)): for i = 0..k-1, j = d - k + i, t = min(floor(u_i (j + 1)), j); pick j when t is already picked, else t.
+    Layers are processed from the seeds outwards and every integer layer draws ONE ``torch.rand((n_dst, k), dtype=float64)`` from
+    ``generator`` (rows of destinations with d <= k are drawn and ignored: the stream depends on shapes only); the tensor stays on
+    the block as ``block.draws``.  ``draws=[...]`` (aligned with ``fanouts``; None for a full layer) replays a run.
+
+    The index (rowptr over destinations; edge ids, sources and types in stable destination order) and two [N] int32 scratch tables
+    are built once, on ``graph.device``.  On a HIP graph a layer is three entry points of csrc/blocks.hip (mrg_block_sizes,
+    mrg_block_emit, mrg_block_relabel) and two host reads of sizes; nothing per call grows with the graph.  CPU graphs run the torch
+    formulation of the same function.  Preconditions: ``seeds`` are unique node ids.  The scratch tables are shared by all calls:
+    a sampler object is used from ONE stream at a time."""
+
+    def __init__(self, graph, fanouts):
+        self.fanouts = [_check_fanout(f) for f in fanouts]
+        dev = self.device = graph.device
+        N = self.N = graph.number_of_nodes()
+        gsrc, gdst = graph.edges()
+        gsrc, gdst = gsrc.long(), gdst.long()
+        E = int(gsrc.numel())
+        if E > _I32_MAX - 1 or N > _I32_MAX - 1:
+            raise ValueError("NeighborSampler indexes nodes and edges with int32")
+        if E and not (0 <= int(torch.minimum(gsrc.min(), gdst.min())) and int(torch.maximum(gsrc.max(), gdst.max())) < N):
+            raise ValueError("NeighborSampler: an edge endpoint lies outside [0, number_of_nodes())")
+        etype = _edge_types(graph)
+        order = torch.argsort(gdst, stable=True)                         # edge ids by destination, ascending within one
+        deg = torch.zeros(N, dtype=torch.long, device=dev).scatter_add_(0, gdst, torch.ones_like(gdst))
+        rowptr = torch.zeros(N + 1, dtype=torch.long, device=dev)
+        rowptr[1:] = torch.cumsum(deg, 0)
+        i32 = lambda t: t.to(torch.int32).contiguous()
+        self.rowptr, self.in_eid, self.in_src = i32(rowptr), i32(order), i32(gsrc[order])
+        self.in_type = i32(etype[order]) if etype is not None else None
+        self.local = torch.full((N,), -1, dtype=torch.int32, device=dev)            # -1 everywhere between calls
+        self.firstpos = torch.full((N,), _I32_MAX, dtype=torch.int32, device=dev)   # INT32_MAX everywhere between calls
+        self._hip = G._hip_ready(gsrc)
+        G.settle(dev)
+
+    def sample(self, seeds, generator=None, draws=None):
+        dev, L = self.device, len(self.fanouts)
+        if draws is not None and len(draws) != L:
+            raise ValueError(f"draws needs one entry per fan-out ({L}), got {len(draws)}")
+        dst_nodes = torch.as_tensor(seeds, device=dev).long().reshape(-1).contiguous()
+        layer = self._layer_hip if self._hip else self._layer_torch
+        blocks = []
+        for j in reversed(range(L)):
+            k, n_dst, u = self.fanouts[j], int(dst_nodes.numel()), None
+            if k is not None and draws is None:
+                u = torch.rand((n_dst, k), dtype=torch.float64, device=dev, generator=generator)
+            elif k is not None:
+                u = draws[j]
+                if not torch.is_tensor(u) or u.dtype != torch.float64 or tuple(u.shape) != (n_dst, k):
+                    raise ValueError(f"draws[{j}] must be a float64 tensor of shape ({n_dst}, {k}), got "
+                                     + (f"{u.dtype} {tuple(u.shape)}" if torch.is_tensor(u) else repr(type(u))))
+                u = u.to(dev).contiguous()
+            elif draws is not None and draws[j] is not None:
+                raise ValueError(f"draws[{j}] must be None: layer {j} takes every in-edge")
+            try:
+                blk = layer(dst_nodes, k, u)
+            except Exception:
+                self.local.fill_(-1)                                          # a failed layer may have left its entries behind
+                self.firstpos.fill_(_I32_MAX)
+                raise
+            blk.draws = u
+            blocks.append(blk)
+            dst_nodes = blk.srcdata[G.NID]
+        return blocks[::-1]
+
+    def _layer_hip(self, dst_nodes, k, u):
+        dev, N, n_dst, k = self.device, self.N, int(dst_nodes.numel()), int(k or 0)
+        lib, st = load(), stream_of(dst_nodes)
+        i64 = lambda n: torch.empty(int(n), dtype=torch.int64, device=dev)
+        E = 0
+        if n_dst:
+            first = torch.empty(n_dst + 1, dtype=torch.int32, device=dev)
+            nb = lib.mrg_block_sizes_workspace_bytes(n_dst)
+            ws = torch.empty(max(nb, 16), dtype=torch.uint8, device=dev)
+            call("mrg_block_sizes", (ptr(self.rowptr), ptr(dst_nodes), n_dst, N, k, ptr(first), ptr(ws), nb, st))
+            E = int(first[n_dst])                                             # host read 1
+            if E < 0:
+                raise ValueError("NeighborSampler: the block has more than 2^31 - 1 edges (are the seeds unique?)")
+        eid, ldst, lsrc = i64(E), i64(E), i64(E)
+        etype = i64(E) if self.in_type is not None else None
+        if E == 0:
+            return G.Block(dst_nodes, dst_nodes, lsrc, ldst, eid, etype)
+        gsrc = torch.empty(E, dtype=torch.int32, device=dev)
+        src_nodes = i64(n_dst + E)
+        n_new = torch.empty(1, dtype=torch.int32, device=dev)
+        nb = lib.mrg_block_relabel_workspace_bytes(E)
+        ws = torch.empty(max(nb, 16), dtype=torch.uint8, device=dev)
+        call("mrg_block_emit", (ptr(self.rowptr), ptr(self.in_eid), ptr(self.in_src), ptr(self.in_type), ptr(dst_nodes), ptr(first), n_dst, N, k,
+                                ptr(u), E, ptr(eid), ptr(etype), ptr(ldst), ptr(gsrc), ptr(self.local), ptr(self.firstpos), st))
+        call("mrg_block_relabel", (ptr(gsrc), ptr(dst_nodes), n_dst, N, E, ptr(self.local), ptr(self.firstpos), ptr(src_nodes), ptr(lsrc),
+                                   ptr(n_new), ptr(ws), nb, st))
+        src_nodes = src_nodes[: n_dst + int(n_new)]                            # host read 2
+        return G.Block(src_nodes, dst_nodes, lsrc, ldst, eid, etype)
+
+    def _layer_torch(self, dst_nodes, k, u):
+        """The same function in torch ops; like the kernels it touches the two tables at the block's nodes only."""
+        dev, n_dst = self.device, int(dst_nodes.numel())
+        if n_dst and not (0 <= int(dst_nodes.min()) and int(dst_nodes.max()) < self.N):
+            raise ValueError("NeighborSampler: a seed lies outside [0, number_of_nodes())")
+        r0 = self.rowptr[dst_nodes].long()
+        d = self.rowptr[dst_nodes + 1].long() - r0
+        if k is None:
+            E = int(d.sum())
+            ldst = torch.repeat_interleave(torch.arange(n_dst, device=dev), d, output_size=E)
+            pos = torch.arange(E, device=dev) - (torch.cumsum(d, 0) - d)[ldst] + r0[ldst]
+        else:
+            pick = torch.arange(k, device=dev).repeat(n_dst, 1)              # d <= k: positions 0..d-1
+            big = d > k
+            if bool(big.any()):                                                # Floyd's k picks, every large destination at once
+                db, ub = d[big], u[big]
+                P = torch.empty(int(db.numel()), k, dtype=torch.long, device=dev)
+                for i in range(k):
+                    j = db - k + i
+                    t = torch.minimum(torch.floor(ub[:, i] * (j + 1).double()).long(), j)
+                    P[:, i] = torch.where((P[:, :i] == t[:, None]).any(1), j, t)
+                pick[big] = P.sort(1).values
+            keep = torch.arange(k, device=dev)[None, :] < d.clamp(max=k)[:, None]
+            ldst = torch.arange(n_dst, device=dev)[:, None].expand(n_dst, k)[keep]
+            pos = (r0[:, None] + pick)[keep]
+        E = int(pos.numel())
+        eid, s = self.in_eid[pos].long(), self.in_src[pos].long()
+        etype = self.in_type[pos].long() if self.in_type is not None else None
+        ar = torch.arange(E, dtype=torch.int32, device=dev)
+        self.local[dst_nodes] = torch.arange(n_dst, dtype=torch.int32, device=dev)
+        self.firstpos.scatter_reduce_(0, s, ar, reduce="amin")
+        ls, fp = self.local[s].long(), self.firstpos[s]
+        fresh = (ls < 0) & (fp == ar)
+        rank = torch.cumsum(fresh, 0) - fresh.long()
+        lsrc = torch.where(ls >= 0, ls, n_dst + rank[fp.long()])
+        src_nodes = torch.cat((dst_nodes, s[fresh]))
+        self.firstpos[s] = _I32_MAX
+        self.local[dst_nodes] = -1
+        return G.Block(src_nodes, dst_nodes, lsrc, ldst, eid, etype)

@@ -10,6 +10,9 @@
                built, and the block build (sampler.full_neighbor_blocks) on its own; synthetic graphs of the size of AIFB (8 285
                entities, 29 043 triples, 45 relations, 4 classes) and AM (1 666 764 entities, 5 988 321 triples, 133 relations, 11
                classes), built with synth.py.  A new batch of seeds every repeat (its blocks are built outside the step's timing).
+               Next to it the same step on blocks of sampler.NeighborSampler with fan-outs [4, 4], and the block-build leg
+               (DESIGN.md section 9.9): full_neighbor_blocks against NeighborSampler with [None, None] and with [4, 4], the three
+               builders alternating on the same seeds in one process.
 
 HIP events, a warm-up, the median of the repeats.  Prints one JSON line at the end.
 Usage on the GPU box:  python tools/nc_bench.py [--reps 20] [--only a_std|train_step]"""
@@ -133,6 +136,38 @@ def bench_train(reps):
         e = np.array(edges[3:reps + 3])
         res = {"step_ms": round(t_step, 3), "blocks_ms": round(t_blocks, 3), "edges_per_block_median": [int(v) for v in np.median(e, 0)],
                "graph": {"N": N, "T": T, "R": R, "classes": C}}
+
+        # the same step on sampled blocks, fan-outs [4, 4]
+        sampled = SM.NeighborSampler(g, [4, 4])
+        gen44 = torch.Generator(device="cuda").manual_seed(9)
+        edges44 = []
+
+        def build44():
+            seeds = batches[state["i"] % len(batches)]
+            state["i"] += 1
+            state["blocks"] = sampled.sample(seeds, generator=gen44)
+            state["seeds"] = seeds
+            edges44.append([b.num_edges() for b in state["blocks"]])
+
+        state["i"] = 0
+        res["step_4_4_ms"] = round(timeit(step, reps, before=build44), 3)
+        res["edges_per_block_4_4_median"] = [int(v) for v in np.median(np.array(edges44[3:reps + 3]), 0)]
+
+        # the block-build leg: the three builders alternate on the same seeds
+        full = SM.NeighborSampler(g, [None, None])
+        builders = {"full_neighbor_blocks": lambda sd: SM.full_neighbor_blocks(g, sd, 2), "sampler_none_none": full.sample,
+                    "sampler_4_4": lambda sd: sampled.sample(sd, generator=gen44)}
+        times = {k: [] for k in builders}
+        for r in range(reps + 3):
+            for k, f in builders.items():
+                a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                a.record()
+                f(batches[r])
+                b.record()
+                torch.cuda.synchronize()
+                if r >= 3:
+                    times[k].append(a.elapsed_time(b))
+        res["blocks_build_ms"] = {k: round(float(np.median(v)), 3) for k, v in times.items()}
         out[name] = res
         print(name, json.dumps(res), flush=True)
         del net, opt, g, tri, trip_index
