@@ -366,9 +366,41 @@ def sync_batch_norm(x, bn, total_rows, group):
 
 
 # ---------------------------------------------------------------------------
+# what the two sharded networks share
+# ---------------------------------------------------------------------------
+def _local_partial(k, shard, op, name, x):
+    """The rank-local half of aggregator `name` (a_max / a_sum / a_mean, reference models/operations_lp.py:223-264) of module `op` on the
+    block's rows x: (partial [N, D] over the LOCAL in-edges -- a_mean's is the sum --, residual self rows x[E:]).  One HIP node where
+    the kernel set `k` has the partial forms, else (the CPU tests' oracle-backed kernel set) linear + seg_reduce."""
+    E = shard.num_edges()
+    hip = x.is_cuda and getattr(k, "linear_relu_partial", None) is not None
+    kind = "max" if name == "a_max" else "sum"
+    if name == "a_sum":
+        return k.sum_partial(x, shard) if hip else (k.seg_reduce("sum", x[:E], None, shard), x[E:])
+    if hip:
+        return k.linear_relu_partial(kind, x, op.linear.weight, op.linear.bias, shard)
+    m = k.linear(x[:E], op.linear.weight, op.linear.bias, act="relu")
+    return k.seg_reduce(kind, m, None, shard), x[E:]
+
+
+class _Sharded:
+    """A network on one relation block `self.s` over process group `self.group`."""
+
+    def _inv_degree(self):
+        """1 / max(in-degree, 1) of the own node rows over the WHOLE graph, [n_own, 1] (computed once)."""
+        if getattr(self, "_inv_deg", None) is None:
+            s = self.s
+            self._inv_deg = (1.0 / s.global_in_degree[s.node_lo:s.node_hi].clamp(min=1).to(torch.float32)).view(-1, 1).contiguous()
+        return self._inv_deg
+
+    def _stat_group(self):
+        return self.group if self.group is not None else dist.group.WORLD
+
+
+# ---------------------------------------------------------------------------
 # the sharded supernet step
 # ---------------------------------------------------------------------------
-class ShardedSupernet:
+class ShardedSupernet(_Sharded):
     """Forward of supernet.SearchNetwork on one relation block (same parameters, same
     arithmetic, rows partitioned).  `kernels` is the namespace providing gather / seg_reduce /
     linear / GatherPlan -- the HIP `functional` module in the product; the CPU tests pass an
@@ -416,22 +448,7 @@ class ShardedSupernet:
         """The rank-local halves of a middle MixedOp (reference models/operations_lp.py:223-264): per candidate the
         partial [N, D] over the LOCAL in-edges and the residual self rows; a_sum's and a_mean's partials are summed by
         the same collective, so they are concatenated to one [N, 2D] tensor."""
-        s, E = self.s, self.s.num_edges()
-        out = {}
-        for name, (op, _, _) in zip(OPS.MIDDLE_OPS, mixed_op._ops):
-            x = take()
-            hip = x.is_cuda and getattr(self.k, "linear_relu_partial", None) is not None
-            if name == "a_sum":
-                part, self_rows = self.k.sum_partial(x, s) if hip else (self.k.seg_reduce("sum", x[:E], None, s), x[E:])
-            else:
-                kind = "max" if name == "a_max" else "sum"
-                if hip:
-                    part, self_rows = self.k.linear_relu_partial(kind, x, op.linear.weight, op.linear.bias, s)
-                else:
-                    m = self.k.linear(x[:E], op.linear.weight, op.linear.bias, act="relu")
-                    part, self_rows = self.k.seg_reduce(kind, m, None, s), x[E:]
-            out[name] = (part, self_rows)
-        return out
+        return {name: _local_partial(self.k, self.s, op, name, take()) for name, (op, _, _) in zip(OPS.MIDDLE_OPS, mixed_op._ops)}
 
     def _exchange_start(self, parts):
         """Launch the two collectives of one middle MixedOp: reduce-scatter(max) of a_max's partial and ONE
@@ -455,16 +472,6 @@ class ShardedSupernet:
               "a_sum": mixed_op._ops[OPS.MIDDLE_OPS.index("a_sum")][0].drop_sum(h_both[:, :D]) + parts["a_sum"][1],
               "a_mean": h_both[:, D:] * self._inv_degree() + parts["a_mean"][1]}
         return [ys[name] for name in OPS.MIDDLE_OPS]
-
-    def _inv_degree(self):
-        """1 / max(in-degree, 1) of the own node rows over the WHOLE graph, [n_own, 1] (computed once)."""
-        if getattr(self, "_inv_deg", None) is None:
-            s = self.s
-            self._inv_deg = (1.0 / s.global_in_degree[s.node_lo:s.node_hi].clamp(min=1).to(torch.float32)).view(-1, 1).contiguous()
-        return self._inv_deg
-
-    def _stat_group(self):
-        return self.group if self.group is not None else dist.group.WORLD
 
     def _middle_stage(self, cell, wm, states, total_nodes):
         """Cell_Middle over a shard: the partials of every MixedOp are computed first and each exchange is launched as
@@ -563,7 +570,7 @@ class ShardedSupernet:
 # ---------------------------------------------------------------------------
 # the sharded fixed-genotype step (reference models/model_lp.py:77-150; BASELINE C5: 10 M edges, 1 M nodes)
 # ---------------------------------------------------------------------------
-class ShardedFixedNet:
+class ShardedFixedNet(_Sharded):
     """Forward of supernet.FixedNetwork on one relation block.  Same cell code (supernet.FixedCell.forward with its two hooks),
     rows partitioned like the supernet's, and -- what the supernet's replicated tables do not need at FB15k-237 size but the
     1 M-node table of C5 does -- the NODE TABLES ROW-SHARDED:
@@ -600,15 +607,6 @@ class ShardedFixedNet:
     def parameters(self):
         return self.replicated_parameters() + [self.emb_own]
 
-    def _stat_group(self):
-        return self.group if self.group is not None else dist.group.WORLD
-
-    def _inv_degree(self):
-        if getattr(self, "_inv_deg", None) is None:
-            s = self.s
-            self._inv_deg = (1.0 / s.global_in_degree[s.node_lo:s.node_hi].clamp(min=1).to(torch.float32)).view(-1, 1).contiguous()
-        return self._inv_deg
-
     def _bn_relu(self, y, bn, total, one):
         if y.is_cuda:
             one = one if one.device == y.device else one.to(y.device)
@@ -618,16 +616,8 @@ class ShardedFixedNet:
     def _aggregate(self, op, name, x):
         """a_max / a_sum / a_mean over a relation block: partial over the LOCAL in-edges, reduce-scatter over the node chunks,
         residual self rows (reference models/operations_lp.py:223-264)."""
-        s, E = self.s, self.s.num_edges()
-        hip = x.is_cuda and getattr(self.k, "linear_relu_partial", None) is not None
-        kind = "max" if name == "a_max" else "sum"
-        if name == "a_sum":
-            part, self_rows = self.k.sum_partial(x, s) if hip else (self.k.seg_reduce("sum", x[:E], None, s), x[E:])
-        elif hip:
-            part, self_rows = self.k.linear_relu_partial(kind, x, op.linear.weight, op.linear.bias, s)
-        else:
-            part, self_rows = self.k.seg_reduce(kind, self.k.linear(x[:E], op.linear.weight, op.linear.bias, act="relu"), None, s), x[E:]
-        own = reduce_scatter_rows(part, s, kind, self.group)
+        part, self_rows = _local_partial(self.k, self.s, op, name, x)
+        own = reduce_scatter_rows(part, self.s, "max" if name == "a_max" else "sum", self.group)
         if name == "a_sum":
             own = op.drop_sum(own)
         elif name == "a_mean":

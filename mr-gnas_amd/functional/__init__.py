@@ -27,7 +27,8 @@ This package re-exports every name of its modules, so callers keep writing ``fro
 from . import switches                                   # noqa: F401
 from ._base import (  # noqa: F401
     bump_counters, deferred_counters,
-    COMPOSE, REDUCE, ACT, gate_ld, same_rows, _same_memory, _cnt, _ws, _WS_BYTES, _ws_bytes, _SIDE_STREAMS, Fork,
+    COMPOSE, REDUCE, ACT, gate_ld, same_rows, _same_memory, _cnt, _ws, _WS_BYTES, _ws_bytes, _chunk_plan_args, _SIDE_STREAMS,
+    Fork,
 )
 from .candidates import (  # noqa: F401
     Link, Candidate, ForEpilogue, wants_stats,
@@ -36,7 +37,7 @@ from .gcs import (  # noqa: F401
     GCS, fused_gcs, span_gcs, ComposePlan, _ComposeAggregate, compose_aggregate,
 )
 from .reducers import (  # noqa: F401
-    _seg_fwd, _seg_bwd, _SegReduce, seg_reduce, _AggRows, aggregate_rows, _fused_agg_ws, _LinReluAgg, linear_relu_aggregate,
+    _seg_fwd, _heads_fwd, _seg_bwd, _SegReduce, seg_reduce, _AggRows, aggregate_rows, _fused_agg_ws, _LinReluAgg, linear_relu_aggregate,
     _LinReluPartial, linear_relu_partial, _SumPartial, sum_partial,
 )
 from .fanin import (  # noqa: F401

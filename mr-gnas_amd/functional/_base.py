@@ -62,6 +62,16 @@ def _ws_bytes(name, *args):
     if n is None:
         n = _WS_BYTES[key] = getattr(_lib.load(), name)(*args)
     return n
+
+
+def _chunk_plan_args(p, D, like, ws_query):
+    """The chunk / hub argument run of the chunk reducers over plan p (graph.dst_csr_plan), in ABI order (chunk_node ... n_slots), and
+    their slot workspace of ws_query(n_slots, D) bytes (None for a plan without slots)."""
+    n_chunks, n_hubs, n_slots = _cnt(p, "chunks"), _cnt(p, "hubs"), _cnt(p, "slots")
+    ws = _ws(_ws_bytes(ws_query, n_slots, D), like) if n_slots > 0 else None
+    ptr = _lib.ptr
+    return (ptr(p["chunk_node"]), ptr(p["chunk_start"]), ptr(p["chunk_end"]), ptr(p["chunk_slot"]), n_chunks,
+            ptr(p["hub_node"]), ptr(p["hub_first"]), ptr(p["hub_count"]), n_hubs, n_slots), ws
 _SIDE_STREAMS = {}
 
 

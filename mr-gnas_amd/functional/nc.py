@@ -9,7 +9,7 @@ import torch
 
 from .. import _lib
 from .._lib import call, f32c, ptr, require_hip, stream_of
-from ._base import _cnt, _ws, _ws_bytes
+from ._base import _chunk_plan_args
 from .reducers import ORDERED_BWD_MIN_BYTES, linear_relu_partial, seg_reduce
 
 
@@ -25,12 +25,9 @@ class _SegStd(torch.autograd.Function):
             raise _lib.MrgnasError(f"a_std: message rows {msg.shape[0]} != number of edges {E}")
         p = graph.plan()
         out, mean, coef = (torch.empty(N, D, dtype=torch.float32, device=msg.device) for _ in range(3))
-        n_chunks, n_hubs, n_slots = _cnt(p, "chunks"), _cnt(p, "hubs"), _cnt(p, "slots")
-        ws = _ws(_ws_bytes("mrg_seg_std_workspace_bytes", n_slots, D), msg) if n_slots > 0 else None
-        call("mrg_seg_std_fwd", (ptr(msg), ptr(p["eid"]), ptr(p["chunk_node"]), ptr(p["chunk_start"]), ptr(p["chunk_end"]),
-                                 ptr(p["chunk_slot"]), n_chunks, ptr(p["hub_node"]), ptr(p["hub_first"]), ptr(p["hub_count"]), n_hubs,
-                                 n_slots, ptr(p["in_degree"]), ptr(out), ptr(mean), ptr(coef), ptr(ws), N, D, stream_of(msg)),
-             nbytes=4 * E * D + 4 * E + 12 * N * D)
+        plan_args, ws = _chunk_plan_args(p, D, msg, "mrg_seg_std_workspace_bytes")
+        call("mrg_seg_std_fwd", (ptr(msg), ptr(p["eid"]), *plan_args, ptr(p["in_degree"]), ptr(out), ptr(mean), ptr(coef), ptr(ws), N, D,
+                                 stream_of(msg)), nbytes=4 * E * D + 4 * E + 12 * N * D)
         ctx.graph = graph
         ctx.save_for_backward(msg, mean, coef)
         return out

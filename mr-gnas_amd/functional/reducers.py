@@ -9,7 +9,7 @@ import torch
 from .. import _lib
 from .._lib import call, f32c, ptr, require_hip, stream_of
 from . import switches as SW
-from ._base import REDUCE, _cnt, _ws, _ws_bytes
+from ._base import REDUCE, _chunk_plan_args, _ws, _ws_bytes
 from .gcs import span_gcs
 
 
@@ -17,15 +17,22 @@ def _seg_fwd(mode, msg, self_rows, p, N, D, want_arg=True):
     """Launch mrg_seg_reduce_fwd over plan p (graph.dst_csr_plan); returns (out, arg)."""
     out = torch.empty(N, D, dtype=torch.float32, device=msg.device)
     arg = torch.empty(N, D, dtype=torch.int32, device=msg.device) if mode == 2 else None
-    n_chunks, n_hubs, n_slots = _cnt(p, "chunks"), _cnt(p, "hubs"), _cnt(p, "slots")
-    ws = _ws(_ws_bytes("mrg_seg_reduce_workspace_bytes", n_slots, D), msg) if n_slots > 0 else None
+    plan_args, ws = _chunk_plan_args(p, D, msg, "mrg_seg_reduce_workspace_bytes")
     E = int(p["eid"].numel())
     nb = 4 * D * E + 4 * E + 4 * D * N * (1 + (self_rows is not None) + (mode == 2))
-    call("mrg_seg_reduce_fwd", (mode, ptr(msg), ptr(self_rows), ptr(p["eid"]), ptr(p["chunk_node"]), ptr(p["chunk_start"]),
-                                ptr(p["chunk_end"]), ptr(p["chunk_slot"]), n_chunks, ptr(p["hub_node"]),
-                                ptr(p["hub_first"]), ptr(p["hub_count"]), n_hubs, n_slots, ptr(p["in_degree"]),
+    call("mrg_seg_reduce_fwd", (mode, ptr(msg), ptr(self_rows), ptr(p["eid"]), *plan_args, ptr(p["in_degree"]),
                                 ptr(out), ptr(arg), ptr(ws), N, D, stream_of(msg)), nbytes=nb)
     return out, arg
+
+
+def _heads_fwd(mode, part, self_rows, p, N, D):
+    """Launch the heads reducer over plan p: out[v] = sum (mode 0) / mean (mode 1) of the run sums that the run-sum GEMM left at node v's head
+    rows of part (+ self_rows[v])."""
+    out = torch.empty(N, D, dtype=torch.float32, device=part.device)
+    plan_args, ws = _chunk_plan_args(p, D, part, "mrg_seg_reduce_workspace_bytes")
+    call("mrg_seg_reduce_heads_fwd", (mode, ptr(part), ptr(self_rows), ptr(p["rowptr"]), *plan_args, ptr(p["in_degree"]), ptr(out), ptr(ws),
+                                      N, D, stream_of(part)), nbytes=8 * N * D + 4 * part.shape[0])
+    return out
 
 
 ORDERED_BWD = os.environ.get("MRG_SEG_BWD_ORDERED", "1") == "1"     # lab switch: 0 = the aggregators' backward walks the edges in edge-id order (rounds 1-4)
@@ -165,109 +172,120 @@ def _fused_agg_ws(N, D):
     return int(_lib.load().mrg_linear_relu_segmax_workspace_bytes(N, D, D))
 
 
-class _LinReluAgg(torch.autograd.Function):
-    """a_max / a_mean as ONE autograd node on the reference's [M, D] layout
-    (reference models/operations_lp.py:230-235, 245-250):
-        m = ReLU(Linear(x[:E]));  h = reduce_{e -> v} m[e];  out = h + x[E:]
-    The backward writes the gradient of x once (rows [0,E) from the input-gradient GEMM, rows [E,M) a copy of
-    the incoming gradient) instead of two zero-padded slice gradients that autograd would add, and the ReLU
-    mask is applied inside the reducer's backward kernel.  Whenever the split matrix core takes the shape, a_max runs as ONE
-    GEMM whose epilogue is the ReLU and the segmented max (mrg_linear_relu_segmax_fwd) and a_mean as a GEMM whose epilogue
-    leaves ordered run sums for the heads reducer (mrg_linear_relu_segsum_fwd): m is never written."""
-
-    @staticmethod
-    def forward(ctx, mode, x, W, b, graph):
-        x, W, b = f32c(x), f32c(W), f32c(b)
-        require_hip(x, W, b)
-        E, N, D = graph.num_edges(), graph.number_of_nodes(), x.shape[1]
-        if x.shape[0] != E + N:
-            raise _lib.MrgnasError(f"expected {E + N} rows (E + N), got {x.shape[0]}")
-        st = stream_of(x)
-        fused_ws = _fused_agg_ws(N, D) if (mode == 2 and SW.FUSED_AMAX and E >= SW.FUSED_AMAX_MIN_ROWS) else 0
-        if fused_ws > 0:
-            # a_max as ONE GEMM whose epilogue is ReLU + segmented max (the [E, D] messages are never written; the
-            # backward's ReLU mask is "the maximum is positive")
-            p = graph.plan()
-            out = torch.empty(N, D, dtype=torch.float32, device=x.device)
-            arg = torch.empty(N, D, dtype=torch.int32, device=x.device)
-            mx = torch.empty(N, D, dtype=torch.float32, device=x.device)
-            call("mrg_linear_relu_segmax_fwd", (ptr(x), ptr(W), ptr(b), ptr(p["eid"]), ptr(graph.i32("dst")), ptr(x[E:]), ptr(out), ptr(arg),
-                                                ptr(mx), ptr(_ws(fused_ws, x)), E, N, D, D, st),
-                 nbytes=4 * E * D + 8 * E + 4 * D * D + 4 * N * D * 4, flops=2 * E * D * D)
-            ctx.mode, ctx.graph, ctx.fused = mode, graph, True
-            ctx.save_for_backward(x, W, arg, mx)
-            if SW.MASK_TAP is not None:                       # test instrumentation: which edge won, and whether the maximum is positive
-                SW.MASK_TAP(("a_max", W.data_ptr()), [arg, mx > 0])
-            return out
-        if (mode == 1 and SW.FUSED_AMEAN and E >= SW.FUSED_AMAX_MIN_ROWS and hasattr(graph, "plan")
-                and _fused_agg_ws(N, D) > 0):
-            # a_mean without the [E, D] messages: the GEMM's epilogue leaves ordered run sums at the head rows of `part` and one
-            # ReLU bit per element; the chunk reducer adds a node's head rows
-            p = graph.plan()
-            part = torch.empty(E, D, dtype=torch.float32, device=x.device)          # only the head rows are written / read
-            bits = torch.empty(E, (D + 31) // 32, dtype=torch.int32, device=x.device)
-            gws = _ws(_ws_bytes("mrg_gemm_workspace_bytes", D, D), x)
-            call("mrg_linear_relu_segsum_fwd", (ptr(x), ptr(W), ptr(b), ptr(p["eid"]), ptr(graph.i32("dst")), ptr(part), ptr(bits), ptr(gws),
-                                                E, D, D, st), nbytes=4 * E * D + 8 * E + 4 * D * D, flops=2 * E * D * D)
-            out = torch.empty(N, D, dtype=torch.float32, device=x.device)
-            n_chunks, n_hubs, n_slots = _cnt(p, "chunks"), _cnt(p, "hubs"), _cnt(p, "slots")
-            ws = _ws(_ws_bytes("mrg_seg_reduce_workspace_bytes", n_slots, D), x) if n_slots > 0 else None
-            call("mrg_seg_reduce_heads_fwd", (1, ptr(part), ptr(x[E:]), ptr(p["rowptr"]), ptr(p["chunk_node"]), ptr(p["chunk_start"]),
-                                              ptr(p["chunk_end"]), ptr(p["chunk_slot"]), n_chunks, ptr(p["hub_node"]), ptr(p["hub_first"]),
-                                              ptr(p["hub_count"]), n_hubs, n_slots, ptr(p["in_degree"]), ptr(out), ptr(ws), N, D, st),
-                 nbytes=8 * N * D + 4 * E)
-            ctx.mode, ctx.graph, ctx.fused = mode, graph, "mean"
-            ctx.save_for_backward(x, W, bits)
-            if SW.MASK_TAP is not None:                       # test instrumentation: the inner ReLU's decisions, one bit per message element
-                SW.MASK_TAP(("a_mean", W.data_ptr()), [bits])
-            return out
+def _lin_relu_forward(ctx, mode, x, W, b, graph, partial):
+    """m = ReLU(Linear(x[:E]));  h = reduce_{e -> v} m[e], for both autograd nodes below.  Whole graph (partial False): returns h + x[E:],
+    the self rows added by the reducer.  partial: returns (h, x[E:].clone()), the reducers see no self rows, and "mean" is the sum.
+    Whenever the split matrix core takes the shape, the maximum runs as ONE GEMM whose epilogue is the ReLU and the segmented max, and
+    the sum / mean as a GEMM whose epilogue leaves ordered run sums for the heads reducer: m is never written."""
+    x, W, b = f32c(x), f32c(W), f32c(b)
+    require_hip(x, W, b)
+    E, N, D = graph.num_edges(), graph.number_of_nodes(), x.shape[1]
+    if not partial and x.shape[0] != E + N:
+        raise _lib.MrgnasError(f"expected {E + N} rows (E + N), got {x.shape[0]}")
+    st = stream_of(x)
+    self_rows = None if partial else x[E:]
+    ctx.mode, ctx.graph = mode, graph
+    run_sums = mode != 2 if partial else (mode == 1 and hasattr(graph, "plan"))
+    fused_ws = _fused_agg_ws(N, D) if (mode == 2 and SW.FUSED_AMAX and E >= SW.FUSED_AMAX_MIN_ROWS) else 0
+    if fused_ws > 0:
+        # the maximum as ONE GEMM whose epilogue is ReLU + segmented max (the [E, D] messages are never written; the
+        # backward's ReLU mask is "the maximum is positive"); its unpack pass adds the self rows
+        p = graph.plan()
+        out = torch.empty(N, D, dtype=torch.float32, device=x.device)
+        arg = torch.empty(N, D, dtype=torch.int32, device=x.device)
+        mx = torch.empty(N, D, dtype=torch.float32, device=x.device)
+        call("mrg_linear_relu_segmax_fwd", (ptr(x), ptr(W), ptr(b), ptr(p["eid"]), ptr(graph.i32("dst")), ptr(self_rows), ptr(out), ptr(arg),
+                                            ptr(mx), ptr(_ws(fused_ws, x)), E, N, D, D, st),
+             nbytes=4 * E * D + 8 * E + 4 * D * D + 4 * N * D * (3 if partial else 4), flops=2 * E * D * D)
+        ctx.fused = True
+        ctx.save_for_backward(x, W, arg, mx)
+        if SW.MASK_TAP is not None:                       # test instrumentation: which edge won, and whether the maximum is positive
+            SW.MASK_TAP(("a_max", W.data_ptr()), [arg, mx > 0])
+    elif run_sums and SW.FUSED_AMEAN and E >= SW.FUSED_AMAX_MIN_ROWS and _fused_agg_ws(N, D) > 0:
+        # the sum / mean without the [E, D] messages: the GEMM's epilogue leaves ordered run sums at the head rows of `part` and one
+        # ReLU bit per element; the chunk reducer adds a node's head rows
+        p = graph.plan()
+        part = torch.empty(E, D, dtype=torch.float32, device=x.device)          # only the head rows are written / read
+        bits = torch.empty(E, (D + 31) // 32, dtype=torch.int32, device=x.device)
+        gws = _ws(_ws_bytes("mrg_gemm_workspace_bytes", D, D), x)
+        call("mrg_linear_relu_segsum_fwd", (ptr(x), ptr(W), ptr(b), ptr(p["eid"]), ptr(graph.i32("dst")), ptr(part), ptr(bits), ptr(gws),
+                                            E, D, D, st), nbytes=4 * E * D + 8 * E + 4 * D * D, flops=2 * E * D * D)
+        ctx.fused = "sum" if partial else "mean"          # the reduction that the heads reducer and the backward apply
+        out = _heads_fwd(REDUCE[ctx.fused], part, self_rows, p, N, D)
+        ctx.save_for_backward(x, W, bits)
+        if SW.MASK_TAP is not None and not partial:       # test instrumentation: the inner ReLU's decisions, one bit per message element
+            SW.MASK_TAP(("a_mean", W.data_ptr()), [bits])
+    else:
         y = torch.empty(E, D, dtype=torch.float32, device=x.device)
         gws = _ws(_ws_bytes("mrg_gemm_workspace_bytes", D, D), x)
         call("mrg_linear_fwd", (ptr(x), ptr(W), ptr(b), ptr(y), ptr(gws), E, D, D, 1, st),
              nbytes=4 * E * 2 * D + 4 * D * D, flops=2 * E * D * D)
         if mode == 2:
-            out, arg = _seg_fwd(2, y, x[E:], graph.plan(), N, D)
+            out, arg = _seg_fwd(2, y, self_rows, graph.plan(), N, D)
         else:
-            sp, meta = graph.agg_plan("mean" if mode == 1 else "sum")
+            sp, meta = graph.agg_plan("mean" if (mode == 1 and not partial) else "sum")
             out, arg = span_gcs("copy", y, None, meta, sp), None
-            out += x[E:]
-        ctx.mode, ctx.graph, ctx.fused = mode, graph, False
+            if not partial:
+                out += self_rows
+        ctx.fused = False
         ctx.save_for_backward(x, W, y, *((arg,) if arg is not None else ()))
-        return out
+    return (out, x[E:].clone()) if partial else out       # partial: the residual self rows leave through the same node
+
+
+def _lin_relu_backward(ctx, g, gself, partial):
+    """Writes the gradient of x once: rows [0, E) from the input-gradient GEMM (or a_max's sparse pass), rows [E, M) the incoming
+    gradient of the self rows -- whole graph: g itself, partial: gself.  The ReLU mask is applied inside the reducer's backward kernel."""
+    graph, mode, fused = ctx.graph, ctx.mode, ctx.fused
+    x, W, *saved = ctx.saved_tensors
+    E, N, D = graph.num_edges(), graph.number_of_nodes(), x.shape[1]
+    g = f32c(g) if g is not None else torch.zeros(N, D, dtype=torch.float32, device=x.device)
+    st = stream_of(x)
+    gx = torch.empty_like(x)
+    gy = torch.empty(E, D, dtype=torch.float32, device=x.device)
+    own = None                                            # gx[E:], where the reducer's backward is the one to write it (a copy of g)
+    if partial and gself is not None:
+        gx[E:] = gself
+    elif partial:
+        gx[E:].zero_()
+    elif fused is True:
+        gx[E:] = g
+    else:
+        own = gx[E:]
+    have_gx = False
+    if fused is True:
+        arg, mx = saved
+        have_gx = _amax_bwd_sparse(g, mx, arg, W, graph, gy, gx)       # gy and gx[:E] in one pass, no dense product
+        if not have_gx:
+            _seg_bwd(mode, g * (mx > 0), graph, arg, gy, None)         # the winning message is ReLU-dead iff the maximum is 0
+    elif fused:
+        _seg_bwd(REDUCE[fused], g, graph, None, gy, own, relu_bits=saved[0])
+    else:
+        y, *arg = saved                                                # arg: a_max only
+        _seg_bwd(mode, g, graph, arg[0] if arg else None, gy, own, relu_src=y)      # gy masked by ReLU
+    work = dict(nbytes=4 * E * 2 * D + 4 * D * D, flops=2 * E * D * D)
+    if not have_gx:
+        wt = _ws(_ws_bytes("mrg_linear_bwd_input_workspace_bytes", D, D), x)
+        call("mrg_linear_bwd_input", (ptr(gy), ptr(W), ptr(gx), ptr(wt), E, D, D, D, 0, st), **work)
+    gW = torch.empty_like(W)
+    gb = torch.empty(D, dtype=torch.float32, device=x.device)
+    ws = _ws(_ws_bytes("mrg_linear_bwd_weight_workspace_bytes", E, D, D), x)
+    call("mrg_linear_bwd_weight", (ptr(gy), ptr(x), None, ptr(gW), ptr(gb), ptr(ws), E, D, 0, D, st), **work)
+    return None, gx, gW, gb, None
+
+
+class _LinReluAgg(torch.autograd.Function):
+    """a_max / a_mean as ONE autograd node on the reference's [M, D] layout
+    (reference models/operations_lp.py:230-235, 245-250):
+        m = ReLU(Linear(x[:E]));  h = reduce_{e -> v} m[e];  out = h + x[E:]
+    The backward writes the gradient of x once instead of two zero-padded slice gradients that autograd would add."""
+
+    @staticmethod
+    def forward(ctx, mode, x, W, b, graph):
+        return _lin_relu_forward(ctx, mode, x, W, b, graph, partial=False)
 
     @staticmethod
     def backward(ctx, g):
-        graph, mode = ctx.graph, ctx.mode
-        g = f32c(g)
-        if ctx.fused == "mean":
-            x, W, bits = ctx.saved_tensors
-        elif ctx.fused:
-            x, W, arg, mx = ctx.saved_tensors
-        else:
-            x, W, y, *rest = ctx.saved_tensors
-            arg = rest[0] if rest else None
-        E, N, D = graph.num_edges(), graph.number_of_nodes(), x.shape[1]
-        st = stream_of(x)
-        gx = torch.empty_like(x)
-        gy = torch.empty(E, D, dtype=torch.float32, device=x.device)
-        if ctx.fused == "mean":
-            _seg_bwd(1, g, graph, None, gy, gx[E:], relu_bits=bits)
-        elif ctx.fused:
-            gx[E:] = g
-            have_gx = _amax_bwd_sparse(g, mx, arg, W, graph, gy, gx)       # gy and gx[:E] in one pass, no dense product
-            if not have_gx:
-                _seg_bwd(mode, g * (mx > 0), graph, arg, gy, None)         # the winning message is ReLU-dead iff the maximum is 0
-        else:
-            _seg_bwd(mode, g, graph, arg, gy, gx[E:], relu_src=y)          # gy masked by ReLU; gx[E:] = g
-        work = dict(nbytes=4 * E * 2 * D + 4 * D * D, flops=2 * E * D * D)
-        if not (ctx.fused is True and have_gx):
-            wt = _ws(_ws_bytes("mrg_linear_bwd_input_workspace_bytes", D, D), x)
-            call("mrg_linear_bwd_input", (ptr(gy), ptr(W), ptr(gx), ptr(wt), E, D, D, D, 0, st), **work)
-        gW = torch.empty_like(W)
-        gb = torch.empty(D, dtype=torch.float32, device=x.device)
-        ws = _ws(_ws_bytes("mrg_linear_bwd_weight_workspace_bytes", E, D, D), x)
-        call("mrg_linear_bwd_weight", (ptr(gy), ptr(x), None, ptr(gW), ptr(gb), ptr(ws), E, D, 0, D, st), **work)
-        return None, gx, gW, gb, None
+        return _lin_relu_backward(ctx, g, None, partial=False)
 
 
 def linear_relu_aggregate(kind, x, W, b, graph):
@@ -275,98 +293,18 @@ def linear_relu_aggregate(kind, x, W, b, graph):
 
 
 class _LinReluPartial(torch.autograd.Function):
-    """The edge part of a_max / a_mean on ONE relation block of a sharded graph (mr-gnas_amd/dist.py): this
-    rank's partial  part[v] = max | sum over its LOCAL in-edges of ReLU(W x_e + b)  for all N nodes; the caller
-    all-reduces it, scales (mean) and adds the residual self rows.  x is the block's [E_local + n_own, D]
-    tensor (rows [E_local, ...) are not read; their gradient is zero here).  One autograd node: the ReLU mask
-    is applied inside the reducer's backward kernel, as in _LinReluAgg."""
+    """The edge part of a_max / a_mean on ONE relation block of a sharded graph (mr-gnas_amd/dist.py) or on a node-classification
+    block (functional/nc.py): this rank's partial  part[v] = max | sum over its LOCAL in-edges of ReLU(W x_e + b)  for all N nodes; the
+    caller all-reduces it, scales (mean) and adds the residual self rows.  x is the block's [E_local + n_own, D] tensor (rows
+    [E_local, ...) are not read: they leave as the second output).  The same forward and backward as _LinReluAgg."""
 
     @staticmethod
     def forward(ctx, mode, x, W, b, graph):
-        x, W, b = f32c(x), f32c(W), f32c(b)
-        require_hip(x, W, b)
-        E, N, D = graph.num_edges(), graph.number_of_nodes(), x.shape[1]
-        st = stream_of(x)
-        fused_ws = _fused_agg_ws(N, D) if (mode == 2 and SW.FUSED_AMAX and E >= SW.FUSED_AMAX_MIN_ROWS) else 0
-        if fused_ws > 0:                                # one GEMM with the ReLU + segmented-max epilogue, as in _LinReluAgg
-            out = torch.empty(N, D, dtype=torch.float32, device=x.device)
-            arg = torch.empty(N, D, dtype=torch.int32, device=x.device)
-            mx = torch.empty(N, D, dtype=torch.float32, device=x.device)
-            call("mrg_linear_relu_segmax_fwd", (ptr(x), ptr(W), ptr(b), ptr(graph.plan()["eid"]), ptr(graph.i32("dst")), None, ptr(out), ptr(arg),
-                                                ptr(mx), ptr(_ws(fused_ws, x)), E, N, D, D, st),
-                 nbytes=4 * E * D + 8 * E + 4 * D * D + 4 * N * D * 3, flops=2 * E * D * D)
-            ctx.mode, ctx.graph, ctx.fused = mode, graph, True
-            ctx.save_for_backward(x, W, arg, mx)
-            if SW.MASK_TAP is not None:                       # test instrumentation: which edge won, and whether the maximum is positive
-                SW.MASK_TAP(("a_max", W.data_ptr()), [arg, mx > 0])
-            return out, x[E:].clone()
-        if (mode != 2 and SW.FUSED_AMEAN and E >= SW.FUSED_AMAX_MIN_ROWS and _fused_agg_ws(N, D) > 0):
-            # the partial SUM of ReLU(linear) without the [E, D] messages (see _LinReluAgg): run sums in the GEMM epilogue + heads reducer
-            p = graph.plan()
-            part = torch.empty(E, D, dtype=torch.float32, device=x.device)
-            bits = torch.empty(E, (D + 31) // 32, dtype=torch.int32, device=x.device)
-            gws = _ws(_ws_bytes("mrg_gemm_workspace_bytes", D, D), x)
-            call("mrg_linear_relu_segsum_fwd", (ptr(x), ptr(W), ptr(b), ptr(p["eid"]), ptr(graph.i32("dst")), ptr(part), ptr(bits), ptr(gws),
-                                                E, D, D, st), nbytes=4 * E * D + 8 * E + 4 * D * D, flops=2 * E * D * D)
-            out = torch.empty(N, D, dtype=torch.float32, device=x.device)
-            n_chunks, n_hubs, n_slots = _cnt(p, "chunks"), _cnt(p, "hubs"), _cnt(p, "slots")
-            ws = _ws(_ws_bytes("mrg_seg_reduce_workspace_bytes", n_slots, D), x) if n_slots > 0 else None
-            call("mrg_seg_reduce_heads_fwd", (0, ptr(part), None, ptr(p["rowptr"]), ptr(p["chunk_node"]), ptr(p["chunk_start"]),
-                                              ptr(p["chunk_end"]), ptr(p["chunk_slot"]), n_chunks, ptr(p["hub_node"]), ptr(p["hub_first"]),
-                                              ptr(p["hub_count"]), n_hubs, n_slots, ptr(p["in_degree"]), ptr(out), ptr(ws), N, D, st),
-                 nbytes=8 * N * D + 4 * E)
-            ctx.mode, ctx.graph, ctx.fused = mode, graph, "sum"
-            ctx.save_for_backward(x, W, bits)
-            return out, x[E:].clone()
-        y = torch.empty(E, D, dtype=torch.float32, device=x.device)
-        gws = _ws(_ws_bytes("mrg_gemm_workspace_bytes", D, D), x)
-        call("mrg_linear_fwd", (ptr(x), ptr(W), ptr(b), ptr(y), ptr(gws), E, D, D, 1, st),
-             nbytes=4 * E * 2 * D + 4 * D * D, flops=2 * E * D * D)
-        if mode == 2:
-            out, arg = _seg_fwd(2, y, None, graph.plan(), N, D)
-        else:
-            sp, meta = graph.agg_plan("sum")
-            out, arg = span_gcs("copy", y, None, meta, sp), None
-        ctx.mode, ctx.graph, ctx.fused = mode, graph, False
-        ctx.save_for_backward(x, W, y, *((arg,) if arg is not None else ()))
-        return out, x[E:].clone()                       # the residual self rows leave through the same node
+        return _lin_relu_forward(ctx, mode, x, W, b, graph, partial=True)
 
     @staticmethod
     def backward(ctx, g, gself):
-        if ctx.fused == "sum":
-            x, W, bits = ctx.saved_tensors
-        elif ctx.fused:
-            x, W, arg, mx = ctx.saved_tensors
-        else:
-            x, W, y, *rest = ctx.saved_tensors
-            arg = rest[0] if rest else None
-        graph, mode = ctx.graph, ctx.mode
-        E, D = graph.num_edges(), x.shape[1]
-        g = f32c(g) if g is not None else torch.zeros(graph.number_of_nodes(), D, dtype=torch.float32, device=x.device)
-        st = stream_of(x)
-        gx = torch.empty_like(x)
-        if gself is not None:
-            gx[E:] = gself
-        else:
-            gx[E:].zero_()
-        gy = torch.empty(E, D, dtype=torch.float32, device=x.device)
-        if ctx.fused == "sum":
-            _seg_bwd(0, g, graph, None, gy, None, relu_bits=bits)
-        elif ctx.fused:
-            have_gx = _amax_bwd_sparse(g, mx, arg, W, graph, gy, gx)    # gy and gx[:E] in one pass, no dense product
-            if not have_gx:
-                _seg_bwd(mode, g * (mx > 0), graph, arg, gy, None)      # the winning message is ReLU-dead iff the maximum is 0
-        else:
-            _seg_bwd(mode, g, graph, arg, gy, None, relu_src=y)        # gy masked by ReLU
-        work = dict(nbytes=4 * E * 2 * D + 4 * D * D, flops=2 * E * D * D)
-        if not (ctx.fused is True and have_gx):
-            wt = _ws(_ws_bytes("mrg_linear_bwd_input_workspace_bytes", D, D), x)
-            call("mrg_linear_bwd_input", (ptr(gy), ptr(W), ptr(gx), ptr(wt), E, D, D, D, 0, st), **work)
-        gW = torch.empty_like(W)
-        gb = torch.empty(D, dtype=torch.float32, device=x.device)
-        ws = _ws(_ws_bytes("mrg_linear_bwd_weight_workspace_bytes", E, D, D), x)
-        call("mrg_linear_bwd_weight", (ptr(gy), ptr(x), None, ptr(gW), ptr(gb), ptr(ws), E, D, 0, D, st), **work)
-        return None, gx, gW, gb, None
+        return _lin_relu_backward(ctx, g, gself, partial=True)
 
 
 def linear_relu_partial(kind, x, W, b, graph):

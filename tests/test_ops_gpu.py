@@ -734,6 +734,119 @@ def test_fused_amean_matches_the_two_launch_form(N, E, R, D, hub):
     close(res[True][0], ref, "fused a_mean vs oracle")
 
 
+# the smallest shapes of the two tests above that reach every branch: a hub, nodes without in-edges and a padded column tile; an edge
+# list shorter than a strip half; several row tiles with 3 -> 4 column-tile padding
+PARTIAL_CASES = [(64, 300, 3, 52, True), (40, 33, 2, 100, False), (700, 30000, 5, 96, False)]
+
+
+def _lin_relu_case(N, E, R, D, hub):
+    """Graph and operands of the two tests above; also 1 / max(in-degree, 1) as [N, 1]."""
+    gen = torch.Generator().manual_seed(N + E + 2)
+    src = torch.randint(0, N, (E,), generator=gen)
+    dst = torch.randint(0, N - 10, (E,), generator=gen)              # the last 10 nodes have no in-edge
+    if hub:
+        dst[: E // 2] = 3
+    et = torch.randint(0, R, (E,), generator=gen)
+    g = G.RelGraph(N, src.numpy(), dst.numpy(), et.numpy(), np.ones(E, np.float32), device=DEV)
+    x0 = torch.randn(E + N, D, generator=gen)
+    W0 = torch.randn(D, D, generator=gen) / D ** 0.5
+    b0 = torch.randn(D, generator=gen) * 0.1
+    gout = torch.randn(N, D, generator=gen).to(DEV)
+    inv_deg = (1.0 / torch.bincount(dst, minlength=N).clamp(min=1).float()).view(-1, 1).to(DEV)
+    return g, (x0, W0, b0), gout, inv_deg
+
+
+def _fwd_bwd(f, operands, gout):
+    """(out, gx, gW, gb) of out = f(x, W, b) on fresh clones of the operands."""
+    x, W, b = (t.clone().to(DEV).requires_grad_(True) for t in operands)
+    out = f(x, W, b)
+    out.backward(gout)
+    return out.detach(), x.grad, W.grad, b.grad
+
+
+@pytest.mark.parametrize("N,E,R,D,hub", PARTIAL_CASES)
+def test_amax_partial_plus_self_rows_is_the_whole_graph_amax(N, E, R, D, hub):
+    """linear_relu_partial("max") (the form of the sharded and the node-classification paths: self rows returned, not added)
+    against linear_relu_aggregate("max"): partial + self rows and every gradient bit-identical (one f32 add per element in
+    both), on the fused GEMM with the sparse and with the dense input gradient and on the three-launch form."""
+    g, operands, gout, _ = _lin_relu_case(N, E, R, D, hub)
+    assert int(mr_gnas_amd._lib.load().mrg_linear_relu_segmax_workspace_bytes(N, D, D)) > 0      # the fused runs are fused
+    min_rows = K.switches.FUSED_AMAX_MIN_ROWS
+    try:
+        K.switches.FUSED_AMAX_MIN_ROWS = 0
+        for fused, sparse in ((True, True), (True, False), (False, False)):
+            K.switches.FUSED_AMAX, K.switches.SPARSE_AMAX_BWD = fused, sparse
+            whole = _fwd_bwd(lambda x, W, b: K.linear_relu_aggregate("max", x, W, b, g), operands, gout)
+            part = _fwd_bwd(lambda x, W, b: torch.add(*K.linear_relu_partial("max", x, W, b, g)), operands, gout)
+            for p, w, what in zip(part, whole, ("out", "gx", "gW", "gb")):
+                assert torch.equal(p, w), f"{what} (fused {fused}, sparse backward {sparse})"
+    finally:
+        K.switches.FUSED_AMAX, K.switches.FUSED_AMAX_MIN_ROWS, K.switches.SPARSE_AMAX_BWD = True, min_rows, True
+
+
+@pytest.mark.parametrize("N,E,R,D,hub", PARTIAL_CASES)
+def test_sum_partial_scaled_plus_self_rows_is_the_whole_graph_amean(N, E, R, D, hub):
+    """linear_relu_partial("sum") * 1 / max(in-degree, 1) + self rows against linear_relu_aggregate("mean"), both on the run-sum
+    GEMM + heads reducer and on the three-launch form: outputs and gradients within the tolerance of the test above (the
+    association differs the same way: a multiplication by the reciprocal against the reducer's own scaling); the fused partial
+    against the unfused one likewise, bitwise reproducible, and the same ReLU-dead edge rows."""
+    g, operands, gout, inv_deg = _lin_relu_case(N, E, R, D, hub)
+    assert int(mr_gnas_amd._lib.load().mrg_linear_relu_segmax_workspace_bytes(N, D, D)) > 0
+
+    def partial_mean(x, W, b):
+        part, self_rows = K.linear_relu_partial("sum", x, W, b, g)
+        return part * inv_deg + self_rows
+
+    res = {}
+    names = ("out", "gx", "gW", "gb")
+    min_rows = K.switches.FUSED_AMAX_MIN_ROWS
+    try:
+        K.switches.FUSED_AMAX_MIN_ROWS = 0
+        for fused in (True, True, False):
+            K.switches.FUSED_AMEAN = fused
+            cur = _fwd_bwd(partial_mean, operands, gout)
+            if fused and True in res:
+                assert all(torch.equal(p, q) for p, q in zip(cur, res[True])), "the fused partial sum is not reproducible"
+            res[fused] = cur
+            whole = _fwd_bwd(lambda x, W, b: K.linear_relu_aggregate("mean", x, W, b, g), operands, gout)
+            for p, w, what in zip(cur, whole, names):
+                close(p, w.cpu(), f"partial vs whole-graph a_mean {what} (fused {fused})", rtol=2e-5, atol=1e-6)
+    finally:
+        K.switches.FUSED_AMEAN, K.switches.FUSED_AMAX_MIN_ROWS = True, min_rows
+    for a, b_, what in zip(res[True], res[False], names):
+        close(a, b_.cpu(), "fused partial sum " + what, rtol=2e-5, atol=1e-6)
+    dead_f, dead_u = (res[True][1][:E] == 0), (res[False][1][:E] == 0)
+    assert torch.equal(dead_f.all(1), dead_u.all(1))
+
+
+@pytest.mark.parametrize("N,E,R,D,hub", PARTIAL_CASES)
+def test_partial_form_with_one_output_unused(N, E, R, D, hub):
+    """Only one of linear_relu_partial's two outputs feeds the loss.  The partial alone: the self rows' gradient is exactly zero
+    and the edge rows' is that of the run with both.  The self rows alone: their gradient is exactly one and everything else
+    exactly zero."""
+    g, operands, _, _ = _lin_relu_case(N, E, R, D, hub)
+    min_rows = K.switches.FUSED_AMAX_MIN_ROWS
+    try:
+        K.switches.FUSED_AMAX_MIN_ROWS = 0
+        for kind in ("max", "sum"):
+            for fused in (True, False):
+                K.switches.FUSED_AMAX = K.switches.FUSED_AMEAN = fused
+                res = {}
+                for use in ("both", "partial", "self"):
+                    x, W, b = (t.clone().to(DEV).requires_grad_(True) for t in operands)
+                    part, self_rows = K.linear_relu_partial(kind, x, W, b, g)
+                    {"both": part.sum() + self_rows.sum(), "partial": part.sum(), "self": self_rows.sum()}[use].backward()
+                    res[use] = (x.grad, W.grad, b.grad)
+                what = f"{kind}, fused {fused}"
+                assert torch.count_nonzero(res["partial"][0][E:]) == 0, what
+                assert torch.equal(res["partial"][0][:E], res["both"][0][:E]), what
+                assert torch.equal(res["self"][0][E:], torch.ones(N, D, device=DEV)), what
+                assert torch.count_nonzero(res["self"][0][:E]) == 0, what
+                assert torch.count_nonzero(res["self"][1]) == 0 and torch.count_nonzero(res["self"][2]) == 0, what
+    finally:
+        K.switches.FUSED_AMAX, K.switches.FUSED_AMEAN, K.switches.FUSED_AMAX_MIN_ROWS = True, True, min_rows
+
+
 @pytest.mark.gpu
 @pytest.mark.parametrize("rows,K1,K2,Nout", [(70001, 200, 0, 200), (66000, 200, 200, 200), (513, 64, 0, 40), (259, 400, 0, 8), (65537, 128, 0, 452),
                                              (300001, 128, 0, 128), (33, 200, 0, 200), (20000, 96, 0, 96), (9000, 52, 0, 300), (131073, 256, 0, 256)])
