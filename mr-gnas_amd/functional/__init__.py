@@ -17,7 +17,7 @@ This package re-exports every name of its modules, so callers keep writing ``fro
   row_linear  Dense linear on rows: the split-bf16 / exact-f32 MFMA row GEMM and its two gradients (csrc/linear.hip).
   dense       Dense (per-feature) filters f_dense_comp / f_comp / f_dense_last on the MFMA row GEMM (csrc/dense.hip, linear.hip).
   mixed       X: the MixedOp epilogue  out = sum_k w_k * ReLU(BatchNorm_k(y_k))  (csrc/mixedop.hip).
-  cell_zero   Cell zero: the MixedOp over the compose candidates, recomputed from the entity / relation tables (csrc/mixedop.hip zero_*).
+  cell_zero   Cell zero: the MixedOp over the compose candidates, recomputed from the entity / relation tables (csrc/cell_zero.hip).
   scoring     The step after the path: DistMult triple scoring and the [B, N] score functions (csrc/scoring.hip).
   ccorr       Standalone circular correlation ccorr(a, b): per-row kernel, or a shared row's circulant on the row GEMM (csrc/ccorr.hip).
   conve       ConvE feature path: BN0 -> conv -> BN1 -> ReLU -> fc of the (subject, relation) image, and the ConvE scorer (csrc/conve.hip).
@@ -57,7 +57,7 @@ from .dense import (  # noqa: F401
     dense_filter_single,
 )
 from .mixed import (  # noqa: F401
-    _MixCfg, _row_candidate_as_s, _MixedEpilogue, mixed_epilogue, PreparedEpilogue, _all_reduce_sum, StatChain,
+    _MixCfg, _ys_of, _MixedEpilogue, mixed_epilogue, PreparedEpilogue, _all_reduce_sum, StatChain,
     mixed_epilogue_prepare,
 )
 from .cell_zero import (  # noqa: F401

@@ -2,6 +2,8 @@
 
 Part of ``mr_gnas_amd.functional`` (autograd Functions over the C ABI, include/mrgnas.h): every Function enqueues HIP kernels of
 libmrgnas_hip.so on torch's current stream through ctypes; every call site states the algorithmic bytes / flops of the launch."""
+import collections
+
 import torch
 
 from .. import _lib
@@ -63,10 +65,16 @@ def wants_stats(for_epilogue):
     return bool(getattr(for_epilogue, "stats", False))
 
 
+# A candidate's first backward pass as a row scale of its incoming gradient: scale_edge * norm[r] (norm [>= edge_rows] or None = 1) on
+# the edge rows [0, edge_rows), scale_self on the self rows behind them; gated: the producer is a gated filter (f_dense_comp), whose
+# dz and direct term the scale is the first factor of.
+RowScale = collections.namedtuple("RowScale", "norm edge_rows scale_edge scale_self gated")
+
+
 class Candidate:
     """What an operator's `for_epilogue=True` path hands to mixed_epilogue_prepare instead of a bare [rows, D] tensor.
 
-      kind "stored"     y = the operator's output; `rowscale` (norm, b1, scale_edge, scale_self, gated) lets the epilogue's gradient
+      kind "stored"     y = the operator's output; `rowscale` (a RowScale) lets the epilogue's gradient
                         store perform the producer's first backward pass (dz = g * c_r [* s gate (1 - gate)], direct term)
       kind "gate"       y = f_dense_comp's GATE; the candidate gate * s * c_r is recomputed wherever it is read (never stored)
       kind "rowfactor"  y = f_sparse_comp's gate as ONE factor per row, [rows]; the candidate is s * y[:, None]

@@ -1,4 +1,4 @@
-"""Cell zero: the MixedOp over the compose candidates, recomputed from the entity / relation tables (csrc/mixedop.hip zero_*).
+"""Cell zero: the MixedOp over the compose candidates, recomputed from the entity / relation tables (csrc/cell_zero.hip).
 
 Part of ``mr_gnas_amd.functional`` (autograd Functions over the C ABI, include/mrgnas.h): every Function enqueues HIP kernels of
 libmrgnas_hip.so on torch's current stream through ctypes; every call site states the algorithmic bytes / flops of the launch."""

@@ -10,7 +10,7 @@ from .. import _lib
 from .._lib import ptr_array, call, f32c, ptr, require_hip, stream_of
 from . import switches as SW
 from ._base import Fork, _ws, _ws_bytes, same_rows
-from .candidates import Candidate, Link, wants_stats
+from .candidates import Candidate, Link, RowScale, wants_stats
 
 
 class _DenseFilter(torch.autograd.Function):
@@ -187,7 +187,7 @@ def dense_filter_comp(kind, s, s_in, norm, b0, b1, W_in, b_in, W_out, b_out, W_s
         # the backward begins with an elementwise pass over the incoming gradient (f_comp: dz = g * c; f_dense_comp: dz = g c s gate
         # (1 - gate) and the direct term g c gate; c = norm / 3 on edge rows, self_scale on self rows): a MixedOp epilogue that is
         # the only reader of y writes its gradient in that form (Candidate.rowscale + the Link it claims)
-        return Candidate("stored", y, link=link, slot=0, rowscale=(norm, int(b1), 1.0 / 3.0, float(self_scale), kind == 0))
+        return Candidate("stored", y, link=link, slot=0, rowscale=RowScale(norm, int(b1), 1.0 / 3.0, float(self_scale), kind == 0))
     return y
 
 
@@ -348,8 +348,8 @@ def dense_filter_pair(s, s_in, norm, b0, b1, dense_params, comp_weights, gate_on
     if not for_epilogue:
         return y_d, y_c
     fold = fold and y_d.requires_grad
-    rs_d = (norm, int(b1), 1.0 / 3.0, 1.0 / 3.0, True) if fold else None
-    rs_c = (norm, int(b1), 1.0 / 3.0, 1.0, False) if fold else None
+    rs_d = RowScale(norm, int(b1), 1.0 / 3.0, 1.0 / 3.0, True) if fold else None
+    rs_c = RowScale(norm, int(b1), 1.0 / 3.0, 1.0, False) if fold else None
     sums_d, sums_c = sums if sums else (None, None)
     if gate_only:
         c_d = Candidate("gate", y_d, link=link, slot=0, s=s, c=_gated_rowscale(norm, int(b1), s.shape[0], 1.0 / 3.0, 1.0 / 3.0, s.device), rowscale=rs_d,

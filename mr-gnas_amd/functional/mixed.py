@@ -2,6 +2,9 @@
 
 Part of ``mr_gnas_amd.functional`` (autograd Functions over the C ABI, include/mrgnas.h): every Function enqueues HIP kernels of
 libmrgnas_hip.so on torch's current stream through ctypes; every call site states the algorithmic bytes / flops of the launch."""
+import collections
+import ctypes
+
 import torch
 
 from .. import _lib
@@ -10,6 +13,12 @@ from . import switches as SW
 from ._base import _same_memory, _ws, _ws_bytes, bump_counters
 from .candidates import Candidate
 from .dense import _gated_rowscale
+
+
+# A candidate's RowScale (candidates.py) once this epilogue has claimed it for its gradient store: gated_link is the producer's Link
+# when the producer is a gated filter (it holds s / gate and receives the direct term), else None; link.written[slot] is where the
+# producer finds the gradient buffer that was written in its place.
+FoldedRowScale = collections.namedtuple("FoldedRowScale", "norm edge_rows scale_edge scale_self gated_link link slot")
 
 
 class _MixCfg:
@@ -31,29 +40,34 @@ class _MixCfg:
         self.gated = gated
         self.chain = None              # (StatChain, index): the statistics collectives are shared with other epilogues
         self.identity = identity       # index of the candidate that returns its input unchanged (f_identity), or None
-        self.rowscale = rowscale       # per candidate None or (norm [E] | None, edge_rows, scale_edge, scale_self, gated node | None, node): folded into its gradient
+        self.rowscale = rowscale       # per candidate None or the FoldedRowScale that is folded into its gradient
 
 
-def _row_candidate_as_s(cfg, ys):
-    """ys with the row-factor candidate's [rows] factor replaced by the tensor the kernels read in its slot: s."""
+def _ys_of(cfg, stored):
+    """The kernels' candidate list: the stored tensors laid out over cfg.present (None: an all-zero candidate), the row-factor
+    candidate's [rows] factor replaced by the tensor the kernels read in its slot: s (the factor travels in the descriptor)."""
+    it = iter(stored)
+    ys = [next(it) if p else None for p in cfg.present]
     if cfg.gated is not None and cfg.gated.get("row_k") is not None:
-        ys = list(ys)
         ys[cfg.gated["row_k"]] = cfg.gated["s"]
     return ys
+
+
+def _n_read(cfg, ys):
+    """[rows, D] tensors a pass reads: the stored candidates, the gate of the recomputed one, and s once for every candidate that is
+    a function of it."""
+    return len({y.data_ptr() for y in ys if y is not None} | ({cfg.gated["s"].data_ptr()} if cfg.gated is not None else set()))
 
 
 class _MixedEpilogue(torch.autograd.Function):
     @staticmethod
     def forward(ctx, cfg, w, *tensors):
-        from .._lib import ptr_array
         K_ = len(cfg.bns)
         nz = sum(cfg.present)
         ys_nz = [f32c(t) for t in tensors[:nz]]
         gam, bet = list(tensors[nz:nz + K_]), list(tensors[nz + K_:nz + 2 * K_])
         addend = f32c(tensors[nz + 2 * K_]) if cfg.has_addend else None
-        it = iter(ys_nz)
-        ys = [next(it) if p else None for p in cfg.present]
-        ys = _row_candidate_as_s(cfg, ys)                  # the row-factor candidate's slot holds s; its [rows] factor travels in the descriptor
+        ys = _ys_of(cfg, ys_nz)
         ref = next((y for y in ys if y is not None), None)
         if ref is None:
             raise _lib.MrgnasError("mixed epilogue needs at least one non-zero branch to know the row count")
@@ -65,8 +79,7 @@ class _MixedEpilogue(torch.autograd.Function):
         coef = torch.empty(K_, 4, D, dtype=torch.float32, device=dev)
         ypa = ptr_array(ys)
         gb = _lib.gated_branch(cfg.gated, act=cfg.act, valid_rows=cfg.valid_rows)
-        # [rows, D] tensors a pass reads: the stored candidates, the gate of the recomputed one, and s once for every candidate that is a function of it
-        nz_rd = len({y.data_ptr() for y in ys if y is not None} | ({cfg.gated["s"].data_ptr()} if cfg.gated is not None else set()))
+        nz_rd = _n_read(cfg, ys)
         bn0 = cfg.bns[0]
         training = bn0.training or not bn0.track_running_stats
         if training:
@@ -93,7 +106,6 @@ class _MixedEpilogue(torch.autograd.Function):
                      nbytes=nb_stats)
                 del given
             else:
-                import torch.distributed as dist
                 if cfg.chain is not None and cfg.chain[0].sums is not None:
                     sums = cfg.chain[0].sums[cfg.chain[1]]             # column sums of the whole graph, all-reduced with the other members'
                 else:
@@ -130,11 +142,9 @@ class _MixedEpilogue(torch.autograd.Function):
     @staticmethod
     def _launch_bwd_reduce(ctx, g, red):
         """red[k][0..2] <- this rank's sums of member ctx for upstream gradient g."""
-        from .._lib import ptr_array
         w, coef, *ys_nz = ctx.saved_tensors
         cfg, K_ = ctx.cfg, len(ctx.cfg.bns)
-        it = iter(ys_nz)
-        ys = _row_candidate_as_s(cfg, [next(it) if p else None for p in cfg.present])
+        ys = _ys_of(cfg, ys_nz)
         rows, D = g.shape
         ws = _ws(_ws_bytes("mrg_mix_workspace_bytes", K_, D), g)
         call("mrg_mix_bwd_reduce", (ptr(g), ptr_array(ys), K_, ptr(coef), ptr(w), ptr(red), ptr(ws), rows, D,
@@ -143,13 +153,10 @@ class _MixedEpilogue(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, g):
-        from .._lib import ptr_array
         w, coef, *ys_nz = ctx.saved_tensors
         cfg, K_, nz = ctx.cfg, len(ctx.cfg.bns), ctx.nz
         g = f32c(g)
-        it = iter(ys_nz)
-        ys = [next(it) if p else None for p in cfg.present]
-        ys = _row_candidate_as_s(cfg, ys)
+        ys = _ys_of(cfg, ys_nz)
         rows, D = g.shape
         dev, st = g.device, stream_of(g)
         ypa = ptr_array(ys)
@@ -183,8 +190,8 @@ class _MixedEpilogue(torch.autograd.Function):
         if (SW.FOLD_IDENTITY and cfg.identity is not None and cfg.present[cfg.identity] and rs is not None):
             pos = sum(cfg.present[:cfg.identity])
             for k in range(K_):
-                if (rs[k] is not None and rs[k][4] is not None and need_y[pos] and k != cfg.identity
-                        and _same_memory(rs[k][4].s, ys[cfg.identity])):
+                if (rs[k] is not None and rs[k].gated_link is not None and need_y[pos] and k != cfg.identity
+                        and _same_memory(rs[k].gated_link.s, ys[cfg.identity])):
                     add_from = (k, cfg.identity)
                     need_y[pos] = False                    # no gradient tensor of its own: None flows back to the alias
                     break
@@ -203,29 +210,27 @@ class _MixedEpilogue(torch.autograd.Function):
                                        valid_rows=cfg.valid_rows)
         n_out = sum(t is not None and t.dim() == 2 for t in gys_nz)
         if rs is not None and any(r is not None for r in rs):
-            import ctypes
             on = (ctypes.c_int * K_)(*[int(r is not None) for r in rs])
-            rs_ptr = ptr_array([r[0] if r is not None else None for r in rs])
-            rs_edge = (ctypes.c_int64 * K_)(*[int(r[1]) if r is not None else 0 for r in rs])
-            rs_scale = (ctypes.c_float * K_)(*[float(r[2]) if r is not None else 1.0 for r in rs])
-            rs_self = (ctypes.c_float * K_)(*[float(r[3]) if r is not None else 1.0 for r in rs])
+            rs_ptr = ptr_array([r.norm if r is not None else None for r in rs])
+            rs_edge = (ctypes.c_int64 * K_)(*[int(r.edge_rows) if r is not None else 0 for r in rs])
+            rs_scale = (ctypes.c_float * K_)(*[float(r.scale_edge) if r is not None else 1.0 for r in rs])
+            rs_self = (ctypes.c_float * K_)(*[float(r.scale_self) if r is not None else 1.0 for r in rs])
             # the same multipliers expanded over all rows (cached per graph): one unconditional load per row in the kernel
-            rs_full_t = [_gated_rowscale(r[0], int(r[1]), rows, float(r[2]), float(r[3]), dev) if r is not None else None for r in rs]
+            rs_full_t = [_gated_rowscale(r.norm, int(r.edge_rows), rows, float(r.scale_edge), float(r.scale_self), dev) if r is not None else None
+                         for r in rs]
             rs_full = ptr_array(rs_full_t)
             # gated consumers (f_dense_comp): their dz AND the direct term of their input gradient are written here; the buffer of
             # the direct term is handed to the consumer's backward node (which runs later, maybe on a side stream)
-            gated = [r is not None and r[4] is not None for r in rs]
-            for k in range(K_):
-                if gated[k]:
+            glinks = [r.gated_link if r is not None else None for r in rs]
+            f_gs = [torch.empty_like(gl.s) if gl is not None else None for gl in glinks]
+            f_s = ptr_array([gl.s if gl is not None else None for gl in glinks])
+            f_gate = ptr_array([gl.gate if gl is not None else None for gl in glinks])
+            for k, gl in enumerate(glinks):
+                if gl is not None:
                     on[k] = 2
-            f_gs = [torch.empty_like(rs[k][4].s) if gated[k] else None for k in range(K_)]
-            f_s = ptr_array([rs[k][4].s if gated[k] else None for k in range(K_)])
-            f_gate = ptr_array([rs[k][4].gate if gated[k] else None for k in range(K_)])
-            for k in range(K_):
-                if gated[k]:
-                    rs[k][4].gs_direct = f_gs[k]
+                    gl.gs_direct = f_gs[k]
             f_gs_p = ptr_array(f_gs)
-            n_fold = sum(gated)
+            n_fold = sum(gl is not None for gl in glinks)
             f_add = (ctypes.c_int * K_)(*[(add_from[1] if (add_from is not None and k == add_from[0]) else -1) for k in range(K_)])
         else:
             on = rs_ptr = rs_edge = rs_scale = rs_self = rs_full = f_s = f_gate = f_gs_p = f_add = None
@@ -236,7 +241,7 @@ class _MixedEpilogue(torch.autograd.Function):
         if rs is not None:
             for k in range(K_):                       # the consumer checks that THIS buffer is what reaches it (no second reader of y)
                 if rs[k] is not None and gys[k] is not None:
-                    rs[k][5].written[rs[k][6]] = gys[k].data_ptr()
+                    rs[k].link.written[rs[k].slot] = gys[k].data_ptr()
         dgam = [red_local[k, 1] for k in range(K_)]
         dbet = [red_local[k, 0] for k in range(K_)]
         return (None, dw, *gys_nz, *dgam, *dbet) + ((g,) if cfg.has_addend else ())       # d out / d addend = identity
@@ -285,7 +290,6 @@ class StatChain:
     member's slice for its own backward.  Values are those of one collective per member (a sum over ranks of the same numbers)."""
 
     def __init__(self, members, group, summed):
-        import torch.distributed as dist
         # Only counts are kept: the members' candidate tensors stay owned by their PreparedEpilogue (advisor r3: a chain that held
         # `members` kept every [rows, D] candidate of every member alive until Python's cyclic collector ran).
         self.group, self.summed = group, summed
@@ -298,19 +302,18 @@ class StatChain:
         if not members or not all(self._trains(c) for c in cfgs):
             return                                         # eval mode: fixed statistics, no collective at all
         ks = self.ks
-        first = next(y for y in _row_candidate_as_s(cfgs[0], self._ys(members[0])) if y is not None)
+        first = next(y for y in self._ys(members[0]) if y is not None)
         D = first.shape[1]
         sums = torch.empty(sum(ks), 2, D, dtype=torch.float64, device=first.device)
         off = 0
         for j, m in enumerate(members):
             m.cfg.chain = (self, j)
-            ys = _row_candidate_as_s(m.cfg, self._ys(m))
+            ys = self._ys(m)
             y0 = next(y for y in ys if y is not None)
             rows = y0.shape[0]
             ws = _ws(_ws_bytes("mrg_mix_workspace_bytes", ks[j], D), y0)
-            nz_rd = len({y.data_ptr() for y in ys if y is not None} | ({m.cfg.gated["s"].data_ptr()} if m.cfg.gated is not None else set()))
             call("mrg_mix_colstats", (ptr_array(ys), ks[j], rows, D, ptr(sums[off:off + ks[j]]), ptr(ws), _lib.gated_branch(m.cfg.gated, act=m.cfg.act), stream_of(y0)),
-                 nbytes=4 * D * rows * nz_rd)
+                 nbytes=4 * D * rows * _n_read(m.cfg, ys))
             off += ks[j]
         _all_reduce_sum(sums, group)
         self.sums, off = [], 0
@@ -325,8 +328,7 @@ class StatChain:
 
     @staticmethod
     def _ys(m):
-        it = iter(f32c(t) for t in m.cand)
-        return [next(it) if p else None for p in m.cfg.present]
+        return _ys_of(m.cfg, [f32c(t) for t in m.cand])
 
     def register(self, j, ctx):
         """Member j's autograd context, needed only when the members share ONE backward reduction (`summed`).  cfg -> chain -> ctx ->
@@ -343,7 +345,6 @@ class StatChain:
 
     def reduced_gradient_sums(self, j, g, launch):
         """(red_local, red_global) of member j for upstream gradient g; `launch(ctx, g, red_out)` runs one member's reduction."""
-        import torch.distributed as dist
         if not self.summed:
             return None
         if self.bwd is None or self.bwd[0] != g.data_ptr():
@@ -384,9 +385,8 @@ def mixed_epilogue_prepare(ys, bns, group=None, total_rows=None, fold_row_scales
     if fold_row_scales:
         for k, c in enumerate(cands):
             if c is not None and c.rowscale is not None and c.link is not None and c.link.claim(c.slot):
-                # (norm, b1, scale_edge, scale_self, the Link when the producer is a gated filter -- it holds s / gate and receives
-                #  the direct term --, the Link, the producer's output slot)
-                rowscale[k] = c.rowscale[:4] + (c.link if c.rowscale[4] else None, c.link, c.slot)
+                r = c.rowscale
+                rowscale[k] = FoldedRowScale(r.norm, r.edge_rows, r.scale_edge, r.scale_self, c.link if r.gated else None, c.link, c.slot)
     gated = None
     for k, c in enumerate(cands):
         if c is not None and c.kind == "gate":
@@ -409,7 +409,7 @@ def mixed_epilogue_prepare(ys, bns, group=None, total_rows=None, fold_row_scales
               and ((D_ % 4 == 0 and D_ <= 256 and aligned) or D_ <= 64))
         if ok and wants_grad:                              # the gated candidate's folded gradient store is where the gradient w.r.t. s goes
             rs_g = rowscale[gated["k"]]
-            ok = rs_g is not None and rs_g[4] is not None and y.requires_grad and c.link is not None
+            ok = rs_g is not None and rs_g.gated_link is not None and y.requires_grad and c.link is not None
         if ok:
             gated.update(row_k=k, row_f=y, b0=rb0, b1=rb1, row_link=c.link if wants_grad else None)
         else:

@@ -1015,13 +1015,16 @@ def test_fused_aggregators_are_bit_exact_across_split_core_kernels(kind, D):
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("N,E,R,D,train", [(3000, 90000, 11, 200, True), (400, 5000, 5, 64, True), (300, 3000, 4, 10, True), (500, 20000, 7, 200, False)])
+@pytest.mark.parametrize("N,E,R,D,train", [(3000, 90000, 11, 200, True), (400, 5000, 5, 64, True), (300, 3000, 4, 10, True), (500, 20000, 7, 200, False),
+                                           # two column steps per lane: float4 rows (66 > 64 lanes), scalar rows on 64 lanes
+                                           (40, 200, 3, 264, True), (40, 200, 3, 70, True)])
 def test_cell_zero_recompute_matches_the_stored_candidates(N, E, R, D, train):
     """Cell_Zero's MixedOp over PRE_OPS with the candidates recomputed from the tables (mrg_zero_*: no [rows, D] candidate is
     stored) against three gather-compose launches + the generic epilogue: output, BatchNorm running statistics, alpha / gamma /
     beta gradients bit-identical (same values, same summation order); the table gradients (the association of their sums
-    differs) within rounding, and against the plain torch formulation."""
-    from mr_gnas_amd import supernet as S
+    differs) within rounding, and against the plain torch formulation.  The fused run must reach the mrg_zero_* entry points (a
+    fallback to the stored form would compare that form with itself)."""
+    from mr_gnas_amd import _lib, supernet as S
     gen = torch.Generator().manual_seed(N + E + D)
     ent0 = torch.randn(N, D, generator=gen)
     rel0 = torch.randn(2 * R + 1, D, generator=gen)
@@ -1042,8 +1045,11 @@ def test_cell_zero_recompute_matches_the_stored_candidates(N, E, R, D, train):
             mixed.train(train)
             ent, rel, w = (t.clone().to(DEV).requires_grad_(True) for t in (ent0, rel0, w0))
             gp_e, gp_r = K.GatherPlan(ei, N), K.GatherPlan(ri, 2 * R + 1)
+            _lib.meter.start()
             out = mixed(w, None, K.LazyRows(ent, gp_e), K.LazyRows(rel, gp_r))
             out.backward(gout)
+            ran = {k: v["launches"] for k, v in _lib.meter.stop().items() if k.startswith("mrg_zero_")}
+            assert ran == (dict(mrg_zero_fwd=1, mrg_zero_bwd_reduce=1, mrg_zero_bwd_apply=1, **({"mrg_zero_stats_coef": 1} if train else {})) if fused else {}), ran
             res[fused] = dict(out=out.detach(), w=w.grad, ent=ent.grad, rel=rel.grad,
                               gam=[bn.weight.grad.clone() for _, bn, _ in mixed._ops], bet=[bn.bias.grad.clone() for _, bn, _ in mixed._ops],
                               rm=[bn.running_mean.clone() for _, bn, _ in mixed._ops], rv=[bn.running_var.clone() for _, bn, _ in mixed._ops])
