@@ -1,5 +1,5 @@
 // Shared parts of the split-bf16 ("3-way split") matrix core: ONE definition of everything the row GEMM kernels
-// (gemm_x3.hpp, gemm_x3s.hpp, gemm_x3s8.hpp, gemm_x3q.hpp), the weight-gradient kernels (linear.hip: wgrad_x3_k, wgrad_x3v_k) and
+// (gemm_x3.hpp, gemm_x3s.hpp, gemm_x3s8.hpp, gemm_x3q.hpp), the weight-gradient kernels (wgrad.hip: wgrad_x3_k, wgrad_x3v_k) and
 // the lab kernels (tools/lab/) have in common, so that the bit-exactness the tests pin between them rests on one text:
 //   * the process-wide kernel switches (GemmSwitches),
 //   * the arithmetic: the split of f32 into three bf16 planes and the six-term product chain,
@@ -33,7 +33,7 @@ typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 
 // ---- process-wide kernel switches ------------------------------------------------------------------------------------------
 // Which kernel a launch takes.  One object per shared library (the static of an inline function), written by the
-// mrg_gemm_set_* / mrg_wgrad_set_variant entry points (linear.hip), read by the launchers and by gemm_dispatch.hpp.  The
+// mrg_gemm_set_* / mrg_wgrad_set_variant entry points (linear.hip, wgrad.hip), read by the launchers and by gemm_dispatch.hpp.  The
 // non-default values are the comparison points of the tests, of bench.py and of the lab tools.
 constexpr int64_t X3N_MAX_ROWS = 16384;     // measured crossover (linear 200 x 200, one MI355X): 13 vs 24 us at 4 096 rows, 19 vs 27 at 16 384, 31 vs 30 at 32 768
 struct GemmSwitches {

@@ -14,8 +14,8 @@ This package re-exports every name of its modules, so callers keep writing ``fro
   fanin       Gradient fan-in of a tensor with several readers: K-way sums and the Fan alias bookkeeping (csrc/accum.hip).
   compose_gather  a1: compose ops (pre_mult / pre_sub / pre_add) and G, the row gather that feeds them (csrc/compose.hip).
   gates       a2 / a3: collapsed scalar gates f_sparse_comp / f_sparse_last (csrc/gate.hip).
-  row_linear  Dense linear on rows: the split-bf16 / exact-f32 MFMA row GEMM and its two gradients (csrc/linear.hip).
-  dense       Dense (per-feature) filters f_dense_comp / f_comp / f_dense_last on the MFMA row GEMM (csrc/dense.hip, linear.hip).
+  row_linear  Dense linear on rows: the split-bf16 / exact-f32 MFMA row GEMM and its two gradients (csrc/linear.hip, wgrad.hip).
+  dense       Dense (per-feature) filters f_dense_comp / f_comp / f_dense_last on the MFMA row GEMM (csrc/dense.hip, linear.hip, wgrad.hip).
   mixed       X: the MixedOp epilogue  out = sum_k w_k * ReLU(BatchNorm_k(y_k))  (csrc/mixedop.hip).
   cell_zero   Cell zero: the MixedOp over the compose candidates, recomputed from the entity / relation tables (csrc/cell_zero.hip).
   scoring     The step after the path: DistMult triple scoring and the [B, N] score functions (csrc/scoring.hip).

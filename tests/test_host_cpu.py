@@ -223,7 +223,8 @@ def test_async_fill_kernels_do_not_spill():
         pytest.skip("hipcc not available")
     csrc = os.path.join(ROOT, "mr-gnas_amd", "csrc")
     seen = 0
-    for unit in ("linear.hip", "dense.hip"):
+    wgrad_x3_clean = set()
+    for unit in ("linear.hip", "wgrad.hip", "dense.hip"):
         out = subprocess.run([hipcc, "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Rpass-analysis=kernel-resource-usage",
                               "--cuda-device-only", "-c", os.path.join(csrc, unit), "-o", os.devnull],
                              capture_output=True, text=True, timeout=600)
@@ -242,7 +243,11 @@ def test_async_fill_kernels_do_not_spill():
                 # (test_split_core_kernels_are_bit_exact_with_each_other); bounded here so that it cannot grow unnoticed
                 gate_x3s = re.search(r"rowgemm_x3s_kILi\d+ELi1E", name) is not None
                 assert int(m.group(1)) <= (16 if gate_x3s else 0), f"{name} spills {m.group(1)} VGPRs"
+                w = re.search(r"(wgrad_x3v?_k)ILi(\d)E", name)
+                if w and int(m.group(1)) == 0:
+                    wgrad_x3_clean.add((w.group(1), int(w.group(2))))
     assert seen >= 20
+    assert wgrad_x3_clean == {("wgrad_x3_k", 1), ("wgrad_x3_k", 2), ("wgrad_x3v_k", 1), ("wgrad_x3v_k", 2)}, wgrad_x3_clean
 
 
 def test_fan_sums_reader_gradients_and_tolerates_unused_aliases():

@@ -454,6 +454,76 @@ def test_weight_gradient_split_once_is_bit_exact_with_split_per_wave(rows, K1, K
     assert float((res[1][0].double() - ref).abs().max()) <= 2e-5 * max(1.0, float(ref.abs().max()))
 
 
+def _wgrad_vs_float64(rows, K1, K2, Nout, bounds=None):
+    """mrg_linear_bwd_weight (bounds None) or mrg_linear_bwd_weight3 over the ranges [0, b0) [b0, b1) [b1, rows) into outputs
+    pre-filled with 7.0, against the float64 product: 2e-5 * max(1, |ref|.max()) for gW and for gb."""
+    from mr_gnas_amd._lib import call, ptr, ptr_array, stream_of
+    lib = mr_gnas_amd._lib.load()
+    gen = torch.Generator().manual_seed(1000 * rows + 7 * Nout + K1 + K2)
+    gy = torch.randn(rows, Nout, generator=gen).to(DEV)
+    x1 = (torch.randn(rows, K1, generator=gen) * 2).to(DEV)
+    x2 = torch.randn(rows, K2, generator=gen).to(DEV) if K2 else None
+    x = x1 if x2 is None else torch.cat((x1, x2), 1)
+    K_ = K1 + K2
+    if bounds is None:
+        cuts = [(0, rows)]
+        gWs, gbs = [torch.full((Nout, K_), 7.0, device=DEV)], [torch.full((Nout,), 7.0, device=DEV)]
+        ws = torch.empty(max(16, int(lib.mrg_linear_bwd_weight_workspace_bytes(rows, K_, Nout))), dtype=torch.uint8, device=DEV)
+        call("mrg_linear_bwd_weight", (ptr(gy), ptr(x1), ptr(x2), ptr(gWs[0]), ptr(gbs[0]), ptr(ws), rows, K1, K2, Nout, stream_of(gy)))
+    else:
+        b0, b1 = bounds
+        cuts = [(0, b0), (b0, b1), (b1, rows)]
+        gWs = [torch.full((Nout, K_), 7.0, device=DEV) for _ in range(3)]
+        gbs = [torch.full((Nout,), 7.0, device=DEV) for _ in range(3)]
+        nbytes = int(lib.mrg_linear_bwd_weight3_workspace_bytes(b0, b1, rows, K1, K2, Nout))
+        assert nbytes > 0
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=DEV)
+        call("mrg_linear_bwd_weight3", (ptr(gy), ptr(x1), ptr(x2), ptr_array(gWs), ptr_array(gbs), ptr(ws), b0, b1, rows, K1, K2, Nout, stream_of(gy)))
+    torch.cuda.synchronize()
+    for (lo, hi), gW, gb in zip(cuts, gWs, gbs):
+        ref_w = gy[lo:hi].double().t() @ x[lo:hi].double()
+        ref_b = gy[lo:hi].double().sum(0)
+        err_w, err_b = float((gW.double() - ref_w).abs().max()), float((gb.double() - ref_b).abs().max())
+        assert err_w <= 2e-5 * max(1.0, float(ref_w.abs().max())), (lo, hi, err_w)
+        assert err_b <= 2e-5 * max(1.0, float(ref_b.abs().max())), (lo, hi, err_b)
+
+
+# (Nout, K1, K2) -> the (accumulator tiles per wave, prefetch class) instance of the exact-f32 kernels the shape lands on
+WGRAD_DMA_SHAPES = [(4, 4, 0), (4, 96, 0), (36, 4, 0), (36, 64, 0), (68, 4, 0), (100, 4, 0), (132, 4, 0), (196, 32, 0),   # (1,2) (1,4) (2,2) (2,4) (4,2) (4,4) (7,4) (7,8)
+                    (196, 16, 16)]                                                                                       # (7,8) from two sources
+WGRAD_PLAIN_SHAPES = [(1, 1, 0), (1, 97, 0), (1, 129, 0), (1, 225, 0), (65, 65, 0), (1, 257, 0), (1, 481, 0), (33, 257, 0), (1, 513, 0),   # (1,2) (1,4) (2,4) (2,8) (4,4) (4,8) (4,16) (7,8) (7,16)
+                      (225, 131, 0),                       # (7,8), eight row tiles: two column blocks on grid.y
+                      (65, 33, 32)]                        # two sources
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("Nout,K1,K2", WGRAD_DMA_SHAPES)
+def test_every_exact_f32_dma_weight_gradient_instance(Nout, K1, K2):
+    """One shape per instance of wgrad_dma_k that the plan can reach (exact-f32 mode, vector-eligible operands); 83 rows are two
+    row blocks whose last tile holds 3 valid rows."""
+    lib = mr_gnas_amd._lib.load()
+    try:
+        assert lib.mrg_gemm_set_mode(1) == 0
+        _wgrad_vs_float64(83, K1, K2, Nout)
+    finally:
+        lib.mrg_gemm_set_mode(0)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("Nout,K1,K2", WGRAD_PLAIN_SHAPES)
+def test_every_plain_weight_gradient_instance(Nout, K1, K2):
+    """One shape per instance of wgrad_k that the plan can reach: odd sizes keep the operands off the vector path."""
+    _wgrad_vs_float64(83, K1, K2, Nout)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("rows,K1,K2,Nout,bounds", [(9, 64, 64, 64, None), (15, 200, 0, 200, None), (40, 64, 64, 64, (13, 30))])
+def test_split_core_weight_gradient_with_fewer_than_16_rows(rows, K1, K2, Nout, bounds):
+    """Below 16 rows wgrad_x3v_k (whose ragged last tile reads the 16 rows ending at the range's end) gives way to wgrad_x3_k: for
+    the single range, and for the whole grouped launch when one of its ranges ends below row 16."""
+    _wgrad_vs_float64(rows, K1, K2, Nout, bounds)
+
+
 @pytest.mark.gpu
 @pytest.mark.parametrize("N,E,D,K_,self_rows", [(300, 5000, 200, 3, True), (50, 0, 64, 2, True), (1000, 70000, 100, 0, True), (200, 3000, 52, 8, False),
                                               (77, 900, 260, 1, True)])
