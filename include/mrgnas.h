@@ -34,7 +34,7 @@
 extern "C" {
 #endif
 
-#define MRG_ABI_VERSION 22   /* 22: mrg_cand_linear_fwd, mrg_cand_linear_bwd_input, mrg_cand_linear_colsum_blocks, mrg_cand_linear_workspace_bytes (the candidate Linears of one node-classification MixedOp in one launch, BatchNorm sums included); 21: mrg_adam_step (multi-tensor Adam over the pointer tables of mrg_clip_sgd_step, two launches; per-tensor step counts and lr in device memory); 20: BatchNorm sums formed by a candidate's producer: mrg_gated_branch.given / given_n / given_stride (mrg_mix_stats_coef skips the sweep over such a candidate), mrg_dense_filter3_colsum_blocks, mrg_dense_filter_fwd3_colsum, mrg_gate_row_colsum_blocks, mrg_gate_row_fwd_colsum; 19: mrg_seg_std_workspace_bytes, mrg_seg_std_fwd, mrg_seg_std_bwd (a_std, the standard-deviation aggregator of the node-classification task); 18: mrg_conve_* (the ConvE feature path: BN0 statistics, conv, BN1, split-K fc and their gradients, stacked or interleaved image layout); 17: mrg_ccorr_rows, mrg_ccorr_matrix, mrg_ccorr_matrix_grad (standalone circular correlation: per-row kernel, and the circulant of a shared row with its gradient fold for the row GEMM); 16: mrg_set_stream_blocks, mrg_gate_collapse and mrg_gate_param_grad removed (the streaming grid bound is fixed; the three-segment forms remain); 15: mrg_gated_branch.valid_rows and the valid_rows argument of mrg_mix_finalize_bwd / mrg_zero_* except colstats (the device row count of a static step graph, passed per call instead of the process-wide registry of 13), mrg_linear_bwd_weight_share (the weight gradient of one range of a grouped launch, instead of the process-wide setter of 14); 14: mrg_clip_sgd_step, mrg_optim_chunk (clip_grad_norm_ + SGD with momentum over every parameter tensor in three launches), mrg_gated_branch.act (tanh behind the BatchNorm: CompGraphConv's tail on the epilogue kernels), mrg_gemm_set_small (few-row products on two-tile column blocks), a weight-gradient share setter, mrg_segmax_bwd_input (a_max's input gradient without a dense product); 13: a registry of device-side row counts (the sampled search step as one replayable HIP graph), mrg_seg_reduce_bwd_ordered (aggregator backward walked in destination order), mrg_gemm_set_q (the 16 x 16 x 32 row GEMM at three workgroups per CU for 129..224 output columns); 12: mrg_act_grad_transpose (the [B, N] scorer's output gradient, activation folded in, as [N, B] rows); 11: mrg_gemm_set_wide8 (eight-tile column block for D = 256); 10: mrg_gemm_set_epilogue(2) (transposed accumulators: a tested comparison point); 9: mrg_gated_branch (the MixedOp epilogue recomputes f_dense_comp's output from its gate and f_sparse_comp's from its row factor), mrg_gate_row_fwd / _bwd, mrg_sum_rows_gather, mrg_wgrad_set_variant, mrg_dense_filter_fwd3 out == NULL; 8: mrg_zero_* (cell-zero MixedOp recomputed from the tables), mrg_linear_bwd_input3_pair, mrg_sample_edge_neighborhood; 7: mrg_gemm_set_epilogue (row-order stores of the split-core row GEMM), mrg_set_stream_blocks, mrg_gemm_set_mode(2); 6: fused a_mean (run-sum epilogue, heads reducer, bit-mask backward), mrg_mix_stats_coef; 5: three-segment dense filter entry points; 4: mrg_linear_relu_segmax_fwd (fused a_max); 3: device graph / plan builders, samplers, [B, N] scorers, ranking; 2: GEMM workspaces, span_gcs ext_scal */
+#define MRG_ABI_VERSION 23   /* 23: mrg_gemm_set_epilogue removed (the row-order and transposed-accumulator store orders of the split-core row GEMM, measured slower, left the library; accumulator-order stores remain), mrg_gemm_set_wide8 and mrg_gemm_set_small take 0 or 1 only; 22: mrg_cand_linear_fwd, mrg_cand_linear_bwd_input, mrg_cand_linear_colsum_blocks, mrg_cand_linear_workspace_bytes (the candidate Linears of one node-classification MixedOp in one launch, BatchNorm sums included); 21: mrg_adam_step (multi-tensor Adam over the pointer tables of mrg_clip_sgd_step, two launches; per-tensor step counts and lr in device memory); 20: BatchNorm sums formed by a candidate's producer: mrg_gated_branch.given / given_n / given_stride (mrg_mix_stats_coef skips the sweep over such a candidate), mrg_dense_filter3_colsum_blocks, mrg_dense_filter_fwd3_colsum, mrg_gate_row_colsum_blocks, mrg_gate_row_fwd_colsum; 19: mrg_seg_std_workspace_bytes, mrg_seg_std_fwd, mrg_seg_std_bwd (a_std, the standard-deviation aggregator of the node-classification task); 18: mrg_conve_* (the ConvE feature path: BN0 statistics, conv, BN1, split-K fc and their gradients, stacked or interleaved image layout); 17: mrg_ccorr_rows, mrg_ccorr_matrix, mrg_ccorr_matrix_grad (standalone circular correlation: per-row kernel, and the circulant of a shared row with its gradient fold for the row GEMM); 16: mrg_set_stream_blocks, mrg_gate_collapse and mrg_gate_param_grad removed (the streaming grid bound is fixed; the three-segment forms remain); 15: mrg_gated_branch.valid_rows and the valid_rows argument of mrg_mix_finalize_bwd / mrg_zero_* except colstats (the device row count of a static step graph, passed per call instead of the process-wide registry of 13), mrg_linear_bwd_weight_share (the weight gradient of one range of a grouped launch, instead of the process-wide setter of 14); 14: mrg_clip_sgd_step, mrg_optim_chunk (clip_grad_norm_ + SGD with momentum over every parameter tensor in three launches), mrg_gated_branch.act (tanh behind the BatchNorm: CompGraphConv's tail on the epilogue kernels), mrg_gemm_set_small (few-row products on two-tile column blocks), a weight-gradient share setter, mrg_segmax_bwd_input (a_max's input gradient without a dense product); 13: a registry of device-side row counts (the sampled search step as one replayable HIP graph), mrg_seg_reduce_bwd_ordered (aggregator backward walked in destination order), mrg_gemm_set_q (the 16 x 16 x 32 row GEMM at three workgroups per CU for 129..224 output columns); 12: mrg_act_grad_transpose (the [B, N] scorer's output gradient, activation folded in, as [N, B] rows); 11: mrg_gemm_set_wide8 (eight-tile column block for D = 256); 10: mrg_gemm_set_epilogue(2) (transposed accumulators: a tested comparison point); 9: mrg_gated_branch (the MixedOp epilogue recomputes f_dense_comp's output from its gate and f_sparse_comp's from its row factor), mrg_gate_row_fwd / _bwd, mrg_sum_rows_gather, mrg_wgrad_set_variant, mrg_dense_filter_fwd3 out == NULL; 8: mrg_zero_* (cell-zero MixedOp recomputed from the tables), mrg_linear_bwd_input3_pair, mrg_sample_edge_neighborhood; 7: mrg_gemm_set_epilogue (row-order stores of the split-core row GEMM), mrg_set_stream_blocks, mrg_gemm_set_mode(2); 6: fused a_mean (run-sum epilogue, heads reducer, bit-mask backward), mrg_mix_stats_coef; 5: three-segment dense filter entry points; 4: mrg_linear_relu_segmax_fwd (fused a_max); 3: device graph / plan builders, samplers, [B, N] scorers, ranking; 2: GEMM workspaces, span_gcs ext_scal */
 
 #define MRG_OK            0
 #define MRG_E_NULLPTR    -1   /* a required pointer is NULL */
@@ -466,21 +466,9 @@ int64_t mrg_gemm_workspace_bytes(int K, int Nout);
  * point with bit-identical results.  Modes 3 / 4 of rounds 2-3 (persistent and two-waves-per-SIMD kernels)
  * left the library in round 4 (tools/lab/).  Process-wide. */
 int mrg_gemm_set_mode(int mode);
-/* Store order of the split-core row GEMM's elementwise epilogues (bias / activation, gate, scale, accumulate):
- * 0 (default): accumulator-order 4-byte stores (two 128-byte row pieces per store instruction);
- * 2 (round 4): the LDS-weight kernel exchanges the MFMA operands, so that a lane holds one output row's 4-column chunks and
- * every epilogue load and store is 16 bytes per lane with no LDS round trip (needs N % 4 == 0 and 16-byte aligned rows of every
- * [rows, N] operand and of the bias; otherwise, and for the fused aggregators' epilogues, mode 0) -- bit-identical, measured
- * 8-30 % slower per launch, kept as a tested comparison point;
- * 1: (one-wave kernel, mrg_gemm_set_mode(2)) a 32-row strip of results goes through wave-private LDS and leaves as
- * row-order 16-byte stores (1 KB of consecutive addresses per store instruction; the gate multiplicand / accumulate input are
- * read the same way) whenever N % 4 == 0 and the rows of every [rows, N] operand are 16-byte aligned.  Bit-identical results;
- * measured slower for the plain epilogue and in the whole step, kept as a tested comparison point.
- * Process-wide. */
-int mrg_gemm_set_epilogue(int mode);
 /* 1 (default): a split-core row GEMM whose output is eight 32-column tiles wide (225 .. 256 columns: D = 256) and that has no
  * direction groups, a single source and no gate epilogue runs as ONE column block (128 accumulator registers per lane, a weight ring of
- * two slabs): the activation operand is read once.  0: two four-tile column blocks (rounds 1-3).  Bit-identical.  Process-wide. */
+ * two slabs): the activation operand is read once.  0: two four-tile column blocks (rounds 1-3).  Bit-identical.  Other values: MRG_E_ENUM.  Process-wide. */
 int mrg_gemm_set_wide8(int on);
 /* 1 (default, round 5): a split-core row GEMM of 129 .. 224 output columns over a reduction dimension K > 224 (D = 200: the dense
  * filters of models/operations_lp.py:266-288,356-390 forward on two operands, K = 2 D, and the paired input gradient of a MixedOp's
@@ -492,7 +480,7 @@ int mrg_gemm_set_wide8(int on);
 int mrg_gemm_set_q(int on);
 /* ABI 14.  1 (default): split-core products of at most 16 384 rows (a sampled step graph, a rank's node chunk) run on the wave-
  * autonomous kernel with two-tile column blocks -- 3.5 x more waves with a 3.5 x shorter instruction chain each; same k-order per
- * output element, bit-identical results.  0: one kernel for every row count.  on > 1 (lab): the row bound itself. */
+ * output element, bit-identical results.  0: one kernel for every row count.  Other values: MRG_E_ENUM. */
 int mrg_gemm_set_small(int on);
 /* The split-core weight gradient (mrg_linear_bwd_weight / _weight3): 1 (default) = every 32-column x 16-row operand fragment is
  * split into its bf16 planes ONCE per workgroup and shared through LDS (wgrad_x3v_k), 0 = by every wave that multiplies it
@@ -576,7 +564,7 @@ int mrg_dense_filter_fwd3(int kind, const float *s, const float *s_in, const flo
  * not -- then the multiplicand s is read by the epilogue) for mrg_gated_branch.given: colsum [blocks][2 (sum, sum of squares)][D],
  * one partial per workgroup, added inside the workgroup in a fixed order (no atomics).  blocks =
  * mrg_dense_filter3_colsum_blocks(kind, b0, b1, M, D, K); 0 = the kernel this launch would take has no such form (exact-f32 core,
- * few rows, D outside 132..224, a non-default epilogue switch): the caller keeps the statistics pass.  colsum_blocks: what the
+ * few rows, D outside 132..224): the caller keeps the statistics pass.  colsum_blocks: what the
  * caller sized colsum for (MRG_E_SHAPE when the launch would write another number). */
 int64_t mrg_dense_filter3_colsum_blocks(int kind, int64_t b0, int64_t b1, int64_t M, int D, int K);
 int mrg_dense_filter_fwd3_colsum(int kind, const float *s, const float *s_in, const float *const *W, const float *const *bias,

@@ -14,7 +14,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("MRG_LIB_PATH") or os.path.join(_HERE, "lib", "libmrgnas_hip.so")     # MRG_LIB_PATH: lab builds of the same ABI
 HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "mrgnas.h")
 
-ABI_VERSION = 22
+ABI_VERSION = 23
 
 
 class MrgnasLibraryError(RuntimeError):
@@ -72,7 +72,6 @@ SIGNATURES = {
     "mrg_dense_filter_dz": (_I, [_I, _P, _P, _P, _P, _F, _P, _P, _L, _I, _P]),
     "mrg_gemm_workspace_bytes": (_L, [_I, _I]),
     "mrg_gemm_set_mode": (_I, [_I]),
-    "mrg_gemm_set_epilogue": (_I, [_I]),
     "mrg_gemm_set_wide8": (_I, [_I]),
     "mrg_gemm_set_q": (_I, [_I]),
     "mrg_gemm_set_small": (_I, [_I]),

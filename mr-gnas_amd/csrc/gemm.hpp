@@ -81,8 +81,8 @@ struct GemmArgs {
   // (EPI_GATE_SUMS / EPI_SCALE_SUMS have no run sums: their colsum pointer travels in this slot, gemm_colsum below)
   float* seg_part;
   unsigned* relu_bits; int bits_ld;
-  // split core, one-wave kernel: stores in row order through a wave-private LDS strip (gemm_epilogue_lds); set by the launcher
-  int epi_lds; int wave_lds_floats;
+  int pad0;                           // never read; keeps wave_lds_floats and grp where the kernels' argument loads expect them
+  int wave_lds_floats;                // split core, one-wave kernel: floats of a wave's private LDS region, the A ring; set by the launcher
   GemmGroups grp;                     // split core, one-wave kernel only
 };
 
@@ -395,182 +395,6 @@ __device__ __forceinline__ void gemm_colsum_flush(const double* __restrict__ lds
     for (int q = 0; q < NSLOT; ++q) acc += lds[(q * 2 + which) * W + c];
     dst[which * N + col0 + c] = acc;
   }
-}
-
-// ---- the same epilogues on a TRANSPOSED accumulator tile (rowgemm_x3s_k<..., TR = true>) ---------------------------------------
-// With the MFMA operands exchanged, lane (li, lh) holds row rowbase + li and, in registers 4g .. 4g+3 of tile n, the columns
-// col0 + 32 n + 8 g + 4 lh + {0..3}: sixteen consecutive bytes of C.  Bias, gate multiplicand and accumulate input are read as
-// float4 and the results leave as global_store_dwordx4: 4 * NT store (and load) instructions per strip instead of 16 * NT, one
-// address computation per row instead of per (row, array).  Arithmetic and its order per element are gemm_epilogue's.
-// Requires gemm_epilogue_tr_ok (N % 4 == 0: a 4-column chunk is valid or invalid as a whole; 16-byte aligned rows).
-template <int NT, int EPI>
-__device__ __forceinline__ void gemm_epilogue_tr(const GemmArgs& a, f32x16 (&acc)[NT], int64_t rowbase, int col0, int li, int lh) {
-  if (rowbase >= a.rows) return;                           // wave-uniform: the whole 32-row strip is out of range
-  const int64_t row = rowbase + li;
-  const bool rok = row < a.rows;
-  const int64_t rc = rok ? row : a.rows - 1;
-  const int cb = col0 + 4 * lh;                            // this lane's first column of (tile 0, group 0)
-  const bool cstore = EPI != EPI_GATE || a.C != nullptr;   // EPI_GATE with C == NULL: only the gate is stored (see gemm_epilogue)
-  float* crow = cstore ? a.C + rc * a.ldc + cb : nullptr;
-  const float* srow = nullptr;
-  if (EPI == EPI_GATE && cstore) srow = a.S + rc * a.ld_s + cb;
-  if (EPI == EPI_ACCUM) srow = a.Cin + rc * a.ld_cin + cb;
-  float* xrow = (EPI == EPI_GATE && a.aux) ? a.aux + rc * a.N + cb : nullptr;
-  float cs = 1.0f;
-  if (EPI == EPI_GATE || EPI == EPI_SCALE) cs = a.scale * (a.rowscale ? a.rowscale[rc] : 1.0f);
-  const float* brow = a.bias ? a.bias + cb : nullptr;
-#pragma unroll
-  for (int n = 0; n < NT; ++n) {
-#pragma unroll
-    for (int g = 0; g < 4; ++g) {
-      const int off = n * 32 + g * 8;
-      if (cb + off >= a.N) continue;                       // beyond the last column (whole chunk)
-      float4 bv = make_float4(0.f, 0.f, 0.f, 0.f), in = make_float4(0.f, 0.f, 0.f, 0.f);
-      if (brow) bv = *reinterpret_cast<const float4*>(brow + off);
-      if (srow) in = *reinterpret_cast<const float4*>(srow + off);
-      const float bb[4] = {bv.x, bv.y, bv.z, bv.w}, ii[4] = {in.x, in.y, in.z, in.w};
-      float v[4], gt[4];
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        const float x = acc[n][4 * g + j] + bb[j];
-        if (EPI == EPI_BIAS_ACT) {
-          v[j] = (a.act == MRG_ACT_RELU) ? (x > 0.f ? x : 0.f) : (a.act == MRG_ACT_SIGMOID ? sigmoidf_fast(x) : x);
-        } else if (EPI == EPI_GATE) {
-          gt[j] = sigmoidf_fast(x);
-          v[j] = gt[j] * ii[j] * cs;
-        } else if (EPI == EPI_SCALE) {
-          v[j] = x * cs;
-        } else {
-          v[j] = x + ii[j];
-        }
-      }
-      if (rok) {
-        if (cstore) *reinterpret_cast<float4*>(crow + off) = make_float4(v[0], v[1], v[2], v[3]);
-        if (EPI == EPI_GATE && xrow) *reinterpret_cast<float4*>(xrow + off) = make_float4(gt[0], gt[1], gt[2], gt[3]);
-      }
-    }
-  }
-}
-
-// host side: may this launch run on transposed accumulators?
-template <int EPI>
-inline bool gemm_epilogue_tr_ok(const GemmArgs& a) {
-  if (EPI != EPI_BIAS_ACT && EPI != EPI_GATE && EPI != EPI_SCALE && EPI != EPI_ACCUM) return false;
-  if (a.N % 4 != 0) return false;
-  const bool gate_only = EPI == EPI_GATE && !a.C && a.aux;
-  if (!gate_only && (!a.C || a.ldc % 4 != 0 || !aligned16(a.C))) return false;
-  if (EPI == EPI_GATE && ((a.C && (a.ld_s % 4 != 0 || !aligned16(a.S))) || (a.aux && !aligned16(a.aux)))) return false;
-  if (EPI == EPI_ACCUM && (a.ld_cin % 4 != 0 || !aligned16(a.Cin))) return false;
-  if (a.bias && !aligned16(a.bias)) return false;
-  for (int i = 0; i < a.grp.n && i < 3; ++i)
-    if (a.grp.bias[i] && !aligned16(a.grp.bias[i])) return false;
-  return true;
-}
-
-// ---- the same epilogues with the stores (and the [rows, N] inputs) in ROW order, through a wave-private LDS strip -----------
-// gemm_epilogue above stores an accumulator register as it stands: one global_store_dword per (row quad, column tile) =
-// two 128-byte pieces of two rows, 16 * NT store instructions per 32-row strip.  The row GEMM's store tail is bound by the
-// NUMBER of store instructions, not by their bytes (lab: the one-wave kernel at rows 272 115, K = N = 200 spends 0.09 of its
-// 0.237 ms there; MI355X_MICROARCH.md "attention epilogue store tail", cdna_hip_programming.md T21).  Here the strip is
-// written to LDS in the accumulator layout (ds_write_b32: 32 consecutive floats per half wave, conflict free) and read back as
-// float4 in row-major order, so one global_store_dwordx4 writes 1 KB of consecutive addresses: W / 8 store instructions per
-// strip (25 instead of 112 at W = 200), and the gate multiplicand / accumulate input are read the same way.
-// Arithmetic and its order per element are those of gemm_epilogue (bit-identical results): the bias add, the activation /
-// sigmoid and the row scale of EPI_SCALE happen before the LDS round trip, the products with row-major inputs after it.
-// stage: wave-private LDS, 32 * NT * 32 + 32 floats.  Requires N % 4 == 0 and 16-byte aligned rows of C / S / aux / Cin.
-constexpr int GEMM_STAGE_PAD = 32;       // the strip's 32 row scales (EPI_GATE)
-inline size_t gemm_stage_floats(int nt) { return (size_t)32 * nt * 32 + GEMM_STAGE_PAD; }
-
-template <int NT, int EPI>
-__device__ __forceinline__ void gemm_epilogue_lds(const GemmArgs& a, f32x16 (&acc)[NT], int64_t rowbase, int col0, int lane,
-                                                  float* __restrict__ stage) {
-  if (rowbase >= a.rows) return;                            // wave-uniform
-  const int li = lane & 31, lh = lane >> 5;
-  const int W = (a.N - col0) < NT * 32 ? (a.N - col0) : NT * 32;                  // columns of this block: wave-uniform, % 4 == 0
-  const int w4 = W >> 2;
-  const int nrows = (int)((a.rows - rowbase) < 32 ? (a.rows - rowbase) : 32);
-  float* cs_lds = stage + 32 * NT * 32;
-  // ---- accumulator layout: bias, activation, (EPI_SCALE) row scale; then the strip goes to LDS as [32][W]
-  float cs[16];
-  if (EPI == EPI_GATE || EPI == EPI_SCALE) {
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      const int row = (r & 3) + 8 * (r >> 2) + 4 * lh;
-      const int rc = row < nrows ? row : nrows - 1;
-      cs[r] = a.scale * (a.rowscale ? a.rowscale[rowbase + rc] : 1.0f);
-      if (EPI == EPI_GATE && li == 0) cs_lds[row] = cs[r];
-    }
-  }
-#pragma unroll
-  for (int n = 0; n < NT; ++n) {
-    const int col = n * 32 + li;
-    const bool cok = col < W;
-    const float bv = a.bias ? a.bias[col0 + (cok ? col : 0)] : 0.f;
-    float* sp = stage + (4 * lh) * W + col;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      const float x = acc[n][r] + bv;
-      float v;
-      if (EPI == EPI_BIAS_ACT) v = (a.act == MRG_ACT_RELU) ? (x > 0.f ? x : 0.f) : (a.act == MRG_ACT_SIGMOID ? sigmoidf_fast(x) : x);
-      else if (EPI == EPI_GATE) v = sigmoidf_fast(x);
-      else if (EPI == EPI_SCALE) v = x * cs[r];
-      else v = x;
-      if (cok) sp[((r & 3) + 8 * (r >> 2)) * W] = v;
-    }
-  }
-  // (same wave: the LDS executes a wave's operations in order, no barrier)
-  // ---- row-major order: float4 q of the strip = row q / w4, columns 4 (q % w4) ...
-  const int total = nrows * w4;
-  const int sr = 64 / w4, sc = 64 - sr * w4;                 // what 64 float4 further means in (row, float4 column)
-  int r = lane / w4, c = lane - r * w4;
-  float* __restrict__ Cb = a.C + rowbase * a.ldc + col0;
-  const float* __restrict__ Sb = nullptr;
-  float* __restrict__ Xb = nullptr;
-  int ld_in = 0;
-  if (EPI == EPI_GATE) { Sb = a.S + rowbase * a.ld_s + col0; ld_in = a.ld_s; Xb = a.aux ? a.aux + rowbase * a.N + col0 : nullptr; }
-  if (EPI == EPI_ACCUM) { Sb = a.Cin + rowbase * a.ld_cin + col0; ld_in = a.ld_cin; }
-  constexpr int U = 5;                                       // float4 per lane in flight
-  for (int q0 = lane; q0 - lane < total; q0 += 64 * U) {
-    float4 v[U], in[U];
-    float csr[U];
-    int ro[U], co[U];
-    bool ok[U];
-#pragma unroll
-    for (int u = 0; u < U; ++u) {
-      const int q = q0 + 64 * u;
-      ok[u] = q < total;
-      const int rr = ok[u] ? r : 0, cc = ok[u] ? c : 0;       // clamped: loads are unconditional, only the stores are guarded
-      ro[u] = rr; co[u] = cc * 4;
-      v[u] = *reinterpret_cast<const float4*>(stage + rr * W + cc * 4);
-      if (EPI == EPI_GATE || EPI == EPI_ACCUM) in[u] = *reinterpret_cast<const float4*>(Sb + (int64_t)rr * ld_in + cc * 4);
-      if (EPI == EPI_GATE) csr[u] = cs_lds[rr];
-      c += sc; r += sr;
-      if (c >= w4) { c -= w4; ++r; }
-    }
-#pragma unroll
-    for (int u = 0; u < U; ++u) {
-      float4 o = v[u];
-      if (EPI == EPI_GATE) {
-        o.x = v[u].x * in[u].x * csr[u]; o.y = v[u].y * in[u].y * csr[u]; o.z = v[u].z * in[u].z * csr[u]; o.w = v[u].w * in[u].w * csr[u];
-      } else if (EPI == EPI_ACCUM) {
-        o.x = v[u].x + in[u].x; o.y = v[u].y + in[u].y; o.z = v[u].z + in[u].z; o.w = v[u].w + in[u].w;
-      }
-      if (ok[u]) {
-        *reinterpret_cast<float4*>(Cb + (int64_t)ro[u] * a.ldc + co[u]) = o;
-        if (EPI == EPI_GATE && Xb) *reinterpret_cast<float4*>(Xb + (int64_t)ro[u] * a.N + co[u]) = v[u];
-      }
-    }
-  }
-}
-
-// host side: may this launch use gemm_epilogue_lds?
-template <int EPI>
-inline bool gemm_epilogue_lds_ok(const GemmArgs& a) {
-  if (EPI != EPI_BIAS_ACT && EPI != EPI_GATE && EPI != EPI_SCALE && EPI != EPI_ACCUM) return false;
-  if (a.N % 4 != 0 || a.ldc % 4 != 0 || !a.C || !aligned16(a.C)) return false;
-  if (EPI == EPI_GATE && (a.ld_s % 4 != 0 || !aligned16(a.S) || (a.aux && !aligned16(a.aux)))) return false;
-  if (EPI == EPI_ACCUM && (a.ld_cin % 4 != 0 || !aligned16(a.Cin))) return false;
-  return true;
 }
 
 template <int NT, int MT, int GBK, int EPI, bool VEC4>

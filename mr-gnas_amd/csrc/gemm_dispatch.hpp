@@ -30,7 +30,7 @@ inline int gemm_mode() { return gemm_switches().mode; }
 // Measured (profiles/r5_rowgemm_q.txt, rows 558 771, interleaved rounds in one process): at K = 400 (the dense filters' forward on
 // two operands, the paired input gradient) 0.552 vs 0.584 ms (-5 %), gate-only forward -7..-12 %; at K = 200 equal (0.986-1.017): the
 // reduction dimension has to be long enough for the smaller tile's doubled weight traffic (L2 -> LDS 2.6 GB instead of 1.2 GB per
-// launch) to be paid back, so switch q == 1 (default) takes only K > X3Q_MIN_K; 2 (lab) takes every K > 48.
+// launch) to be paid back, so switch q == 1 (default) takes only K > X3Q_MIN_K; 2 (lab, tests) takes every K > 48.
 constexpr int X3Q_MIN_K = 224;
 inline bool x3q_shape(int epi, int N, int K) {
   const int q = gemm_switches().q;
@@ -98,11 +98,11 @@ inline int launch_rowgemm_x3_mode(GemmArgs a, const void* Bp, hipStream_t st) {
 
 // ---- column sums of the output as a by-product (EPI_GATE / EPI_SCALE: the MixedOp epilogue's BatchNorm statistics) ---------------
 // The workgroups (= [2][N] float64 partials) a launch of `a` would leave, or 0 when the kernel it would take has no such form: the
-// exact-f32 core and mode 2, the row-order / transposed epilogues, few-row launches on rowgemm_x3_k, and outputs that are not
+// exact-f32 core and mode 2, few-row launches on rowgemm_x3_k, and outputs that are not
 // one seven-tile column block (129..224 columns, N % 4 == 0).  The caller then keeps the statistics pass.
 inline int64_t gemm_colsum_blocks(int epi, GemmArgs a) {
   const int K = a.K1 + a.K2;
-  if ((epi != EPI_GATE && epi != EPI_SCALE) || gemm_mode() != 0 || gemm_switches().epilogue != 0) return 0;
+  if ((epi != EPI_GATE && epi != EPI_SCALE) || gemm_mode() != 0) return 0;
   if (a.N % 4 != 0 || a.N <= 128 || a.N > 224 || a.rows <= 0 || !x3_eligible(a)) return 0;
   int gbm = 128;
   if (x3q_shape(epi, a.N, K)) {

@@ -27,12 +27,8 @@
 
 namespace mrg {
 
-// TR: the MFMA operands change places (weight fragment first, activation fragment second), which transposes the accumulator
-// tile -- a lane then holds ONE row's columns 8g + 4 lh + {0..3} in registers 4g..4g+3 -- so that the epilogue loads and stores
-// 16 bytes per lane (gemm_epilogue_tr below): 4 * NT store instructions per strip instead of 16 * NT.  Same products, same
-// order of accumulation: bit-identical results.
 // Two waves per SIMD for every NT (three for NT <= 4, at most 168 registers, was tried in the lab).
-template <int NT, int EPI, bool DUAL, bool TR>
+template <int NT, int EPI, bool DUAL>
 __global__ __launch_bounds__(256, 2) void rowgemm_x3s_k(GemmArgs a, const char* __restrict__ Bp, int ntile) {
   constexpr int GBM = 128;
   constexpr int NCH = NT * 3;                   // 1 KB chunks (64 lanes x 16 B) of one pre-split B slab of this column block
@@ -123,9 +119,9 @@ __global__ __launch_bounds__(256, 2) void rowgemm_x3s_k(GemmArgs a, const char* 
       if (n1 < NT) {
         const bf16x8 Bh1 = __builtin_bit_cast(bf16x8, bq2[pp & 1][1][0]), Bm1 = __builtin_bit_cast(bf16x8, bq2[pp & 1][1][1]),
                      Bl1 = __builtin_bit_cast(bf16x8, bq2[pp & 1][1][2]);
-        x3_chain2<TR>(acc[n0], acc[n1], Ah, Am, Al, Bh0, Bm0, Bl0, Ah, Am, Al, Bh1, Bm1, Bl1);
+        x3_chain2(acc[n0], acc[n1], Ah, Am, Al, Bh0, Bm0, Bl0, Ah, Am, Al, Bh1, Bm1, Bl1);
       } else {
-        x3_chain<TR>(acc[n0], Ah, Am, Al, Bh0, Bm0, Bl0);
+        x3_chain(acc[n0], Ah, Am, Al, Bh0, Bm0, Bl0);
       }
 #pragma unroll
       for (int i = 0; i < 12; ++i) {
@@ -166,7 +162,6 @@ __global__ __launch_bounds__(256, 2) void rowgemm_x3s_k(GemmArgs a, const char* 
   }
   else if constexpr (EPI == EPI_SEGMAX) gemm_epilogue_segmax<NT>(a, acc, roww, col0, li, lh);
   else if constexpr (EPI == EPI_SEGSUM) gemm_epilogue_segsum<NT>(a, acc, roww, col0, li, lh);
-  else if constexpr (TR) gemm_epilogue_tr<NT, EPI>(a, acc, roww, col0, li, lh);
   else gemm_epilogue<NT, EPI>(a, acc, roww, col0, li, lh, row0 + GBM <= a.rows);
 }
 
@@ -183,14 +178,7 @@ inline int launch_rowgemm_x3s(GemmArgs a, const void* Bp, hipStream_t st) {
   if (a.grp.n > 0 && gemm_group_tiles(a.grp, gbm) == 0) return MRG_OK;     // grouped launch: nothing to do
   dim3 grid((unsigned)(a.grp.n > 0 ? a.grp.tile0[3] : (a.rows + gbm - 1) / gbm), (unsigned)(ntile / nt));
   size_t lds = (size_t)3 * nt * 3 * 1024;
-  bool tr = false;
-  if constexpr (EPI != EPI_SEGMAX && EPI != EPI_SEGSUM) tr = gemm_switches().epilogue == 2 && gemm_epilogue_tr_ok<EPI>(a);
-#define MRG_GOS3(NTV, DV, TV) return launch_kernel(rowgemm_x3s_k<NTV, EPI, DV, TV>, grid, dim3(256), lds, st, a, Bp, ntile)
-#define MRG_GOS2(NTV, DV)                                                                                             \
-  do {                                                                                                                \
-    if constexpr (EPI == EPI_SEGMAX || EPI == EPI_SEGSUM) MRG_GOS3(NTV, DV, false);                                   \
-    else { if (tr) MRG_GOS3(NTV, DV, true); else MRG_GOS3(NTV, DV, false); }                                          \
-  } while (0)
+#define MRG_GOS2(NTV, DV) return launch_kernel(rowgemm_x3s_k<NTV, EPI, DV>, grid, dim3(256), lds, st, a, Bp, ntile)
 #define MRG_GOS(NTV) do { if (a.K2 > 0) MRG_GOS2(NTV, true); else MRG_GOS2(NTV, false); } while (0)
   switch (nt) {
     case 1: MRG_GOS(1); break;
@@ -200,7 +188,6 @@ inline int launch_rowgemm_x3s(GemmArgs a, const void* Bp, hipStream_t st) {
   }
 #undef MRG_GOS
 #undef MRG_GOS2
-#undef MRG_GOS3
 }
 
 // EPI_GATE_SUMS / EPI_SCALE_SUMS: the seven-tile column block (129..224 columns), accumulator-order epilogue; gemm_set_colsum(a, ...) done
@@ -215,8 +202,8 @@ inline int launch_rowgemm_x3s_colsum(GemmArgs a, const void* Bp, hipStream_t st)
   if (a.grp.n > 0 && gemm_group_tiles(a.grp, 128) == 0) return MRG_OK;
   dim3 grid((unsigned)(a.grp.n > 0 ? a.grp.tile0[3] : (a.rows + 127) / 128), 1);
   const size_t lds = (size_t)3 * nt * 3 * 1024;
-  if (a.K2 > 0) return launch_kernel(rowgemm_x3s_k<7, EPI, true, false>, grid, dim3(256), lds, st, a, Bp, ntile);
-  return launch_kernel(rowgemm_x3s_k<7, EPI, false, false>, grid, dim3(256), lds, st, a, Bp, ntile);
+  if (a.K2 > 0) return launch_kernel(rowgemm_x3s_k<7, EPI, true>, grid, dim3(256), lds, st, a, Bp, ntile);
+  return launch_kernel(rowgemm_x3s_k<7, EPI, false>, grid, dim3(256), lds, st, a, Bp, ntile);
 }
 
 }  // namespace mrg

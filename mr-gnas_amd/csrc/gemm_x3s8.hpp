@@ -125,8 +125,7 @@ __global__ __launch_bounds__(256, 2) void rowgemm_x3s8_k(GemmArgs a, const char*
 template <int EPI>
 inline bool x3s8_eligible(const GemmArgs& a) {
   if (EPI == EPI_GATE) return false;                       // 55 register spills at eight tiles: keeps the two-block form
-  if (!(gemm_switches().wide8 && a.grp.n == 0 && (a.K2 == 0 || !a.A2) && a.K1 >= 32 && x3s_eligible(a))) return false;
-  return (a.N > 224 && a.N <= 256) || (gemm_switches().wide8 == 2 && a.N > 192 && a.N <= 224);   // 2 (lab): seven-tile outputs on the ring of two as well
+  return gemm_switches().wide8 && a.grp.n == 0 && (a.K2 == 0 || !a.A2) && a.K1 >= 32 && x3s_eligible(a) && a.N > 224 && a.N <= 256;
 }
 
 // Bp: the split of B prepared by launch_bsplit(..., nt = gemm_pick_nt(a.N) = 4, ...): [slab][8 tiles][plane][lane], the layout of one
@@ -135,7 +134,7 @@ template <int EPI>
 inline int launch_rowgemm_x3s8(GemmArgs a, const void* Bp, hipStream_t st) {
   if (a.rows <= 0) return MRG_OK;
   a.A2 = a.A1; a.K2 = 0;
-  const int ntile = x3_tiles(a.N, gemm_pick_nt(a.N));      // 8 (7: the lab's seven-tile form)
+  const int ntile = x3_tiles(a.N, gemm_pick_nt(a.N));      // 8 for what x3s8_eligible admits (7: a seven-tile output, which only a direct call brings here)
   dim3 grid((unsigned)((a.rows + 127) / 128), 1);
   const size_t lds = (size_t)2 * ntile * 3 * 1024;
   if (ntile == 8) return launch_kernel(rowgemm_x3s8_k<8, EPI>, grid, dim3(256), lds, st, a, Bp, ntile);

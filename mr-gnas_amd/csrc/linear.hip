@@ -97,26 +97,20 @@ extern "C" int mrg_gemm_set_mode(int mode) {
 }
 
 extern "C" int mrg_gemm_set_wide8(int on) {
-  if (on < 0 || on > 2) return MRG_E_ENUM;          // 2 (lab): seven-tile plain launches on the ring-of-two kernel as well
+  if (on < 0 || on > 1) return MRG_E_ENUM;
   gemm_switches().wide8 = on;
   return MRG_OK;
 }
 
 extern "C" int mrg_gemm_set_small(int on) {
-  if (on < 0) return MRG_E_ENUM;
-  gemm_switches().small_rows = on == 1 ? X3N_MAX_ROWS : (int64_t)on;      // 0 off, 1 the default bound, > 1 (lab) that many rows
+  if (on < 0 || on > 1) return MRG_E_ENUM;
+  gemm_switches().small_rows = on ? X3N_MAX_ROWS : 0;      // 0 off, 1 the row bound
   return MRG_OK;
 }
 
 extern "C" int mrg_gemm_set_q(int on) {
   if (on < 0 || on > 2) return MRG_E_ENUM;          // 2 (lab, tests): every eligible K, not only K > 224
   gemm_switches().q = on;
-  return MRG_OK;
-}
-
-extern "C" int mrg_gemm_set_epilogue(int mode) {
-  if (mode < 0 || mode > 2) return MRG_E_ENUM;
-  gemm_switches().epilogue = mode;
   return MRG_OK;
 }
 

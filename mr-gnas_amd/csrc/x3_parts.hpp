@@ -48,21 +48,8 @@ struct GemmSwitches {
   // (gemm_dispatch.hpp: x3n_shape); 0 = off.
   int64_t small_rows = X3N_MAX_ROWS;
   // mrg_gemm_set_wide8.  1 (default): plain launches whose output is eight column tiles wide run on rowgemm_x3s8_k; 0: two
-  // four-tile column blocks (round 3); 2 (lab): seven-tile outputs on the ring of two as well.
+  // four-tile column blocks (round 3).
   int wide8 = 1;
-  // mrg_gemm_set_epilogue.  0 (default): accumulator-order stores.
-  // 1: row-order 16-byte stores through LDS where the operands allow (wave-autonomous kernel, gemm_epilogue_lds).  Round 3 measured
-  // the store tail NOT to be bound by the number of store instructions: with 4.5x fewer (25 instead of 112 per strip) the plain
-  // epilogue is 9 % slower alone (0.249 vs 0.228 ms at rows 272 115, K = N = 200; the LDS round trip is pure overhead), the
-  // accumulate epilogue 5-8 % faster (its input is read in row order too), the gate epilogue equal; in the supernet step the row
-  // GEMM entry points lose 0.9 ms / step in total (profiles/r3_rowgemm_epilogue.txt).  Kept as a tested option.
-  // 2 (round 4): TRANSPOSED accumulators in the LDS-weight kernel (gemm_x3s.hpp, gemm_epilogue_tr): the MFMA operands change
-  // places, a lane owns one row's 4-column chunks, and every epilogue load / store is 16 bytes per lane with no LDS round trip (28
-  // store instructions per 32-row strip instead of 112).  Bit-identical, and SLOWER (rows 558 771, K = N = 200: plain 0.426 vs
-  // 0.393 ms, accumulate 0.598 vs 0.463, gate 0.717 vs 0.611): a store instruction that writes 32 rows x 32 bytes costs the memory
-  // pipeline more than one that writes 2 rows x 128 bytes, and the epilogue is not bound by its instruction count -- the same
-  // 112 stores alone, at the kernel's grid, move 4.0 TB/s (profiles/r4_rowgemm_phases.txt).  Kept as a tested comparison point.
-  int epilogue = 0;
   // mrg_wgrad_set_variant.  1 (default): weight-gradient fragments split once per workgroup (wgrad_x3v_k); 0: by every consuming
   // wave (wgrad_x3_k).
   int wgrad_variant = 1;
@@ -106,52 +93,42 @@ __device__ __forceinline__ void split_pair_of(const v4f (&x)[2], int q, u32x4& H
 }
 
 // One matrix instruction of the chain: 32 x 32 x 16 on a 16-register accumulator, 16 x 16 x 32 on a 4-register one (gemm_x3q.hpp).
-// TR: the operands change places, which transposes the accumulator tile (gemm_x3s.hpp) -- same products, same sums.
-template <bool TR>
-__device__ __forceinline__ f32x16 x3_mm(bf16x8 a, bf16x8 b, f32x16 c) {
-  if constexpr (TR) return __builtin_amdgcn_mfma_f32_32x32x16_bf16(b, a, c, 0, 0, 0);
-  else return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0);
-}
-template <bool TR>
-__device__ __forceinline__ f32x4v x3_mm(bf16x8 a, bf16x8 b, f32x4v c) {
-  static_assert(!TR, "the 16 x 16 x 32 kernel has no transposed form");
-  return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0);
-}
+__device__ __forceinline__ f32x16 x3_mm(bf16x8 a, bf16x8 b, f32x16 c) { return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0); }
+__device__ __forceinline__ f32x4v x3_mm(bf16x8 a, bf16x8 b, f32x4v c) { return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0); }
 // THE TERM ORDER of every split-core kernel: Am*Bm, Al*Bh, Ah*Bl, Am*Bh, Ah*Bm, Ah*Bh -- small terms first, the leading term
 // last, so that the small ones are not rounded away against an accumulator that already holds the large one.  Every accumulator
 // of every kernel receives its six terms in this order; that (and the order of the k-slabs) is what makes the kernels agree bit
 // for bit.
 // One accumulator (a single chain: each MFMA waits for its predecessor):
-template <bool TR = false, class ACC>
+template <class ACC>
 __device__ __forceinline__ void x3_chain(ACC& c, bf16x8 Ah, bf16x8 Am, bf16x8 Al, bf16x8 Bh, bf16x8 Bm, bf16x8 Bl) {
-  c = x3_mm<TR>(Am, Bm, c);
-  c = x3_mm<TR>(Al, Bh, c);
-  c = x3_mm<TR>(Ah, Bl, c);
-  c = x3_mm<TR>(Am, Bh, c);
-  c = x3_mm<TR>(Ah, Bm, c);
-  c = x3_mm<TR>(Ah, Bh, c);
+  c = x3_mm(Am, Bm, c);
+  c = x3_mm(Al, Bh, c);
+  c = x3_mm(Ah, Bl, c);
+  c = x3_mm(Am, Bh, c);
+  c = x3_mm(Ah, Bm, c);
+  c = x3_mm(Ah, Bh, c);
 }
 // Two accumulators interleaved (a dependent MFMA issued back to back costs ~6 extra cycles, measured with
 // tools/mfma_bf16_peak.hip; with another accumulator's MFMA in between the pipe stays busy): accumulator i takes A_i * B_i.
 // The callers pass the same A twice (two column tiles of one row tile) or the same B twice (two row tiles of one column tile).
-template <bool TR = false>
 __device__ __forceinline__ void x3_chain2(f32x16& c0, f32x16& c1, bf16x8 Ah0, bf16x8 Am0, bf16x8 Al0, bf16x8 Bh0, bf16x8 Bm0, bf16x8 Bl0,
                                           bf16x8 Ah1, bf16x8 Am1, bf16x8 Al1, bf16x8 Bh1, bf16x8 Bm1, bf16x8 Bl1) {
-  c0 = x3_mm<TR>(Am0, Bm0, c0); c1 = x3_mm<TR>(Am1, Bm1, c1);
-  c0 = x3_mm<TR>(Al0, Bh0, c0); c1 = x3_mm<TR>(Al1, Bh1, c1);
-  c0 = x3_mm<TR>(Ah0, Bl0, c0); c1 = x3_mm<TR>(Ah1, Bl1, c1);
-  c0 = x3_mm<TR>(Am0, Bh0, c0); c1 = x3_mm<TR>(Am1, Bh1, c1);
-  c0 = x3_mm<TR>(Ah0, Bm0, c0); c1 = x3_mm<TR>(Ah1, Bm1, c1);
-  c0 = x3_mm<TR>(Ah0, Bh0, c0); c1 = x3_mm<TR>(Ah1, Bh1, c1);
+  c0 = x3_mm(Am0, Bm0, c0); c1 = x3_mm(Am1, Bm1, c1);
+  c0 = x3_mm(Al0, Bh0, c0); c1 = x3_mm(Al1, Bh1, c1);
+  c0 = x3_mm(Ah0, Bl0, c0); c1 = x3_mm(Ah1, Bl1, c1);
+  c0 = x3_mm(Am0, Bh0, c0); c1 = x3_mm(Am1, Bh1, c1);
+  c0 = x3_mm(Ah0, Bm0, c0); c1 = x3_mm(Ah1, Bm1, c1);
+  c0 = x3_mm(Ah0, Bh0, c0); c1 = x3_mm(Ah1, Bh1, c1);
 }
 // MT = 1 or 2 row tiles of column tile n against one weight fragment (the wave-autonomous kernels)
-template <bool TR = false, int MT, int NT>
+template <int MT, int NT>
 __device__ __forceinline__ void x3_chain_rows(f32x16 (&acc)[MT][NT], int n, const u32x4 (&Ah)[MT], const u32x4 (&Am)[MT], const u32x4 (&Al)[MT],
                                               bf16x8 Bh, bf16x8 Bm, bf16x8 Bl) {
   static_assert(MT == 1 || MT == 2, "one or two row tiles per wave");
   auto c = [](const u32x4& v) { return __builtin_bit_cast(bf16x8, v); };
-  if constexpr (MT == 2) x3_chain2<TR>(acc[0][n], acc[1][n], c(Ah[0]), c(Am[0]), c(Al[0]), Bh, Bm, Bl, c(Ah[1]), c(Am[1]), c(Al[1]), Bh, Bm, Bl);
-  else x3_chain<TR>(acc[0][n], c(Ah[0]), c(Am[0]), c(Al[0]), Bh, Bm, Bl);
+  if constexpr (MT == 2) x3_chain2(acc[0][n], acc[1][n], c(Ah[0]), c(Am[0]), c(Al[0]), Bh, Bm, Bl, c(Ah[1]), c(Am[1]), c(Al[1]), Bh, Bm, Bl);
+  else x3_chain(acc[0][n], c(Ah[0]), c(Am[0]), c(Al[0]), Bh, Bm, Bl);
 }
 
 // ---- weight split ------------------------------------------------------------------------------------------------------------

@@ -44,6 +44,15 @@ def test_argument_errors_without_gpu():
     assert lib.mrg_distmult_score(None, P(16), P(16), P(16), P(16), P(16), 4, 8, None) == -1
     assert lib.mrg_distmult_score(P(16), P(16), P(16), P(16), P(16), P(16), 4, 0, None) == -2
     assert lib.mrg_gemm_set_mode(7) == -3 and lib.mrg_gemm_set_mode(3) == -3 and lib.mrg_gemm_set_mode(-1) == -3 and lib.mrg_gemm_set_mode(2) == 0 and lib.mrg_gemm_set_mode(0) == 0
+    # the kernel switches take their documented values only; the store-order switch left the library at ABI 23
+    assert not hasattr(lib, "mrg_gemm_set_epilogue")
+    try:
+        assert lib.mrg_gemm_set_wide8(2) == -3 and lib.mrg_gemm_set_small(2) == -3 and lib.mrg_gemm_set_small(-1) == -3
+        assert lib.mrg_gemm_set_wide8(0) == 0 and lib.mrg_gemm_set_wide8(1) == 0
+        assert lib.mrg_gemm_set_small(0) == 0 and lib.mrg_gemm_set_small(1) == 0
+        assert lib.mrg_gemm_set_q(2) == 0 and lib.mrg_gemm_set_mode(2) == 0
+    finally:
+        assert lib.mrg_gemm_set_wide8(1) == 0 and lib.mrg_gemm_set_small(1) == 0 and lib.mrg_gemm_set_q(1) == 0 and lib.mrg_gemm_set_mode(0) == 0
     assert lib.mrg_gemm_workspace_bytes(400, 200) >= 400 * 200 * 4 and lib.mrg_gemm_workspace_bytes(0, 200) == 0
     assert lib.mrg_linear_fwd(P(16), P(16), None, P(16), None, 0, 8, 8, 0, None) == 0  # zero rows
     assert lib.mrg_linear_fwd(None, P(16), None, P(16), None, 4, 8, 8, 0, None) == -1

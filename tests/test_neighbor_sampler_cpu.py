@@ -194,7 +194,7 @@ def test_bad_draws_raise():
 # ---- the host side of the C ABI ----------------------------------------------------------------------------------------------------
 def test_the_library_declares_the_entry_points_at_abi_22():
     lib = _lib.load()
-    assert _lib.ABI_VERSION == 22 and lib.mrg_abi_version() == 22
+    assert _lib.ABI_VERSION == 23 and lib.mrg_abi_version() == 23
     for name in NEW:
         assert name in _lib.SIGNATURES and name in _lib.declared_symbols() and hasattr(lib, name)
 

@@ -921,13 +921,12 @@ def test_partial_form_with_one_output_unused(N, E, R, D, hub):
 @pytest.mark.parametrize("rows,K1,K2,Nout", [(70001, 200, 0, 200), (66000, 200, 200, 200), (513, 64, 0, 40), (259, 400, 0, 8), (65537, 128, 0, 452),
                                              (300001, 128, 0, 128), (33, 200, 0, 200), (20000, 96, 0, 96), (9000, 52, 0, 300), (131073, 256, 0, 256)])
 def test_split_core_kernels_are_bit_exact_with_each_other(rows, K1, K2, Nout):
-    """The four forms of the split-core row GEMM compute the same sums in the same order: the default kernel with the
-    weight slabs shared through LDS (mode 0, gemm_x3s.hpp) with accumulator-order stores (the default) and on transposed
-    accumulators with 16-byte epilogue accesses (mrg_gemm_set_epilogue(2), round 4's comparison point), the wave-autonomous kernel
-    (mode 2) with accumulator-order stores and with row-order 16-byte stores through LDS (mrg_gemm_set_epilogue(1)).  Bias / ReLU / sigmoid, gate (+ stored
-    gate), row scale, accumulate -- bit-identical outputs; ragged last strips, partial last column tiles, two column blocks,
-    both row-tile shapes, dual-source K.  Third switch: the eight-tile column block of a 256-wide output (gemm_x3s8.hpp, the
-    default for 224 < N <= 256) against the 2 x 4-tile kernel (mrg_gemm_set_wide8(0))."""
+    """The forms of the split-core row GEMM compute the same sums in the same order: the default kernel with the weight slabs
+    shared through LDS (mode 0, gemm_x3s.hpp) and the wave-autonomous kernel (mode 2, gemm_x3.hpp).  Bias / ReLU / sigmoid,
+    gate (+ stored gate), row scale, accumulate -- bit-identical outputs; ragged last strips, partial last column tiles, two
+    column blocks, both row-tile shapes, dual-source K.  Second switch: the eight-tile column block of a 256-wide output
+    (gemm_x3s8.hpp, the default for 224 < N <= 256) against the 2 x 4-tile kernel (mrg_gemm_set_wide8(0)).  Orders are
+    (mode, wide8): (0, 1) is the base, (0, 0) and (2, 1) are compared with it."""
     from mr_gnas_amd._lib import call, ptr, stream_of
     lib = mr_gnas_amd._lib.load()
     gen = torch.Generator().manual_seed(rows + Nout + K2)
@@ -942,8 +941,8 @@ def test_split_core_kernels_are_bit_exact_with_each_other(rows, K1, K2, Nout):
     res = {}
     try:
         assert lib.mrg_gemm_set_q(0) == 0           # the 16 x 16 x 32 kernel (round 5) sums k 32 at a time: equal to rounding, tested below
-        for order in ((0, 0, 1), (0, 0, 0), (0, 2, 0), (2, 0, 1), (2, 1, 1)):
-            assert lib.mrg_gemm_set_mode(order[0]) == 0 and lib.mrg_gemm_set_epilogue(order[1]) == 0 and lib.mrg_gemm_set_wide8(order[2]) == 0
+        for order in ((0, 1), (0, 0), (2, 1)):
+            assert lib.mrg_gemm_set_mode(order[0]) == 0 and lib.mrg_gemm_set_wide8(order[1]) == 0
             outs = []
             if K2 == 0:
                 for act in (None, "relu", "sigmoid"):
@@ -964,14 +963,13 @@ def test_split_core_kernels_are_bit_exact_with_each_other(rows, K1, K2, Nout):
                     outs += [out] + ([gate] if gate is not None else [])
             res[order] = outs
     finally:
-        lib.mrg_gemm_set_epilogue(0)
         lib.mrg_gemm_set_mode(0)
         lib.mrg_gemm_set_wide8(1)
         lib.mrg_gemm_set_q(1)
-    assert len(res[(0, 0, 1)]) > 0
-    for other in ((0, 0, 0), (0, 2, 0), (2, 0, 1), (2, 1, 1)):
-        assert len(res[other]) == len(res[(0, 0, 1)])
-        for i, (x, y) in enumerate(zip(res[(0, 0, 1)], res[other])):
+    assert len(res[(0, 1)]) > 0
+    for other in ((0, 0), (2, 1)):
+        assert len(res[other]) == len(res[(0, 1)])
+        for i, (x, y) in enumerate(zip(res[(0, 1)], res[other])):
             assert torch.equal(x, y), (other, i, float((x - y).abs().max()))
 
 

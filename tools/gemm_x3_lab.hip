@@ -40,38 +40,18 @@ int main(int argc, char** argv) {
     printf("%-28s %8.3f ms  %7.1f TF/s (f32-equivalent)  err=%s\n", name, ms, 2.0 * rows * K * N / ms * 1e-9, hipGetErrorString(hipGetLastError()));
   };
   timeit("x3 (split + gemm)", [&] { launch_bsplit(B, K, 1, N, K, nt, Bp, 0); launch_rowgemm_x3<EPI_BIAS_ACT>(a, Bp, 0); });
-  gemm_switches().epilogue = 0;
-  timeit("x3 (gemm only, acc-order stores)", [&] { launch_rowgemm_x3<EPI_BIAS_ACT>(a, Bp, 0); });
-  std::vector<float> c0(rows * N);
-  hipMemcpy(c0.data(), C, c0.size() * 4, hipMemcpyDeviceToHost);
-  hipMemset(C, 0, rows * N * 4);
-  gemm_switches().epilogue = 1;
-  timeit("x3 (gemm only, row-order stores)", [&] { launch_rowgemm_x3<EPI_BIAS_ACT>(a, Bp, 0); });
-  {
-    std::vector<float> cx(rows * N);
-    hipMemcpy(cx.data(), C, cx.size() * 4, hipMemcpyDeviceToHost);
-    int64_t bad = 0;
-    for (size_t i = 0; i < cx.size(); ++i) bad += (cx[i] != c0[i]);
-    printf("row-order vs acc-order stores: %lld of %lld outputs differ\n", (long long)bad, (long long)cx.size());
-  }
-  {   // accumulate epilogue (C += ...) both ways
+  timeit("x3 (gemm only)", [&] { launch_rowgemm_x3<EPI_BIAS_ACT>(a, Bp, 0); });
+  {   // accumulate epilogue (C += ...) and gate
     GemmArgs g = a; g.Cin = C2; g.ld_cin = N; g.bias = nullptr;
     hipMemset(C2, 0, rows * N * 4);
-    gemm_switches().epilogue = 0;
-    timeit("x3 accumulate, acc-order", [&] { launch_rowgemm_x3<EPI_ACCUM>(g, Bp, 0); });
-    gemm_switches().epilogue = 1;
-    timeit("x3 accumulate, row-order", [&] { launch_rowgemm_x3<EPI_ACCUM>(g, Bp, 0); });
-    GemmArgs q = a; q.S = A1; q.ld_s = K1; q.aux = C2; q.scale = 1.f / 3; 
+    timeit("x3 accumulate", [&] { launch_rowgemm_x3<EPI_ACCUM>(g, Bp, 0); });
     if (K1 == N) {
-      gemm_switches().epilogue = 0;
-      timeit("x3 gate (+aux), acc-order", [&] { launch_rowgemm_x3<EPI_GATE>(q, Bp, 0); });
-      gemm_switches().epilogue = 1;
-      timeit("x3 gate (+aux), row-order", [&] { launch_rowgemm_x3<EPI_GATE>(q, Bp, 0); });
+      GemmArgs q = a; q.S = A1; q.ld_s = K1; q.aux = C2; q.scale = 1.f / 3;
+      timeit("x3 gate (+aux)", [&] { launch_rowgemm_x3<EPI_GATE>(q, Bp, 0); });
     }
     launch_rowgemm_x3<EPI_BIAS_ACT>(a, Bp, 0);      // C as the error check below expects it
   }
   {
-    gemm_switches().epilogue = 0;
     launch_rowgemm_x3<EPI_BIAS_ACT>(a, Bp, 0);
     std::vector<float> cref(rows * N), cs(rows * N);
     hipMemcpy(cref.data(), C, cref.size() * 4, hipMemcpyDeviceToHost);
@@ -89,9 +69,7 @@ int main(int argc, char** argv) {
     }
     launch_rowgemm_x3<EPI_BIAS_ACT>(a, Bp, 0);
   }
-  if (getenv("MRG_LAB_RING2")) gemm_switches().wide8 = 2;   // seven-tile outputs on the ring-of-two kernel as well
   if (x3s8_eligible<EPI_BIAS_ACT>(a)) {   // round 4: eight column tiles as ONE block (gemm_x3s8.hpp) against two four-tile blocks
-    gemm_switches().epilogue = 0;
     launch_rowgemm_x3<EPI_BIAS_ACT>(a, Bp, 0);
     std::vector<float> cref(rows * N), cs(rows * N);
     hipMemcpy(cref.data(), C, cref.size() * 4, hipMemcpyDeviceToHost);
@@ -106,37 +84,6 @@ int main(int argc, char** argv) {
     GemmArgs g = a; g.Cin = C2; g.ld_cin = N; g.bias = nullptr;
     timeit("x3s accumulate, 2 x 4 tiles", [&] { launch_rowgemm_x3s<EPI_ACCUM>(g, Bp, 0); });
     timeit("x3s8 accumulate", [&] { launch_rowgemm_x3s8<EPI_ACCUM>(g, Bp, 0); });
-    launch_rowgemm_x3<EPI_BIAS_ACT>(a, Bp, 0);
-  }
-  {   // round 4: transposed accumulators (16-byte epilogue accesses) against accumulator-order stores, every epilogue, bit for bit
-    std::vector<float> r0(rows * N), r1(rows * N), x0(rows * N), x1(rows * N);
-    float* AUX; hipMalloc(&AUX, rows * N * 4);
-    auto cmp = [&](const char* what, std::vector<float>& u, std::vector<float>& v) {
-      int64_t bad = 0; for (size_t i = 0; i < u.size(); ++i) bad += (u[i] != v[i]);
-      printf("   %s: %lld of %lld outputs differ between the two accumulator layouts\n", what, (long long)bad, (long long)u.size());
-    };
-    for (int e = 0; e < 4; ++e) {
-      if ((e == 2 || e == 3) && K1 != N) continue;
-      GemmArgs g = a;
-      const char* name = e == 0 ? "bias+act" : e == 1 ? "accumulate" : e == 2 ? "gate (+aux)" : "gate only";
-      if (e == 1) { g.Cin = C2; g.ld_cin = N; g.bias = nullptr; }
-      if (e == 2 || e == 3) { g.S = A1; g.ld_s = K1; g.aux = AUX; g.scale = 1.f / 3; if (e == 3) g.C = nullptr; }
-      for (int mode = 0; mode <= 2; mode += 2) {
-        gemm_switches().epilogue = mode;
-        hipMemset(C, 0, rows * N * 4); hipMemset(AUX, 0, rows * N * 4);
-        char label[96]; snprintf(label, sizeof label, "x3s %s, %s", name, mode ? "transposed acc" : "acc-order");
-        timeit(label, [&] {
-          if (e == 0) launch_rowgemm_x3s<EPI_BIAS_ACT>(g, Bp, 0); else if (e == 1) launch_rowgemm_x3s<EPI_ACCUM>(g, Bp, 0);
-          else launch_rowgemm_x3s<EPI_GATE>(g, Bp, 0);
-        });
-        hipMemcpy((mode ? r1 : r0).data(), C, r0.size() * 4, hipMemcpyDeviceToHost);
-        hipMemcpy((mode ? x1 : x0).data(), AUX, x0.size() * 4, hipMemcpyDeviceToHost);
-      }
-      cmp(name, r0, r1);
-      if (e >= 2) cmp("its gate", x0, x1);
-    }
-    gemm_switches().epilogue = 2;
-    hipFree(AUX);
     launch_rowgemm_x3<EPI_BIAS_ACT>(a, Bp, 0);
   }
   if (x3p_eligible(a)) {

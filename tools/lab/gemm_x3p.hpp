@@ -34,6 +34,18 @@ namespace mrg {
 
 typedef float v4f_t __attribute__((ext_vector_type(4)));
 
+// x3_chain_rows (x3_parts.hpp: same six terms, same order, row tiles interleaved) with the MFMA operands exchanged -- weight fragment
+// first, activation fragment second -- which transposes the accumulator tile.
+template <int MT, int NT>
+__device__ __forceinline__ void x3p_chain_rows_t(f32x16 (&acc)[MT][NT], int n, const u32x4 (&Ah)[MT], const u32x4 (&Am)[MT], const u32x4 (&Al)[MT],
+                                                 bf16x8 Bh, bf16x8 Bm, bf16x8 Bl) {
+  auto term = [&](const u32x4 (&A)[MT], bf16x8 B) {
+#pragma unroll
+    for (int m = 0; m < MT; ++m) acc[m][n] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(B, __builtin_bit_cast(bf16x8, A[m]), acc[m][n], 0, 0, 0);
+  };
+  term(Am, Bm); term(Al, Bh); term(Ah, Bl); term(Am, Bh); term(Ah, Bm); term(Ah, Bh);
+}
+
 template <int EPI> struct X3pEpiOps {      // lower bound of vector-memory instructions one FULL column tile of one row tile issues
   static constexpr int value = 4;          // 4 float4 stores (the gate's S loads / aux stores, the accumulate loads only add to it)
 };
@@ -173,7 +185,7 @@ __global__ __launch_bounds__(X3_THREADS, 1) void rowgemm_x3p_k(GemmArgs a, const
       const bf16x8 Bh = __builtin_bit_cast(bf16x8, bq[n][0]), Bm = __builtin_bit_cast(bf16x8, bq[n][1]),
                    Bl = __builtin_bit_cast(bf16x8, bq[n][2]);
       // transposed product: the weight fragment is the A operand, the activation fragment the B operand
-      x3_chain_rows<true>(acc, n, ch, cm, cl, Bh, Bm, Bl);
+      x3p_chain_rows_t(acc, n, ch, cm, cl, Bh, Bm, Bl);
       if (n == NT - 1) {
 #pragma unroll
         for (int m = 0; m < MT; ++m) { ch[m] = nh[m]; cm[m] = nm[m]; cl[m] = nl[m]; }
