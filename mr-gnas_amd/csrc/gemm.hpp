@@ -37,6 +37,11 @@ enum { EPI_BIAS_ACT = 0, EPI_GATE = 1, EPI_SCALE = 2, EPI_ACCUM = 3, EPI_SEGMAX 
 enum { EPI_GATE_SUMS = 6, EPI_SCALE_SUMS = 7 };
 constexpr bool epi_sums(int epi) { return epi == EPI_GATE_SUMS || epi == EPI_SCALE_SUMS; }
 constexpr int epi_base(int epi) { return epi == EPI_GATE_SUMS ? EPI_GATE : (epi == EPI_SCALE_SUMS ? EPI_SCALE : epi); }
+// The counting epilogues of mrg_distmult_rank (rank.hip; gemm_epilogue_rank / gemm_epilogue_rank_diag below): rows are queries, columns
+// are entities, nothing is stored.  EPI_RANK_DIAG multiplies row block x by COLUMN block x (the rows' gathered targets) and keeps the
+// diagonal.  Kernel instances of their own, like the column-sum kinds.
+enum { EPI_RANK = 8, EPI_RANK_DIAG = 9 };
+constexpr bool epi_diag(int epi) { return epi == EPI_RANK_DIAG; }
 
 // Up to three row ranges of ONE launch of the split-core row GEMM that share every tensor but differ in the weight matrix
 // (the in / out / self direction segments of a dense filter: one launch instead of three).  Workgroup blocks
@@ -103,6 +108,109 @@ __device__ __forceinline__ const float* gemm_a_ptr(const float* r1, const float*
     return (first ? r1 : r2) + (kk + 4 <= ld ? kk : ld - 4);
   }
   return r1 + (k + 4 <= K ? k : K - 4);
+}
+
+// EPI_RANK / EPI_RANK_DIAG: what the counting epilogues read and write.  The pointers travel in slots of GemmArgs that these kinds do
+// not otherwise use (S, aux, row_seg, Cin, rowscale, relu_bits), so the argument block -- and with it the code of every other
+// kernel instance -- stays what it was.  row_index stays NULL.
+struct RankEpi {
+  const float* tscore;        // EPI_RANK: [rows] the target's score of each query, formed by EPI_RANK_DIAG on the same tile routine
+  float* tscore_out;          // EPI_RANK_DIAG: where it goes
+  const int32_t* qinfo;       // [rows][4]: target entity, begin and end of the query's filter list in members / gone_at, `when`
+  const int32_t* members;     // filter lists: entity ids, ascending inside a list
+  const int32_t* gone_at;     // per member: filtered iff gone_at > when
+  unsigned* counts;           // [rows], zeroed: candidates that beat the target
+};
+inline void gemm_set_rank(GemmArgs& a, const RankEpi& r) {
+  a.S = r.tscore; a.aux = r.tscore_out; a.row_seg = r.qinfo;
+  a.Cin = reinterpret_cast<const float*>(r.members); a.rowscale = reinterpret_cast<const float*>(r.gone_at); a.relu_bits = r.counts;
+}
+__device__ __forceinline__ RankEpi gemm_rank(const GemmArgs& a) {
+  return RankEpi{a.S, a.aux, a.row_seg, reinterpret_cast<const int32_t*>(a.Cin), reinterpret_cast<const int32_t*>(a.rowscale), a.relu_bits};
+}
+
+// ---- DistMult ranking: "how many columns beat this row's target" as the GEMM's epilogue (reference utils/utils_rgcn.py:212-380) --
+// Candidate `col` of query `row` counts iff it exists, is not the target, is not filtered, and beats the target under the rule of
+// mrg_rank_filtered: score greater, or equal with the lower entity id.  The comparison and the filter decision are taken on the SAME
+// accumulator value, once per (query, candidate): a ballot per accumulator register turns the 32 x 32 comparisons of a tile into one
+// 32-bit column mask per row, lane l < 32 collects the masks of row l, walks the slice of that row's ascending filter list that falls
+// into the workgroup's column range (binary search for its start), clears the bits of the members still in force (gone_at > when),
+// and publishes ONE integer atomicAdd per (row, workgroup).  Integer atomics only: the counts do not depend on their order.
+// The target's score comes from gemm_epilogue_rank_diag: the same k-order and term order on the same operand values, so a
+// duplicate of the target's entity row scores bit-identically and ties.
+template <int NT>
+__device__ __forceinline__ void gemm_epilogue_rank(const GemmArgs& a, f32x16 (&acc)[NT], int64_t rowbase, int col0, int li, int lh) {
+  if (rowbase >= a.rows) return;
+  const RankEpi k = gemm_rank(a);
+  float ts[16];
+  int tg[16];
+#pragma unroll
+  for (int r = 0; r < 16; ++r) {
+    const int64_t row = rowbase + (r & 3) + 8 * (r >> 2) + 4 * lh;
+    const int64_t rc = row < a.rows ? row : a.rows - 1;
+    ts[r] = k.tscore[rc];
+    tg[r] = k.qinfo[rc * 4];
+  }
+  const int lane = lh * 32 + li;
+  unsigned word[NT];                                         // lane l < 32: the column masks of row rowbase + l
+#pragma unroll
+  for (int n = 0; n < NT; ++n) {
+    const int col = col0 + n * 32 + li;
+    const bool cok = col < a.N;
+    unsigned w = 0;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+      const float x = acc[n][r];
+      const bool hit = cok && col != tg[r] && (x > ts[r] || (x == ts[r] && col < tg[r]));
+      const unsigned long long ball = __ballot(hit);         // lanes 0-31: this register's row of half 0, lanes 32-63: of half 1
+      const int rl = (r & 3) + 8 * (r >> 2);
+      w = lane == rl ? (unsigned)ball : (lane == rl + 4 ? (unsigned)(ball >> 32) : w);
+    }
+    word[n] = w;
+  }
+  const int64_t row = rowbase + lane;
+  if (lane >= 32 || row >= a.rows) return;
+  const int4 qi = *reinterpret_cast<const int4*>(k.qinfo + row * 4);
+  const int hi = qi.z, when = qi.w;
+  if (qi.y < hi) {
+    const int cend = col0 + NT * 32;
+    int b = qi.y, e = hi;
+    while (b < e) {                                          // first member >= col0
+      const int mid = b + ((e - b) >> 1);
+      if (k.members[mid] < col0) b = mid + 1; else e = mid;
+    }
+    for (; b < hi; ++b) {
+      const int m = k.members[b];
+      if (m >= cend) break;
+      if (k.gone_at[b] > when) {
+        const int d = m - col0;
+#pragma unroll
+        for (int n = 0; n < NT; ++n) word[n] &= ~((d >> 5) == n ? 1u << (d & 31) : 0u);
+      }
+    }
+  }
+  unsigned cnt = 0;
+#pragma unroll
+  for (int n = 0; n < NT; ++n) cnt += __popc(word[n]);
+  if (cnt) atomicAdd(k.counts + row, cnt);
+}
+
+// EPI_RANK_DIAG: row block x against column block x, whose 128 columns are the gathered target rows of the block's 128 queries
+// (NT = 4: wave w's rows meet their own targets in column tile w).  tscore_out[row] = the accumulator of (row, row's own column).
+template <int NT>
+__device__ __forceinline__ void gemm_epilogue_rank_diag(const GemmArgs& a, f32x16 (&acc)[NT], int64_t rowbase, int wave, int li, int lh) {
+  static_assert(NT == 4, "the diagonal of a 128 x 128 block");
+  if (rowbase >= a.rows) return;
+  float* __restrict__ out = gemm_rank(a).tscore_out;
+#pragma unroll
+  for (int n = 0; n < NT; ++n) {
+    if (n != wave) continue;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+      const int rl = (r & 3) + 8 * (r >> 2) + 4 * lh;
+      if (li == rl && rowbase + rl < a.rows) out[rowbase + rl] = acc[n][r];
+    }
+  }
 }
 
 // ---- a_max: ReLU + destination-segmented max as the GEMM's epilogue (reference models/operations_lp.py:230-234) ----------
@@ -409,7 +517,7 @@ __global__ __launch_bounds__(MRG_BLOCK, (MT == 1 ? 2 : 1)) void rowgemm_k(GemmAr
   constexpr int A_TILE = GBM * GLD, B_TILE = NT * 32 * GLD, STAGE = A_TILE + B_TILE;
   const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, li = lane & 31, lh = lane >> 5;
   const int64_t row0 = (int64_t)blockIdx.x * GBM;
-  const int col0 = blockIdx.y * (NT * 32);
+  const int col0 = (epi_diag(EPI) ? blockIdx.x : blockIdx.y) * (NT * 32);
   const int K = a.K1 + a.K2;
   const int nkt = (K + GBK - 1) / GBK;
 
@@ -506,8 +614,11 @@ __global__ __launch_bounds__(MRG_BLOCK, (MT == 1 ? 2 : 1)) void rowgemm_k(GemmAr
 
   // ---- epilogue
 #pragma unroll
-  for (int m = 0; m < MT; ++m)
-    gemm_epilogue<NT, EPI>(a, acc[m], row0 + wave * 32 * MT + m * 32, col0, li, lh, row0 + GBM <= a.rows);
+  for (int m = 0; m < MT; ++m) {
+    if constexpr (EPI == EPI_RANK) gemm_epilogue_rank<NT>(a, acc[m], row0 + wave * 32 * MT + m * 32, col0, li, lh);
+    else if constexpr (EPI == EPI_RANK_DIAG) gemm_epilogue_rank_diag<NT>(a, acc[m], row0 + wave * 32 * MT + m * 32, wave, li, lh);
+    else gemm_epilogue<NT, EPI>(a, acc[m], row0 + wave * 32 * MT + m * 32, col0, li, lh, row0 + GBM <= a.rows);
+  }
 }
 
 // ---- LDS-DMA variant (the fast path) ---------------------------------------------------------

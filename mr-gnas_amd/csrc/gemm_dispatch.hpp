@@ -7,6 +7,7 @@
 //     gemm_x3q.hpp   rowgemm_x3q_k   16 x 16 x 32 tiles, 64-row workgroups, three per CU: 129..224 columns with K > X3Q_MIN_K
 //                                    (sums 32 k at a time: agrees with the others to rounding, not bit for bit)
 //     gemm_x3.hpp    rowgemm_x3_k    wave-autonomous, one wave per SIMD: few rows (<= X3N_MAX_ROWS, two-tile column blocks) and mode 2
+// mrg_distmult_rank (rank.hip) launches rowgemm_x3s_k / rowgemm_k itself with the counting epilogues EPI_RANK / EPI_RANK_DIAG (gemm.hpp).
 // The persistent transposed-accumulator kernel and the two-waves-per-SIMD kernel of rounds 2-3 live in tools/lab/ (tools/gemm_x3_lab.hip
 // still times them).  The switches that move a launch off its default kernel are GemmSwitches (x3_parts.hpp).
 #pragma once

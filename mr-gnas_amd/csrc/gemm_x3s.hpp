@@ -38,7 +38,7 @@ __global__ __launch_bounds__(256, 2) void rowgemm_x3s_k(GemmArgs a, const char* 
   const int tid = threadIdx.x, wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63, li = lane & 31, lh = lane >> 5;
   MRG_GROUP_SELECT(GBM)                                // row0, Bq; a.rows / bias / scale / rowscale of a grouped launch's range
   const int64_t roww = row0 + wave * 32;
-  const int col0 = blockIdx.y * (NT * 32);
+  const int col0 = (epi_diag(EPI) ? blockIdx.x : blockIdx.y) * (NT * 32);     // EPI_RANK_DIAG: row block x meets column block x
   const int K = a.K1 + a.K2;
   const int nslab = (K + 15) >> 4;
 
@@ -54,7 +54,7 @@ __global__ __launch_bounds__(256, 2) void rowgemm_x3s_k(GemmArgs a, const char* 
   v4f xr[3][2];                                          // raw fragments: a ring of three slabs
   auto load_a = [&](int slab, v4f (&x)[2]) { x3_load_a<16, DUAL>(x, slab, nslab, lh, ar1, ar2, a.K1, a.K2, K); };
   // ---- B: the slab's NCH chunks, NBW per wave (the last wave repeats the last chunk: same bytes to the same place)
-  const char* bcol = Bq + (int64_t)blockIdx.y * NT * 3072;
+  const char* bcol = Bq + (int64_t)(epi_diag(EPI) ? blockIdx.x : blockIdx.y) * NT * 3072;
   auto fetch_b = [&](int slab, int buf) { x3_fetch_b<NCH>(bcol + (int64_t)slab * ntile * 3072, smem_b + buf * BSLAB, wave, lane); };
   const unsigned lds0 = (unsigned)(size_t)(lds_ptr_t)smem_b + (unsigned)lane * 16u;
   u32x4 bq2[2][2][3];                                    // [double buffer][tile of the pair][plane]
@@ -162,6 +162,8 @@ __global__ __launch_bounds__(256, 2) void rowgemm_x3s_k(GemmArgs a, const char* 
   }
   else if constexpr (EPI == EPI_SEGMAX) gemm_epilogue_segmax<NT>(a, acc, roww, col0, li, lh);
   else if constexpr (EPI == EPI_SEGSUM) gemm_epilogue_segsum<NT>(a, acc, roww, col0, li, lh);
+  else if constexpr (EPI == EPI_RANK) gemm_epilogue_rank<NT>(a, acc, roww, col0, li, lh);
+  else if constexpr (EPI == EPI_RANK_DIAG) gemm_epilogue_rank_diag<NT>(a, acc, roww, wave, li, lh);
   else gemm_epilogue<NT, EPI>(a, acc, roww, col0, li, lh, row0 + GBM <= a.rows);
 }
 

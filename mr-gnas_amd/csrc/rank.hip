@@ -1,0 +1,142 @@
+// mrg_distmult_rank: raw / filtered ranks of DistMult link prediction without a [Q, N] tensor (reference utils/utils_rgcn.py:212-380,
+// search/mr_lp_search.py:258-278).
+//   score of candidate e for query i:  x = sum_c ent[a_i, c] * rel[r_i, c] * ent[e, c]
+//   ranks[i] = 1 + #{e != t_i, not filtered : x_e > x_t  or  (x_e == x_t and e < t_i)}
+// The product [Q, D] x [N, D]^T runs as a row GEMM (rows = queries, columns = entities, grid.y over the column blocks) whose
+// epilogue counts instead of storing (gemm.hpp: gemm_epilogue_rank).  Per chunk of RANK_CHUNK queries:
+//   1. the operand ent[a] * rel[r] and the gathered target rows ent[t] are materialised (mrg_gather_compose_fwd),
+//   2. EPI_RANK_DIAG forms every query's target score on the tile routine of the sweep (row block x against its own 128 gathered
+//      targets, diagonal kept): bit-identical with what the sweep computes for a column that holds the same entity row,
+//   3. EPI_RANK sweeps all entities and adds, per (row, workgroup), the number of unfiltered candidates that beat the target.
+// Split-bf16 core (rowgemm_x3s_k, the entity table pre-split once per call) where it takes the shape, D > 48 and D % 4 == 0;
+// every other D runs the same two epilogues on the exact-f32 core (rowgemm_k).
+#include "gemm_dispatch.hpp"
+
+namespace mrg {
+
+constexpr int64_t RANK_CHUNK = 8192;          // queries per sweep launch: bounds the [chunk, D] operands of the workspace
+constexpr int RANK_NT = 7;                    // column tiles per block of the sweep
+constexpr int64_t RANK_MAX_N = 65535LL * RANK_NT * 32;     // grid.y
+
+inline bool rank_split_core(int D) { return gemm_mode() != 1 && D > 48 && D % 4 == 0; }
+
+struct RankPlan { size_t ent_split, a, t, t_split, qinfo, tscore, counts, total; };
+inline size_t rank_up(size_t x) { return (x + 255) & ~(size_t)255; }
+inline RankPlan rank_plan(int64_t Q, int64_t N, int D) {
+  RankPlan p{};
+  const int64_t qc = Q < RANK_CHUNK ? Q : RANK_CHUNK;
+  const bool split = D > 48 && D % 4 == 0;                  // (sized for the split core whatever mrg_gemm_set_mode says)
+  size_t off = 256;                                          // slack: the workspace pointer is rounded up to 256 bytes
+  p.ent_split = off; off += rank_up(split ? x3_bsplit_bytes((int)N, D, RANK_NT) : 0);
+  p.a = off; off += rank_up((size_t)qc * D * sizeof(float));
+  p.t = off; off += rank_up((size_t)qc * D * sizeof(float));
+  p.t_split = off; off += rank_up(split ? x3_bsplit_bytes((int)qc, D, 4) : 0);
+  p.qinfo = off; off += rank_up((size_t)Q * 4 * sizeof(int32_t));
+  p.tscore = off; off += rank_up((size_t)Q * sizeof(float));
+  p.counts = off; off += rank_up((size_t)Q * sizeof(unsigned));
+  p.total = off;
+  return p;
+}
+
+// qinfo[i] = {target, begin, end of the list of qkey[i] (empty when the key is -1 or unknown), when}; counts[i] = 0
+__global__ void rank_prep_k(const int32_t* __restrict__ t_idx, const int64_t* __restrict__ qkey, const int32_t* __restrict__ when,
+                            const int64_t* __restrict__ keys, const int32_t* __restrict__ rowptr, int64_t U, int64_t Q,
+                            int32_t* __restrict__ qinfo, unsigned* __restrict__ counts) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= Q) return;
+  int lo = 0, hi = 0;
+  const int64_t key = (qkey && U > 0) ? qkey[i] : -1;
+  if (key >= 0) {
+    int64_t b = 0, e = U;
+    while (b < e) {
+      const int64_t mid = b + ((e - b) >> 1);
+      if (keys[mid] < key) b = mid + 1; else e = mid;
+    }
+    if (b < U && keys[b] == key) { lo = rowptr[b]; hi = rowptr[b + 1]; }
+  }
+  *reinterpret_cast<int4*>(qinfo + i * 4) = make_int4(t_idx[i], lo, hi, when ? when[i] : -1);
+  counts[i] = 0;
+}
+
+__global__ void rank_finish_k(const unsigned* __restrict__ counts, int64_t* __restrict__ ranks, int64_t Q) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < Q) ranks[i] = 1 + (int64_t)counts[i];
+}
+
+// one chunk: target scores, then the sweep.  g: A1 / K1 / rows and the rank pointers of the chunk are set
+inline int rank_chunk_split(GemmArgs g, const float* T, void* t_split, const void* ent_split, int64_t N, int D, hipStream_t st) {
+  GemmArgs d = g;
+  d.N = (int)g.rows;
+  launch_bsplit(T, D, 1, d.N, D, 4, t_split, st);
+  int rc = launch_kernel(rowgemm_x3s_k<4, EPI_RANK_DIAG, false>, dim3((unsigned)((g.rows + 127) / 128), 1), dim3(256), (size_t)3 * 4 * 3 * 1024, st,
+                         d, (const char*)t_split, x3_tiles(d.N, 4));
+  if (rc != MRG_OK) return rc;
+  g.N = (int)N;
+  const int ntile = x3_tiles(g.N, RANK_NT);
+  return launch_kernel(rowgemm_x3s_k<RANK_NT, EPI_RANK, false>, dim3((unsigned)((g.rows + 127) / 128), (unsigned)(ntile / RANK_NT)), dim3(256),
+                       (size_t)3 * RANK_NT * 3 * 1024, st, g, (const char*)ent_split, ntile);
+}
+
+template <bool VEC4>
+inline int rank_chunk_exact(GemmArgs g, const float* T, const float* ent, int64_t N, int D, hipStream_t st) {
+  GemmArgs d = g;
+  d.N = (int)g.rows; d.B = T; d.ldb = D;
+  int rc = launch_kernel(rowgemm_k<4, 1, 16, EPI_RANK_DIAG, VEC4>, dim3((unsigned)((g.rows + 127) / 128), 1), dim3(MRG_BLOCK), gemm_lds_bytes(4, 1, 16), st, d);
+  if (rc != MRG_OK) return rc;
+  g.N = (int)N; g.B = ent; g.ldb = D;
+  return launch_kernel(rowgemm_k<RANK_NT, 1, 16, EPI_RANK, VEC4>, dim3((unsigned)((g.rows + 127) / 128), (unsigned)((N + RANK_NT * 32 - 1) / (RANK_NT * 32))),
+                       dim3(MRG_BLOCK), gemm_lds_bytes(RANK_NT, 1, 16), st, g);
+}
+
+}  // namespace mrg
+
+using namespace mrg;
+
+static bool rank_shape_ok(int64_t Q, int64_t N, int D) { return Q >= 0 && N >= 1 && N <= RANK_MAX_N && D >= 1 && D <= 1024 && (D <= 256 || D % 4 == 0); }
+
+extern "C" int64_t mrg_distmult_rank_workspace_bytes(int64_t Q, int64_t N, int D) {
+  if (!rank_shape_ok(Q, N, D)) return MRG_E_SHAPE;
+  return (int64_t)rank_plan(Q, N, D).total;
+}
+
+extern "C" int mrg_distmult_rank(const float* ent, const float* rel, const int32_t* a_idx, const int32_t* r_idx, const int32_t* t_idx,
+                                 const int64_t* qkey, const int32_t* when, const int64_t* keys, const int32_t* rowptr, const int32_t* members,
+                                 const int32_t* gone_at, int64_t U, int64_t Q, int64_t N, int D, int64_t* ranks, void* ws, int64_t ws_bytes,
+                                 void* stream) {
+  if (U < 0 || !rank_shape_ok(Q, N, D)) return MRG_E_SHAPE;
+  if (Q == 0) return MRG_OK;
+  if (!ent || !rel || !a_idx || !r_idx || !t_idx || !ranks) return MRG_E_NULLPTR;
+  if (U > 0 && (!qkey || !when || !keys || !rowptr || !members || !gone_at)) return MRG_E_NULLPTR;
+  const RankPlan p = rank_plan(Q, N, D);
+  if (!ws || ws_bytes < (int64_t)p.total) return MRG_E_WORKSPACE;
+  hipStream_t st = (hipStream_t)stream;
+  char* w = (char*)(((uintptr_t)ws + 255) & ~(uintptr_t)255) - 256;        // the plan's offsets start at 256
+  float* A = (float*)(w + p.a);
+  float* T = (float*)(w + p.t);
+  int32_t* qinfo = (int32_t*)(w + p.qinfo);
+  float* tscore = (float*)(w + p.tscore);
+  unsigned* counts = (unsigned*)(w + p.counts);
+  const bool split = rank_split_core(D);
+  const bool vec = D % 4 == 0 && aligned16(ent);
+
+  hipLaunchKernelGGL(rank_prep_k, dim3((unsigned)((Q + 255) / 256)), dim3(256), 0, st, t_idx, qkey, when, keys, rowptr, U, Q, qinfo, counts);
+  MRG_LAUNCH_CHECK();
+  if (split) launch_bsplit(ent, D, 1, (int)N, D, RANK_NT, w + p.ent_split, st);
+  for (int64_t q0 = 0; q0 < Q; q0 += RANK_CHUNK) {
+    const int64_t rows = Q - q0 < RANK_CHUNK ? Q - q0 : RANK_CHUNK;
+    int rc = mrg_gather_compose_fwd(MRG_COMPOSE_MULT, ent, rel, a_idx + q0, r_idx + q0, A, rows, D, stream);
+    if (rc != MRG_OK) return rc;
+    rc = mrg_gather_compose_fwd(-1, ent, rel, t_idx + q0, r_idx + q0, T, rows, D, stream);
+    if (rc != MRG_OK) return rc;
+    GemmArgs g{};
+    g.A1 = A; g.A2 = A; g.K1 = D; g.K2 = 0; g.rows = rows;
+    gemm_set_rank(g, RankEpi{tscore + q0, tscore + q0, qinfo + q0 * 4, members, gone_at, counts + q0});
+    if (split) rc = rank_chunk_split(g, T, w + p.t_split, w + p.ent_split, N, D, st);
+    else if (vec) rc = rank_chunk_exact<true>(g, T, ent, N, D, st);
+    else rc = rank_chunk_exact<false>(g, T, ent, N, D, st);
+    if (rc != MRG_OK) return rc;
+  }
+  hipLaunchKernelGGL(rank_finish_k, dim3((unsigned)((Q + 255) / 256)), dim3(256), 0, st, counts, ranks, Q);
+  MRG_LAUNCH_CHECK();
+  return MRG_OK;
+}

@@ -5,11 +5,15 @@
 pass counts, per row, the entries that beat the target.  Ties follow a stable descending sort (the reference's
 ``torch.argsort`` leaves the order of equal scores unspecified).  ``predict`` / ``combine_results`` mirror the
 reference's functions of the same role so a driver can swap them in.
+
+The search driver's evaluation (reference utils/utils_rgcn.py:212-380, search/mr_lp_search.py:258-278) is the second half of the
+module: ``calc_mrr`` / ``calc_raw_mrr`` / ``calc_filtered_mrr`` / ``infer_graph`` over ``KnownTriples`` and ``distmult_ranks``
+(``mrg_distmult_rank``: the DistMult product as a row GEMM whose epilogue counts; no [Q, N] tensor).
 """
 import torch
 import torch.nn.functional as F
 
-from ._lib import call, ptr, require_hip, stream_of, f32c
+from ._lib import MrgnasError, call, check, load, ptr, require_hip, stream_of, f32c
 
 
 def filtered_ranks(pred, labels, obj):
@@ -66,3 +70,171 @@ def combine_results(left, right):
         results[f'right_hits@{k}'] = round(right[f'hits@{k}'] / count, 5)
         results[f'hits@{k}'] = round((results[f'left_hits@{k}'] + results[f'right_hits@{k}']) / 2, 5)
     return results
+
+
+# ---- calc_mrr: the search driver's evaluation (reference utils/utils_rgcn.py:212-380, search/mr_lp_search.py:258-278) ----------------
+# Raw and filtered MRR / Hits@k of entity and relation embeddings under DistMult, on the device and without a [Q, N] tensor: one
+# entry point, ``mrg_distmult_rank``, runs the product (emb[a] * w[r]) emb^T as a row GEMM whose epilogue counts, per query, the
+# unfiltered candidates that beat the target.
+#
+# Semantics (checked against the reference's own functions, tests/golden/make_golden_mrr.py):
+#   * the reference ranks sigmoid(x); sigmoid is monotone, so the kernel ranks x.  Ties follow mrg_rank_filtered's rule,
+#     rank = 1 + #(greater) + #(equal at a lower entity id); the reference's torch.sort leaves equal scores in unspecified order, and
+#     where float32 sigmoid saturates and the reference ties, this value lies inside the reference's tie interval.
+#   * raw: nothing is filtered.  Pass S perturbs the subject (fixed entity o, target s), pass O the object (fixed s, target o).
+#   * filtered, protocol="reference": the reference's filter set starts as the distinct triples of train, valid and test, and
+#     filter_s / filter_o REMOVE the query's own triple from it for good.  Pass S runs first on the same set object, so its query i is
+#     filtered by the set minus test triples 0..i, and every query of pass O by the set minus all test triples.  Here every known
+#     triple carries gone_at = index of the first test triple equal to it (else INT32_MAX), every query a `when` (i in pass S, T in
+#     pass O), and a candidate is filtered iff its triple is known, gone_at > when, and it is not the target.
+#   * protocol="standard" filters every known triple but the query's own: the same kernel with when = -1.  It differs from the
+#     reference's numbers and is therefore not the default.
+#   * the reference's calc_raw_mrr returns only mrr, so its calc_mrr(eval_p="raw") fails at the unpacking; here both protocols return
+#     (mrr, hit_k).
+_INT32_MAX = 2 ** 31 - 1
+
+
+class _KnownSide:
+    """The filter index of one pass: list u holds the entities that complete key keys[u] = fixed_entity * num_rels + relation to a
+    known triple, members[rowptr[u]:rowptr[u + 1]] ascending, with their gone_at."""
+
+    __slots__ = ("keys", "rowptr", "members", "gone_at", "num_rels")
+
+    def __init__(self, key, member, gone_at, num_ent, num_rels):
+        order = torch.argsort(key * num_ent + member)              # (key, member) ascending; the triples are distinct
+        key, self.num_rels = key[order], num_rels
+        self.members, self.gone_at = member[order].int().contiguous(), gone_at[order].int().contiguous()
+        self.keys, counts = torch.unique_consecutive(key, return_counts=True)
+        self.rowptr = torch.cat((counts.new_zeros(1), counts.cumsum(0))).int().contiguous()
+
+
+class KnownTriples:
+    """The distinct triples of train, valid and test as the two filter indexes of calc_mrr, built with torch sorts on whatever device
+    the triples live on (CPU tensors work too).  `subject`: key o * R + r, members s (pass S); `object`: key s * R + r, members o
+    (pass O).  gone_at: index of the first test triple equal to the member's triple, else INT32_MAX."""
+
+    def __init__(self, train, valid, test, num_ent, num_rels):
+        parts = [torch.as_tensor(t).long().reshape(-1, 3) for t in (train, valid, test)]
+        parts = [p.to(parts[2].device) for p in parts]
+        tri = torch.cat(parts)
+        self.num_ent, self.num_rels, self.num_test = int(num_ent), int(num_rels), int(parts[2].shape[0])
+        if tri.numel() and (int(tri.min()) < 0 or int(tri[:, (0, 2)].max()) >= num_ent or int(tri[:, 1].max()) >= num_rels):
+            raise ValueError("KnownTriples: an entity or relation id is out of range")
+        if num_ent * num_rels * num_ent >= 2 ** 63 or tri.shape[0] >= _INT32_MAX or num_ent >= _INT32_MAX:
+            raise ValueError("KnownTriples: the triple codes do not fit")
+        code = (tri[:, 0] * num_rels + tri[:, 1]) * num_ent + tri[:, 2]
+        pos = torch.full((tri.shape[0],), _INT32_MAX, dtype=torch.int64, device=tri.device)
+        pos[tri.shape[0] - self.num_test:] = torch.arange(self.num_test, device=tri.device)
+        uniq, inv = torch.unique(code, return_inverse=True)
+        gone = torch.full((uniq.numel(),), _INT32_MAX, dtype=torch.int64, device=tri.device).scatter_reduce(0, inv, pos, "amin")
+        s, r, o = uniq // (num_rels * num_ent), (uniq // num_ent) % num_rels, uniq % num_ent
+        self.subject = _KnownSide(o * num_rels + r, s, gone, num_ent, num_rels)
+        self.object = _KnownSide(s * num_rels + r, o, gone, num_ent, num_rels)
+
+
+def distmult_ranks(embedding, w, a, r, target, known_side=None, when=None):
+    """ranks [Q] int64 (1-based) of `target` among all entities for the DistMult queries (fixed entity a, relation r), through
+    mrg_distmult_rank.  known_side: a KnownTriples side (`.subject` when the subject is perturbed, `.object` when the object is) with
+    `when` [Q] int32, or None for raw ranks.  Ids are trusted to be in range (KnownTriples and calc_mrr check theirs)."""
+    embedding, w = f32c(embedding), f32c(w)
+    a, r, target = (t.int().contiguous() for t in (a, r, target))
+    require_hip(embedding, w, a, r, target)
+    Q, (N, D) = a.numel(), embedding.shape
+    if r.numel() != Q or target.numel() != Q or w.shape[1] != D:
+        raise ValueError("distmult_ranks: a / r / target [Q] and w [R, D] expected")
+    qkey = keys = rowptr = members = gone_at = None
+    U = 0
+    if known_side is not None and known_side.keys.numel() > 0:
+        if when is None or when.numel() != Q:
+            raise ValueError("distmult_ranks: a filtered call needs when [Q]")
+        k = known_side
+        require_hip(k.keys, k.rowptr, k.members, k.gone_at)
+        qkey, when = (a.long() * k.num_rels + r.long()).contiguous(), when.int().contiguous()
+        require_hip(when)
+        keys, rowptr, members, gone_at, U = k.keys, k.rowptr, k.members, k.gone_at, k.keys.numel()
+    else:
+        when = None
+    ranks = torch.empty(Q, dtype=torch.int64, device=embedding.device)
+    nbytes = load().mrg_distmult_rank_workspace_bytes(Q, N, D)
+    if nbytes < 0:
+        check(int(nbytes), "mrg_distmult_rank_workspace_bytes")
+    ws = torch.empty(max(int(nbytes), 1), dtype=torch.uint8, device=embedding.device)
+    call("mrg_distmult_rank", (ptr(embedding), ptr(w), ptr(a), ptr(r), ptr(target), ptr(qkey), ptr(when), ptr(keys), ptr(rowptr),
+                               ptr(members), ptr(gone_at), U, Q, N, D, ptr(ranks), ptr(ws), int(nbytes), stream_of(embedding)),
+         nbytes=4 * (Q + N) * D, flops=2 * Q * N * D)
+    return ranks
+
+
+def _both_passes(embedding, w, test, eval_bz, known, protocol):
+    """cat(ranks_s, ranks_o) over the test triples, at most eval_bz queries per launch."""
+    s, r, o = test[:, 0], test[:, 1], test[:, 2]
+    T, step = test.shape[0], max(int(eval_bz), 1)
+    out = []
+    for fixed, tgt, side, when_all in ((o, s, known.subject if known else None, None), (s, o, known.object if known else None, T)):
+        if known is None:
+            when = None
+        elif protocol == "standard":
+            when = torch.full((T,), -1, dtype=torch.int32, device=test.device)
+        else:
+            when = (torch.arange(T, dtype=torch.int32, device=test.device) if when_all is None
+                    else torch.full((T,), when_all, dtype=torch.int32, device=test.device))
+        for b in range(0, T, step):
+            e = min(T, b + step)
+            out.append(distmult_ranks(embedding, w, fixed[b:e], r[b:e], tgt[b:e], side, None if when is None else when[b:e]))
+    return torch.cat(out) if out else torch.empty(0, dtype=torch.int64, device=test.device)
+
+
+def _summarise(ranks, hits):
+    """(mrr, [hits@k]) as Python floats: float64 on the device, ONE device -> host copy."""
+    rd = ranks.double()
+    ks = torch.tensor([float(k) for k in hits], dtype=torch.float64, device=ranks.device)
+    vals = torch.cat((rd.reciprocal().mean().view(1), (rd.unsqueeze(0) <= ks.unsqueeze(1)).double().mean(dim=1))).tolist()
+    return vals[0], vals[1:]
+
+
+def _test_on(embedding, test_triplets):
+    if not embedding.is_cuda:
+        raise MrgnasError("calc_mrr runs on a HIP device (no CPU fallback); got embeddings on " + str(embedding.device))
+    return torch.as_tensor(test_triplets).long().reshape(-1, 3).to(embedding.device)
+
+
+def calc_raw_mrr(embedding, w, test_triplets, hits=[], eval_bz=100):
+    """Raw MRR and Hits@k (reference utils/utils_rgcn.py:241-264; returns (mrr, hit_k) where the reference returns mrr alone)."""
+    with torch.no_grad():
+        test = _test_on(embedding, test_triplets)
+        if test.numel() and (int(test.min()) < 0 or int(test[:, (0, 2)].max()) >= embedding.shape[0] or int(test[:, 1].max()) >= w.shape[0]):
+            raise ValueError("calc_raw_mrr: an entity or relation id is out of range")
+        return _summarise(_both_passes(embedding, w, test, eval_bz, None, "reference"), hits)
+
+
+def calc_filtered_mrr(embedding, w, train_triplets, valid_triplets, test_triplets, hits=[], eval_bz=100, protocol="reference"):
+    """Filtered MRR and Hits@k (reference utils/utils_rgcn.py:342-367).  protocol: "reference" (the reference's removal order, see
+    above) or "standard" (every known triple but the query's own)."""
+    if protocol not in ("reference", "standard"):
+        raise ValueError("calc_filtered_mrr: protocol is 'reference' or 'standard'")
+    with torch.no_grad():
+        test = _test_on(embedding, test_triplets)
+        known = KnownTriples(torch.as_tensor(train_triplets).to(test.device), torch.as_tensor(valid_triplets).to(test.device), test,
+                             embedding.shape[0], w.shape[0])
+        return _summarise(_both_passes(embedding, w, test, eval_bz, known, protocol), hits)
+
+
+def calc_mrr(embedding, w, train_triplets, valid_triplets, test_triplets, hits=[], eval_bz=100, eval_p="filtered", protocol="reference"):
+    """The reference's calc_mrr (utils/utils_rgcn.py:375-380) on the device: (mrr, hit_k) as Python floats.  eval_bz only bounds the
+    number of queries per launch; the result does not depend on it."""
+    if eval_p == "filtered":
+        return calc_filtered_mrr(embedding, w, train_triplets, valid_triplets, test_triplets, hits, eval_bz, protocol)
+    return calc_raw_mrr(embedding, w, test_triplets, hits, eval_bz)
+
+
+def infer_graph(test_graph, test_src_in, test_rel, test_node_id, model, train_data, valid_data, test_data, device, eval_bz=1000,
+                eval_p="filtered"):
+    """infer_graph of the search driver (reference search/mr_lp_search.py:258-278): the network in eval mode, one forward without
+    autograd, calc_mrr with hits at 1 / 3 / 10.  model: supernet.SearchNetwork (anything whose forward(graph, node_id, src_in,
+    edge_type) returns (entity embeddings, relation embeddings))."""
+    model.eval()
+    with torch.no_grad():
+        test_src_in = torch.as_tensor(test_src_in).to(device)
+        ent_embed, rel_embed = model(test_graph.to(device), test_node_id, test_src_in, test_rel.to(device))
+        return calc_mrr(ent_embed, rel_embed, torch.as_tensor(train_data).long(), torch.as_tensor(valid_data).long(), test_data,
+                        hits=[1, 3, 10], eval_bz=eval_bz, eval_p=eval_p)
