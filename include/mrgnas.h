@@ -735,6 +735,28 @@ int mrg_distmult_rank(const float *ent, const float *rel, const int32_t *a_idx, 
                       const int64_t *qkey, const int32_t *when, const int64_t *keys, const int32_t *rowptr, const int32_t *members,
                       const int32_t *gone_at, int64_t U, int64_t Q, int64_t N, int D, int64_t *ranks, void *ws, int64_t ws_bytes,
                       void *stream);
+/* The fixed-genotype driver's 1-N training loss (reference train/mr_lp_train.py Network._loss: BCELoss over sf_DisMult_op's [B, N]
+ * predictions and the label-smoothed multi-hot labels of utils/data_set.py:21-33) with no [B, N] tensor in memory.  Additive: ABI 23.
+ *   x[b, e] = sum_c q[b, c] * ent[e, c]   (q [B, D] = ent[subj] * rel_emb[rel], materialised by the caller),  p = sigmoid(x) in float32
+ *   y[b, e] = v_one if e is in the list of key qkey[b] (= subj * 2R + rel) in the index keys [U] ascending / rowptr [U + 1] / objs
+ *             (entity ids, ascending inside a list: sampler.LabelIndex), else v_zero; an unknown key has an empty list
+ * mrg_distmult_bce_fwd:    loss[0] (float32, device) = mean over b, e of (y - 1) * max(log1p(-p), -100) - y * max(log p, -100): torch's
+ *   binary_cross_entropy term for term (p == 1 gives 100 (1 - y), p == 0 gives 100 y), summed in float64 -- lane, wave, workgroup, then
+ *   one float64 partial per workgroup added in a fixed order: no float atomics, bitwise repeatable.
+ * mrg_distmult_bce_dlogit: dl [B][c1 - c0] = gscale[0] * (p - y) * (p (1 - p) / max(p (1 - p), 1e-12)) for the entities [c0, c1): torch's
+ *   binary_cross_entropy_backward times sigmoid_backward, exactly 0 where p saturates.  gscale: one float on the device, the upstream
+ *   gradient divided by B * N (no host synchronisation).
+ * Both recompute the product as the row GEMM of mrg_distmult_rank: split-bf16 core for D > 48 with D % 4 == 0 (error class of
+ * mrg_linear_fwd), else the exact-f32 core.  Indices are trusted (objs < N).  Workspace: mrg_distmult_bce_workspace_bytes(B, N, D) for the
+ * forward and (B, c1 - c0, D) for the logit gradient, O(min(columns, 28 672) D + B + B columns / 28 672) bytes.  Argument errors are
+ * returned before any HIP call; B == 0 returns MRG_OK with nothing launched; N is bounded as for mrg_distmult_rank. */
+int64_t mrg_distmult_bce_workspace_bytes(int64_t B, int64_t N, int D);
+int mrg_distmult_bce_fwd(const float *q, const float *ent, const int64_t *qkey, const int64_t *keys, const int32_t *rowptr,
+                         const int32_t *objs, int64_t U, float v_zero, float v_one, int64_t B, int64_t N, int D, float *loss,
+                         void *ws, int64_t ws_bytes, void *stream);
+int mrg_distmult_bce_dlogit(const float *q, const float *ent, const int64_t *qkey, const int64_t *keys, const int32_t *rowptr,
+                            const int32_t *objs, int64_t U, float v_zero, float v_one, int64_t B, int64_t N, int D, int64_t c0,
+                            int64_t c1, const float *gscale, float *dl, void *ws, int64_t ws_bytes, void *stream);
 /* sf_TransE_op.forward, reference models/operations_lp.py:101-112:
  *   score[b, n] = sigmoid(gamma - sum_c |sub[b, c] + rel[b, c] - ent[n, c]|)
  * backward: gobj [B][D] (the gradient of both sub and rel) and gent [N][D]; either may be NULL.

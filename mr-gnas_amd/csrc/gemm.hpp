@@ -42,6 +42,10 @@ constexpr int epi_base(int epi) { return epi == EPI_GATE_SUMS ? EPI_GATE : (epi 
 // diagonal.  Kernel instances of their own, like the column-sum kinds.
 enum { EPI_RANK = 8, EPI_RANK_DIAG = 9 };
 constexpr bool epi_diag(int epi) { return epi == EPI_RANK_DIAG; }
+// The loss epilogues of mrg_distmult_bce_fwd / mrg_distmult_bce_dlogit (bce.hip; gemm_epilogue_bce / gemm_epilogue_bce_grad below): rows
+// are queries, columns are entities, the label of an element is looked up in the query's object list.  EPI_BCE stores nothing per
+// element (one float64 partial per workgroup), EPI_BCE_GRAD stores the gradient with respect to the logits.  Kernel instances of their own.
+enum { EPI_BCE = 10, EPI_BCE_GRAD = 11 };
 
 // Up to three row ranges of ONE launch of the split-core row GEMM that share every tensor but differ in the weight matrix
 // (the in / out / self direction segments of a dense filter: one launch instead of three).  Workgroup blocks
@@ -209,6 +213,142 @@ __device__ __forceinline__ void gemm_epilogue_rank_diag(const GemmArgs& a, f32x1
     for (int r = 0; r < 16; ++r) {
       const int rl = (r & 3) + 8 * (r >> 2) + 4 * lh;
       if (li == rl && rowbase + rl < a.rows) out[rowbase + rl] = acc[n][r];
+    }
+  }
+}
+
+// ---- DistMult 1-N loss: BCELoss(sigmoid(x), y) and its logit gradient as the GEMM's epilogue (reference models/operations_lp.py:115-127,
+// train/mr_lp_train.py Network._loss; labels utils/data_set.py:21-33) ------------------------------------------------------------------
+// EPI_BCE / EPI_BCE_GRAD: what the loss epilogues read and write.  Like RankEpi the values travel in slots of GemmArgs that these
+// kinds do not otherwise use (row_seg, Cin, scale, act, bits_ld, seg_part, rowscale), so the argument block stays what it was.
+// EPI_BCE_GRAD stores through C / ldc as every storing epilogue does.  row_index stays NULL.
+struct BceEpi {
+  const int32_t* qlist;       // [rows][2]: begin and end of the query's object list in objs (empty: every label is v_zero)
+  const int32_t* objs;        // object lists: entity ids, ascending inside a list
+  float v_zero, v_one;        // the two label values (label smoothing folded in by the caller)
+  int c0;                     // entity id of the launch's column 0 (B points at that entity's row)
+  double* partial;            // EPI_BCE: [gridDim.y][gridDim.x], the workgroup's sum of its elements' loss terms
+  const float* gscale;        // EPI_BCE_GRAD: [1] on the device, upstream gradient / (B * N)
+};
+inline void gemm_set_bce(GemmArgs& a, const BceEpi& b) {
+  a.row_seg = b.qlist; a.Cin = reinterpret_cast<const float*>(b.objs); a.scale = b.v_zero; a.act = __builtin_bit_cast(int, b.v_one);
+  a.bits_ld = b.c0; a.seg_part = reinterpret_cast<float*>(b.partial); a.rowscale = b.gscale;
+}
+__device__ __forceinline__ BceEpi gemm_bce(const GemmArgs& a) {
+  return BceEpi{a.row_seg, reinterpret_cast<const int32_t*>(a.Cin), a.scale, __builtin_bit_cast(float, a.act), a.bits_ld,
+                reinterpret_cast<double*>(a.seg_part), a.rowscale};
+}
+
+// The labels of a wave's 32 rows x NT * 32 columns as bits: lane l < 32 walks the slice of row (rowbase + l)'s ascending object list
+// that falls into the workgroup's column range (binary search for its start, as gemm_epilogue_rank does) and leaves one 32-bit column
+// mask per tile; lanes 32-63 and rows beyond the launch leave zeros.
+template <int NT>
+__device__ __forceinline__ void gemm_bce_label_words(const BceEpi& k, int64_t rowbase, int64_t rows, int col0, int lane, unsigned (&word)[NT]) {
+#pragma unroll
+  for (int n = 0; n < NT; ++n) word[n] = 0u;
+  const int64_t row = rowbase + lane;
+  if (lane >= 32 || row >= rows) return;
+  const int2 q = *reinterpret_cast<const int2*>(k.qlist + row * 2);
+  if (q.x >= q.y) return;
+  const int cbeg = k.c0 + col0, cend = cbeg + NT * 32;
+  int b = q.x, e = q.y;
+  while (b < e) {                                            // first member >= cbeg
+    const int mid = b + ((e - b) >> 1);
+    if (k.objs[mid] < cbeg) b = mid + 1; else e = mid;
+  }
+  for (; b < q.y; ++b) {
+    const int m = k.objs[b];
+    if (m >= cend) break;
+    const int d = m - cbeg;
+#pragma unroll
+    for (int n = 0; n < NT; ++n) word[n] |= (d >> 5) == n ? 1u << (d & 31) : 0u;
+  }
+}
+// the label of accumulator register r, tile word `w` (gemm_bce_label_words), of this lane: the mask lives in lane `row within the strip`
+__device__ __forceinline__ float gemm_bce_label(unsigned w, int r, int li, int lh, float v_zero, float v_one) {
+  const int rl = (r & 3) + 8 * (r >> 2);
+  const unsigned w0 = (unsigned)__builtin_amdgcn_readlane((int)w, rl), w1 = (unsigned)__builtin_amdgcn_readlane((int)w, rl + 4);
+  return (((lh ? w1 : w0) >> li) & 1u) ? v_one : v_zero;
+}
+
+// EPI_BCE: the sum over the wave's valid elements of  (y - 1) * max(log1p(-p), -100) - y * max(log p, -100),  p = sigmoid(x) in float32
+// as EPI_BIAS_ACT forms it -- torch's binary_cross_entropy term for term, saturation included (p == 1: 100 (1 - y); p == 0: 100 y).
+// A lane adds its NT * 16 terms in register order in float64, then the wave's lanes are added by a butterfly: a fixed order.  Every
+// lane returns the wave's sum (0 for a strip beyond the rows); gemm_bce_flush adds the waves.
+template <int NT>
+__device__ __forceinline__ double gemm_epilogue_bce(const GemmArgs& a, f32x16 (&acc)[NT], int64_t rowbase, int col0, int li, int lh) {
+  if (rowbase >= a.rows) return 0.0;                         // wave-uniform
+  const BceEpi k = gemm_bce(a);
+  unsigned word[NT];
+  gemm_bce_label_words<NT>(k, rowbase, a.rows, col0, lh * 32 + li, word);
+  double s = 0.0;
+#pragma unroll
+  for (int n = 0; n < NT; ++n) {
+    const bool cok = col0 + n * 32 + li < a.N;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+      const bool ok = cok && rowbase + (r & 3) + 8 * (r >> 2) + 4 * lh < a.rows;
+      const float y = gemm_bce_label(word[n], r, li, lh, k.v_zero, k.v_one);
+      const float p = sigmoidf_fast(acc[n][r]);
+      const float lp = fmaxf(logf(p), -100.f), lq = fmaxf(log1pf(-p), -100.f);
+      const float t = (y - 1.f) * lq - y * lp;
+      s += ok ? (double)t : 0.0;
+    }
+  }
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) s += __shfl_xor(s, off);
+  return s;
+}
+// The workgroup's partial from its four waves' sums, added in wave order; lds: 4 doubles of the LDS the k-loop is done with.
+// Every thread of the workgroup calls it.
+__device__ __forceinline__ void gemm_bce_flush(const GemmArgs& a, double wave_sum, double* __restrict__ lds) {
+  __syncthreads();                                           // every wave has read its last operands from LDS
+  if ((threadIdx.x & 63) == 0) lds[threadIdx.x >> 6] = wave_sum;
+  __syncthreads();
+  if (threadIdx.x == 0) gemm_bce(a).partial[(int64_t)blockIdx.y * gridDim.x + blockIdx.x] = ((lds[0] + lds[1]) + lds[2]) + lds[3];
+}
+
+// EPI_BCE_GRAD: C[row][col] = gscale * (p - y) * (p (1 - p) / max(p (1 - p), 1e-12)), torch's binary_cross_entropy_backward times
+// sigmoid_backward: gscale * (p - y) wherever p (1 - p) > 1e-12, exactly 0 where p saturates.  Addressing and store pattern of
+// gemm_epilogue (one clamped pointer per accumulator row, a full tile stores without per-element branches).
+template <int NT>
+__device__ __forceinline__ void gemm_epilogue_bce_grad(const GemmArgs& a, f32x16 (&acc)[NT], int64_t rowbase, int col0, int li, int lh, bool full) {
+  if (rowbase >= a.rows) return;                             // wave-uniform
+  const BceEpi k = gemm_bce(a);
+  const float gs = k.gscale[0];
+  unsigned word[NT];
+  gemm_bce_label_words<NT>(k, rowbase, a.rows, col0, lh * 32 + li, word);
+  const int last = (int)((a.rows - 1 - rowbase) < 31 ? (a.rows - 1 - rowbase) : 31);
+  const int colw = col0 + li < a.N ? col0 + li : a.N - 1;
+  float* crow[16];
+  bool rok[16];
+#pragma unroll
+  for (int r = 0; r < 16; ++r) {
+    const int row = (r & 3) + 8 * (r >> 2) + 4 * lh;
+    const int rc = row < last ? row : last;
+    rok[r] = row <= last;
+    crow[r] = a.C + (rowbase + rc) * a.ldc + colw;
+  }
+#pragma unroll
+  for (int n = 0; n < NT; ++n) {
+    const bool cok = col0 + n * 32 + li < a.N;
+    float v[16];
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+      const float y = gemm_bce_label(word[n], r, li, lh, k.v_zero, k.v_one);
+      const float p = sigmoidf_fast(acc[n][r]);
+      const float pq = p * (1.f - p);
+      v[r] = gs * (p - y) * (pq / fmaxf(pq, 1e-12f));
+    }
+    if (full) {
+      if (cok) {
+#pragma unroll
+        for (int r = 0; r < 16; ++r) crow[r][n * 32] = v[r];
+      }
+    } else {
+#pragma unroll
+      for (int r = 0; r < 16; ++r)
+        if (cok && rok[r]) crow[r][n * 32] = v[r];
     }
   }
 }
@@ -613,9 +753,17 @@ __global__ __launch_bounds__(MRG_BLOCK, (MT == 1 ? 2 : 1)) void rowgemm_k(GemmAr
   }
 
   // ---- epilogue
+  if constexpr (EPI == EPI_BCE) {
+    double s = 0.0;
+#pragma unroll
+    for (int m = 0; m < MT; ++m) s += gemm_epilogue_bce<NT>(a, acc[m], row0 + wave * 32 * MT + m * 32, col0, li, lh);
+    gemm_bce_flush(a, s, reinterpret_cast<double*>(smem));
+    return;
+  }
 #pragma unroll
   for (int m = 0; m < MT; ++m) {
-    if constexpr (EPI == EPI_RANK) gemm_epilogue_rank<NT>(a, acc[m], row0 + wave * 32 * MT + m * 32, col0, li, lh);
+    if constexpr (EPI == EPI_BCE_GRAD) gemm_epilogue_bce_grad<NT>(a, acc[m], row0 + wave * 32 * MT + m * 32, col0, li, lh, row0 + GBM <= a.rows);
+    else if constexpr (EPI == EPI_RANK) gemm_epilogue_rank<NT>(a, acc[m], row0 + wave * 32 * MT + m * 32, col0, li, lh);
     else if constexpr (EPI == EPI_RANK_DIAG) gemm_epilogue_rank_diag<NT>(a, acc[m], row0 + wave * 32 * MT + m * 32, wave, li, lh);
     else gemm_epilogue<NT, EPI>(a, acc[m], row0 + wave * 32 * MT + m * 32, col0, li, lh, row0 + GBM <= a.rows);
   }

@@ -124,6 +124,12 @@ inline int launch_rowgemm_x3_mode_colsum(GemmArgs a, const void* Bp, hipStream_t
   return launch_rowgemm_x3s_colsum<EPI>(a, Bp, st);
 }
 
+// ---- queries x all entities (rank.hip, bce.hip): the sweeps that launch rowgemm_x3s_k / rowgemm_k themselves -------------------------
+constexpr int64_t RANK_CHUNK = 8192;          // queries per sweep launch: bounds the [chunk, D] operands of the workspace and grid.x
+constexpr int RANK_NT = 7;                    // column tiles per block of the sweep
+constexpr int64_t RANK_MAX_N = 65535LL * RANK_NT * 32;     // grid.y
+inline bool rank_split_core(int D) { return gemm_mode() != 1 && D > 48 && D % 4 == 0; }
+
 inline size_t gemm_workspace_bytes(int K, int N) {
   const size_t split = bsplit_bytes_any(N, K);
   const size_t transp = (size_t)K * N * sizeof(float);

@@ -14,12 +14,6 @@
 
 namespace mrg {
 
-constexpr int64_t RANK_CHUNK = 8192;          // queries per sweep launch: bounds the [chunk, D] operands of the workspace
-constexpr int RANK_NT = 7;                    // column tiles per block of the sweep
-constexpr int64_t RANK_MAX_N = 65535LL * RANK_NT * 32;     // grid.y
-
-inline bool rank_split_core(int D) { return gemm_mode() != 1 && D > 48 && D % 4 == 0; }
-
 struct RankPlan { size_t ent_split, a, t, t_split, qinfo, tscore, counts, total; };
 inline size_t rank_up(size_t x) { return (x + 255) & ~(size_t)255; }
 inline RankPlan rank_plan(int64_t Q, int64_t N, int D) {

@@ -55,6 +55,56 @@ def predict(val_test_loader, g, model, device):
     return results, tot[3]
 
 
+class _LabelSide:
+    """A sampler.LabelIndex as the filter side of distmult_ranks (the layout of _KnownSide with num_rels = 2R): every labelled object
+    is a member that never leaves (gone_at = 0 against when = -1, the "standard" protocol)."""
+
+    __slots__ = ("keys", "rowptr", "members", "gone_at", "num_rels")
+
+    def __init__(self, label_index):
+        li = label_index
+        self.keys, self.rowptr, self.members, self.num_rels = li.keys, li.rowptr, li.objs, 2 * li.num_rel
+        self.gone_at = torch.zeros_like(li.objs)
+
+
+def predict_fused(val_test_loader, g, model, label_index, device):
+    """predict() for a DistMult network without a [B, N] tensor: same (results, summed loss), same single device -> host copy.
+    Per batch of (s, r, o) triples one model.embed(g); the ranks come from distmult_ranks (mrg_distmult_rank) with label_index -- a
+    sampler.LabelIndex over the known triples, the source of predict's dense labels -- as the filter: every labelled object but the
+    target is filtered, mrg_rank_filtered's rule; the batch's mean BCE comes from mrg_distmult_bce_fwd on the unsmoothed labels.
+    The loader yields triplets; a second element (dense labels), if present, is ignored.
+    Ranks are taken on the logits, as calc_mrr takes them, where predict ranks float32 sigmoid(x): sigmoid is monotone, ties follow
+    the same rule (equal score at a lower entity id), and where float32 sigmoid ties two different logits the value returned here
+    lies inside predict's tie interval."""
+    from . import functional as K
+    from .operations_lp import sf_DisMult_op
+    if torch.device(device).type != "cuda" or not next(model.parameters()).is_cuda:
+        raise MrgnasError("predict_fused runs on a HIP device (no CPU fallback); got " + str(device))
+    if not isinstance(model.score_func, sf_DisMult_op):
+        raise MrgnasError(f"predict_fused covers the DistMult scorer only; this network scores with {type(model.score_func).__name__}")
+    side = _LabelSide(label_index)
+    v_zero, v_one = label_index.label_values(0.0)
+    ks = torch.tensor(_HITS, dtype=torch.float64, device=device)
+    acc = torch.zeros(4 + len(_HITS), dtype=torch.float64, device=device)       # [count, mr, mrr, loss, hits@k ...]
+    with torch.no_grad():
+        model.eval()
+        for batch in val_test_loader:
+            triplets = (batch[0] if isinstance(batch, (tuple, list)) else batch).to(device)
+            s, r, o = (triplets[:, i].int().contiguous() for i in range(3))
+            ent, rel_emb = model.embed(g)
+            when = torch.full((s.numel(),), -1, dtype=torch.int32, device=device)
+            ranks = distmult_ranks(ent, rel_emb, s, r, o, side, when).double()
+            qkey = (s.long() * side.num_rels + r.long()).contiguous()
+            loss = K.distmult_bce_mean(K.gather_rows(f32c(ent), s, f32c(rel_emb), r, "mult"), f32c(ent), label_index, qkey, v_zero, v_one)
+            batch_acc = torch.cat((torch.stack((ranks.new_tensor(float(ranks.numel())), ranks.sum(), ranks.reciprocal().sum(), loss.double())),
+                                   (ranks.unsqueeze(0) <= ks.unsqueeze(1)).sum(dim=1).double()))
+            acc += batch_acc
+    tot = acc.tolist()                                                          # the pass's only device -> host copy
+    results = {'count': int(tot[0]), 'mr': tot[1], 'mrr': tot[2]}
+    results.update({f'hits@{k}': int(tot[4 + i]) for i, k in enumerate(_HITS)})
+    return results, tot[3]
+
+
 def combine_results(left, right):
     """get_combined_results of the reference's infer() (train/mr_lp_train.py:327-345)."""
     if left['count'] != right['count']:

@@ -65,6 +65,7 @@ from .cell_zero import (  # noqa: F401
 )
 from .scoring import (  # noqa: F401
     ScorePlan, _DistMult, distmult_score, distmult_scores_all, _TransE, transe_scores_all,
+    _DistMultBCE, distmult_bce_all, distmult_bce_mean, distmult_bce_dlogit, bce_default_col_chunk,
 )
 from .ccorr import (  # noqa: F401
     _CCorrRows, _Circulant, ccorr,

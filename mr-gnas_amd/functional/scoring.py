@@ -1,10 +1,14 @@
-"""The step after the path: DistMult triple scoring and the [B, N] score functions (csrc/scoring.hip).
+"""The step after the path: DistMult triple scoring, the [B, N] score functions (csrc/scoring.hip) and the 1-N DistMult loss that needs
+no [B, N] tensor (csrc/bce.hip).
 
 Part of ``mr_gnas_amd.functional`` (autograd Functions over the C ABI, include/mrgnas.h): every Function enqueues HIP kernels of
 libmrgnas_hip.so on torch's current stream through ctypes; every call site states the algorithmic bytes / flops of the launch."""
+import ctypes
+
 import torch
 
-from .._lib import call, f32c, ptr, require_hip, stream_of
+from .._lib import MrgnasError, call, check, f32c, ptr, require_hip, stream_of
+from ._base import _ws, _ws_bytes
 from .gcs import span_gcs
 from .compose_gather import compose
 from .row_linear import linear
@@ -65,6 +69,128 @@ def distmult_scores_all(all_ent, sub_emb, rel_emb):
     the MFMA row GEMM with a sigmoid epilogue (all_ent [N, D] is the GEMM's weight operand: no transpose, no [B, N]
     pre-activation tensor)."""
     return linear(compose("mult", sub_emb, rel_emb), all_ent, None, "sigmoid")
+
+
+BCE_COL_BLOCK = 7 * 32              # the sweep's column block (csrc/gemm_dispatch.hpp: RANK_NT tiles of 32)
+BCE_DL_BYTES = 64 << 20             # default bound of the backward's [B, col_chunk] logit-gradient slice
+
+
+def bce_default_col_chunk(B):
+    """The largest multiple of the sweep's column block whose [B, col_chunk] float32 slice stays within BCE_DL_BYTES."""
+    return max(BCE_COL_BLOCK, BCE_DL_BYTES // (4 * max(int(B), 1)) // BCE_COL_BLOCK * BCE_COL_BLOCK)
+
+
+def _bce_ws(B, cols, D, like):
+    nbytes = _ws_bytes("mrg_distmult_bce_workspace_bytes", B, cols, D)
+    if nbytes < 0:
+        check(int(nbytes), "mrg_distmult_bce_workspace_bytes")
+    return _ws(nbytes, like), int(nbytes)
+
+
+def distmult_bce_mean(q, ent, label_index, qkey, v_zero, v_one):
+    """mrg_distmult_bce_fwd, no autograd: mean over [B, N] of BCE(sigmoid(q ent^T), labels) as a float32 device scalar."""
+    li = label_index
+    B, D = q.shape
+    N = ent.shape[0]
+    loss = torch.empty((), dtype=torch.float32, device=q.device)
+    ws, nbytes = _bce_ws(B, N, D, q)
+    call("mrg_distmult_bce_fwd", (ptr(q), ptr(ent), ptr(qkey), ptr(li.keys), ptr(li.rowptr), ptr(li.objs), int(li.keys.numel()),
+                                  v_zero, v_one, B, N, D, ptr(loss), ptr(ws), nbytes, stream_of(q)),
+         nbytes=4 * (B + N) * D, flops=2 * B * N * D)
+    return loss
+
+
+def distmult_bce_dlogit(q, ent, label_index, qkey, v_zero, v_one, c0, c1, gscale, out=None):
+    """mrg_distmult_bce_dlogit, no autograd: the loss gradient with respect to the logits of the entities [c0, c1) as [B, c1 - c0],
+    written into the first B * (c1 - c0) floats of `out` when given.  gscale: float32 [1] on the device (upstream gradient / (B N))."""
+    li = label_index
+    (B, D), N, nc = q.shape, ent.shape[0], c1 - c0
+    if out is None:
+        out = torch.empty(B * nc, dtype=torch.float32, device=q.device)
+    ws, nbytes = _bce_ws(B, nc, D, q)
+    call("mrg_distmult_bce_dlogit", (ptr(q), ptr(ent), ptr(qkey), ptr(li.keys), ptr(li.rowptr), ptr(li.objs), int(li.keys.numel()),
+                                     v_zero, v_one, B, N, D, c0, c1, ptr(gscale), ptr(out), ptr(ws), nbytes, stream_of(q)),
+         nbytes=4 * (B + nc) * D + 4 * B * nc, flops=2 * B * nc * D)
+    return out[:B * nc].view(B, nc)
+
+
+class _DistMultBCE(torch.autograd.Function):
+    """loss(q, ent) of distmult_bce_all.  Forward: one sweep that stores nothing per element.  Backward: per column chunk the logit
+    gradient slice dl [B, chunk] (mrg_distmult_bce_dlogit, the tile recomputed) and the two gradient GEMMs of `linear` on it:
+    g_q += dl ent[c0:c1] (mrg_linear_bwd_input, accumulating) and g_ent[c0:c1] = dl^T q (mrg_linear_fwd on the transposed operands)."""
+
+    @staticmethod
+    def forward(ctx, q, ent, label_index, qkey, v_zero, v_one, col_chunk):
+        q, ent = f32c(q), f32c(ent)
+        li = label_index
+        require_hip(q, ent, qkey, li.keys, li.rowptr, li.objs)
+        ctx.li, ctx.v, ctx.col_chunk = li, (v_zero, v_one), col_chunk
+        ctx.save_for_backward(q, ent, qkey)
+        return distmult_bce_mean(q, ent, li, qkey, v_zero, v_one)
+
+    @staticmethod
+    def backward(ctx, g):
+        q, ent, qkey = ctx.saved_tensors
+        li, (v_zero, v_one), step = ctx.li, ctx.v, ctx.col_chunk
+        (B, D), N, st = q.shape, ent.shape[0], stream_of(q)
+        step = min(step, N)
+        need_q, need_ent = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        gscale = (g.detach().float().reshape(1) / float(B * N)).contiguous()          # stays on the device: no host synchronisation
+        dl = torch.empty(B * step, dtype=torch.float32, device=q.device)               # ONE slice, reused by every chunk
+        g_q = torch.empty_like(q) if need_q else None
+        g_ent = torch.empty_like(ent) if need_ent else None
+        esz = ent.element_size()
+        if need_ent:
+            qT, gws = q.t().contiguous(), _ws(_ws_bytes("mrg_gemm_workspace_bytes", B, D), q)
+        for c0 in range(0, N, step):
+            c1 = min(N, c0 + step)
+            nc = c1 - c0
+            distmult_bce_dlogit(q, ent, li, qkey, v_zero, v_one, c0, c1, gscale, out=dl)
+            work = dict(nbytes=4 * B * (D + nc) + 4 * D * nc, flops=2 * B * D * nc)
+            ent_c = ctypes.c_void_p(ent.data_ptr() + c0 * D * esz)
+            # a wide chunk: both gradients run on the transposed slice dl^T [nc, B], as `linear`'s backward does for Nout = N >> rows
+            wide_q = need_q and nc > 1024 and B <= 1024 and (B <= 128 or (B % 4 == 0 and D % 4 == 0))
+            dlT = dl[:B * nc].view(B, nc).t().contiguous() if (need_ent or wide_q) else None
+            if wide_q:
+                # g_q (+)= dl ent[c0:c1] is a reduction over the chunk's entities into a [B, D] block, the shape of a weight gradient
+                # (rows := nc, gY := dl^T, X := ent[c0:c1]): the split-over-rows kernel spreads it over the chip, where the row GEMM
+                # would give the whole reduction to ceil(B / 128) workgroups
+                out = g_q if c0 == 0 else torch.empty_like(g_q)
+                ws = _ws(_ws_bytes("mrg_linear_bwd_weight_workspace_bytes", nc, D, B), q)
+                call("mrg_linear_bwd_weight", (ptr(dlT), ent_c, None, ptr(out), None, ptr(ws), nc, D, 0, B, st), **work)
+                if c0 > 0:
+                    g_q += out
+            elif need_q:                  # g_q (+)= dl ent[c0:c1]
+                wt = _ws(_ws_bytes("mrg_linear_bwd_input_workspace_bytes", D, nc), q)
+                call("mrg_linear_bwd_input", (ptr(dl), ent_c, ptr(g_q), ptr(wt), B, D, nc, D, 1 if c0 > 0 else 0, st), **work)
+            if need_ent:
+                # g_ent[c0:c1] = dl^T q: a tall-skinny row GEMM over the transposed operands (the split-over-rows weight-gradient
+                # kernel keeps all of gW's row tiles in registers: it does not cover thousands of output rows, nor a chunk whose
+                # width is no multiple of 4)
+                call("mrg_linear_fwd", (ptr(dlT), ptr(qT), None, ctypes.c_void_p(g_ent.data_ptr() + c0 * D * esz), ptr(gws), nc, B, D, 0, st),
+                     **work)
+        return g_q, g_ent, None, None, None, None, None
+
+
+def distmult_bce_all(all_ent, sub_emb, rel_emb, label_index, subj, rel, label_smooth=0.0, col_chunk=None):
+    """The fixed-genotype driver's training loss (reference train/mr_lp_train.py Network._loss with sf_DisMult_op): the mean over [B, N]
+    of BCELoss(sigmoid((sub_emb * rel_emb) all_ent^T), label_index.labels(subj, rel, label_smooth)) as a float32 scalar, with no [B, N]
+    tensor -- neither the labels, nor the predictions, nor the loss terms.  The backward holds one [B, col_chunk] slice of the logit
+    gradient and its transpose (default: bce_default_col_chunk(B)).  label_index: sampler.LabelIndex on the same device.  No host synchronisation."""
+    for t in (all_ent, sub_emb, rel_emb, subj, rel):
+        if not t.is_cuda:
+            raise MrgnasError("distmult_bce_all runs on a HIP device (no CPU fallback); got a tensor on " + str(t.device))
+    B, N = int(sub_emb.shape[0]), int(all_ent.shape[0])
+    if B == 0 or N == 0 or N != label_index.num_ent or subj.numel() != B or rel.numel() != B:
+        raise ValueError("distmult_bce_all: all_ent [num_ent, D], sub_emb / rel_emb [B, D], subj / rel [B] with B > 0 expected")
+    if col_chunk is None:
+        col_chunk = bce_default_col_chunk(B)
+    col_chunk = int(col_chunk)
+    if col_chunk < 1:
+        raise ValueError("distmult_bce_all: col_chunk must be positive")
+    v_zero, v_one = label_index.label_values(label_smooth)
+    qkey = (subj.long() * (2 * label_index.num_rel) + rel.long()).contiguous()
+    return _DistMultBCE.apply(compose("mult", sub_emb, rel_emb), all_ent, label_index, qkey, v_zero, v_one, col_chunk)
 
 
 class _TransE(torch.autograd.Function):

@@ -218,15 +218,20 @@ class LabelIndex:
         self.rowptr, self.objs = rowptr.to(torch.int32).contiguous(), obj_s.to(torch.int32).contiguous()
         G.settle(t.device)
 
+    def label_values(self, label_smooth=0.0):
+        """(v_zero, v_one): the two values a label takes, as Python floats that are exact float32."""
+        v = torch.tensor([0.0, 1.0])
+        if label_smooth != 0.0:                                             # the reference's own float32 expression (data_set.py:23)
+            v = (1.0 - label_smooth) * v + (1.0 / self.num_ent)
+        return float(v[0]), float(v[1])
+
     def labels(self, subj, rel, label_smooth=0.0):
         subj, rel = subj.long(), rel.long()
         q = (subj * (2 * self.num_rel) + rel).contiguous()
         require_hip(q)
         B = int(q.numel())
         out = torch.empty(B, self.num_ent, dtype=torch.float32, device=q.device)
-        v = torch.tensor([0.0, 1.0])
-        if label_smooth != 0.0:                                             # the reference's own float32 expression (data_set.py:23)
-            v = (1.0 - label_smooth) * v + (1.0 / self.num_ent)
+        v = self.label_values(label_smooth)
         call("mrg_multi_hot_labels", (ptr(self.keys), ptr(self.rowptr), ptr(self.objs), ptr(q), B, int(self.keys.numel()), self.num_ent,
                                       float(v[0]), float(v[1]), ptr(out), stream_of(q)))
         return out

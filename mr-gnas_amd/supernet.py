@@ -22,6 +22,7 @@ import torch.nn.functional as F
 
 from . import functional as K
 from . import operations_lp as OPS
+from ._lib import MrgnasError
 from .graph import cached_on
 
 Genotype = collections.namedtuple('Genotype', 'alpha_cell concat_node score_func')   # reference configs/genotypes.py:3
@@ -424,6 +425,11 @@ class FixedNetwork(nn.Module):
             return self._forward(g, subj, rel)
 
     def _forward(self, g, subj, rel):
+        ent, rel_emb = self.embed(g)
+        return self.score_func(ent, ent[subj], rel_emb[rel])
+
+    def embed(self, g):
+        """(entity embeddings [N, D], relation embeddings [2R + 1, D]) after the cells: everything of the forward but the scorer."""
         ent = K.module_linear(self.linear_e, self.embedding_h.weight)
         rel_emb = torch.mm(self.rel_wt, self.embedding_e.weight)
         p_ent, p_rel = self._plans(g)
@@ -434,7 +440,18 @@ class FixedNetwork(nn.Module):
                 ent = cell(g, K.gather(ent, p_ent), K.gather(rel_emb, p_rel))
             ent = F.dropout(ent, self._dropout, training=self.training)
             rel_emb = torch.matmul(rel_emb, self.w_rel)
-        return self.score_func(ent, ent[subj], rel_emb[rel])
+        return ent, rel_emb
 
     def _loss(self, g, subj, rel, label):
         return self.criterion(self.forward(g, subj, rel), label)
+
+    def loss_fused(self, g, subj, rel, label_index, label_smooth=0.0):
+        """_loss on label_index.labels(subj, rel, label_smooth) with nn.BCELoss, without the [B, N] labels, predictions and loss terms
+        (functional.distmult_bce_all).  DistMult scoring only."""
+        if not isinstance(self.score_func, OPS.sf_DisMult_op):
+            raise MrgnasError(f"loss_fused covers the DistMult scorer only; this network scores with {type(self.score_func).__name__}")
+        if not self.embedding_h.weight.is_cuda:
+            raise MrgnasError("loss_fused runs on a HIP device (no CPU fallback); the network is on " + str(self.embedding_h.weight.device))
+        with K.deferred_counters():
+            ent, rel_emb = self.embed(g)
+            return K.distmult_bce_all(ent, ent[subj], rel_emb[rel], label_index, subj, rel, label_smooth)
