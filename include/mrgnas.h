@@ -34,7 +34,7 @@
 extern "C" {
 #endif
 
-#define MRG_ABI_VERSION 23   /* 23 (addition, no bump: nothing existing changed, and tests pin the number): mrg_distmult_rank, mrg_distmult_rank_workspace_bytes (raw / filtered DistMult ranks as a row GEMM with a counting epilogue); 23: mrg_gemm_set_epilogue removed (the row-order and transposed-accumulator store orders of the split-core row GEMM, measured slower, left the library; accumulator-order stores remain), mrg_gemm_set_wide8 and mrg_gemm_set_small take 0 or 1 only; 22: mrg_cand_linear_fwd, mrg_cand_linear_bwd_input, mrg_cand_linear_colsum_blocks, mrg_cand_linear_workspace_bytes (the candidate Linears of one node-classification MixedOp in one launch, BatchNorm sums included); 21: mrg_adam_step (multi-tensor Adam over the pointer tables of mrg_clip_sgd_step, two launches; per-tensor step counts and lr in device memory); 20: BatchNorm sums formed by a candidate's producer: mrg_gated_branch.given / given_n / given_stride (mrg_mix_stats_coef skips the sweep over such a candidate), mrg_dense_filter3_colsum_blocks, mrg_dense_filter_fwd3_colsum, mrg_gate_row_colsum_blocks, mrg_gate_row_fwd_colsum; 19: mrg_seg_std_workspace_bytes, mrg_seg_std_fwd, mrg_seg_std_bwd (a_std, the standard-deviation aggregator of the node-classification task); 18: mrg_conve_* (the ConvE feature path: BN0 statistics, conv, BN1, split-K fc and their gradients, stacked or interleaved image layout); 17: mrg_ccorr_rows, mrg_ccorr_matrix, mrg_ccorr_matrix_grad (standalone circular correlation: per-row kernel, and the circulant of a shared row with its gradient fold for the row GEMM); 16: mrg_set_stream_blocks, mrg_gate_collapse and mrg_gate_param_grad removed (the streaming grid bound is fixed; the three-segment forms remain); 15: mrg_gated_branch.valid_rows and the valid_rows argument of mrg_mix_finalize_bwd / mrg_zero_* except colstats (the device row count of a static step graph, passed per call instead of the process-wide registry of 13), mrg_linear_bwd_weight_share (the weight gradient of one range of a grouped launch, instead of the process-wide setter of 14); 14: mrg_clip_sgd_step, mrg_optim_chunk (clip_grad_norm_ + SGD with momentum over every parameter tensor in three launches), mrg_gated_branch.act (tanh behind the BatchNorm: CompGraphConv's tail on the epilogue kernels), mrg_gemm_set_small (few-row products on two-tile column blocks), a weight-gradient share setter, mrg_segmax_bwd_input (a_max's input gradient without a dense product); 13: a registry of device-side row counts (the sampled search step as one replayable HIP graph), mrg_seg_reduce_bwd_ordered (aggregator backward walked in destination order), mrg_gemm_set_q (the 16 x 16 x 32 row GEMM at three workgroups per CU for 129..224 output columns); 12: mrg_act_grad_transpose (the [B, N] scorer's output gradient, activation folded in, as [N, B] rows); 11: mrg_gemm_set_wide8 (eight-tile column block for D = 256); 10: mrg_gemm_set_epilogue(2) (transposed accumulators: a tested comparison point); 9: mrg_gated_branch (the MixedOp epilogue recomputes f_dense_comp's output from its gate and f_sparse_comp's from its row factor), mrg_gate_row_fwd / _bwd, mrg_sum_rows_gather, mrg_wgrad_set_variant, mrg_dense_filter_fwd3 out == NULL; 8: mrg_zero_* (cell-zero MixedOp recomputed from the tables), mrg_linear_bwd_input3_pair, mrg_sample_edge_neighborhood; 7: mrg_gemm_set_epilogue (row-order stores of the split-core row GEMM), mrg_set_stream_blocks, mrg_gemm_set_mode(2); 6: fused a_mean (run-sum epilogue, heads reducer, bit-mask backward), mrg_mix_stats_coef; 5: three-segment dense filter entry points; 4: mrg_linear_relu_segmax_fwd (fused a_max); 3: device graph / plan builders, samplers, [B, N] scorers, ranking; 2: GEMM workspaces, span_gcs ext_scal */
+#define MRG_ABI_VERSION 23   /* 23 (addition, no bump): mrg_rows_rank, mrg_transe_bce_fwd / _dlogit / _workspace_bytes, mrg_transe_dist_bwd, mrg_transe_rank / _workspace_bytes (1-N loss and ranks of ConvE and TransE without [B, N] tensors); 23 (addition, no bump: nothing existing changed, and tests pin the number): mrg_distmult_rank, mrg_distmult_rank_workspace_bytes (raw / filtered DistMult ranks as a row GEMM with a counting epilogue); 23: mrg_gemm_set_epilogue removed (the row-order and transposed-accumulator store orders of the split-core row GEMM, measured slower, left the library; accumulator-order stores remain), mrg_gemm_set_wide8 and mrg_gemm_set_small take 0 or 1 only; 22: mrg_cand_linear_fwd, mrg_cand_linear_bwd_input, mrg_cand_linear_colsum_blocks, mrg_cand_linear_workspace_bytes (the candidate Linears of one node-classification MixedOp in one launch, BatchNorm sums included); 21: mrg_adam_step (multi-tensor Adam over the pointer tables of mrg_clip_sgd_step, two launches; per-tensor step counts and lr in device memory); 20: BatchNorm sums formed by a candidate's producer: mrg_gated_branch.given / given_n / given_stride (mrg_mix_stats_coef skips the sweep over such a candidate), mrg_dense_filter3_colsum_blocks, mrg_dense_filter_fwd3_colsum, mrg_gate_row_colsum_blocks, mrg_gate_row_fwd_colsum; 19: mrg_seg_std_workspace_bytes, mrg_seg_std_fwd, mrg_seg_std_bwd (a_std, the standard-deviation aggregator of the node-classification task); 18: mrg_conve_* (the ConvE feature path: BN0 statistics, conv, BN1, split-K fc and their gradients, stacked or interleaved image layout); 17: mrg_ccorr_rows, mrg_ccorr_matrix, mrg_ccorr_matrix_grad (standalone circular correlation: per-row kernel, and the circulant of a shared row with its gradient fold for the row GEMM); 16: mrg_set_stream_blocks, mrg_gate_collapse and mrg_gate_param_grad removed (the streaming grid bound is fixed; the three-segment forms remain); 15: mrg_gated_branch.valid_rows and the valid_rows argument of mrg_mix_finalize_bwd / mrg_zero_* except colstats (the device row count of a static step graph, passed per call instead of the process-wide registry of 13), mrg_linear_bwd_weight_share (the weight gradient of one range of a grouped launch, instead of the process-wide setter of 14); 14: mrg_clip_sgd_step, mrg_optim_chunk (clip_grad_norm_ + SGD with momentum over every parameter tensor in three launches), mrg_gated_branch.act (tanh behind the BatchNorm: CompGraphConv's tail on the epilogue kernels), mrg_gemm_set_small (few-row products on two-tile column blocks), a weight-gradient share setter, mrg_segmax_bwd_input (a_max's input gradient without a dense product); 13: a registry of device-side row counts (the sampled search step as one replayable HIP graph), mrg_seg_reduce_bwd_ordered (aggregator backward walked in destination order), mrg_gemm_set_q (the 16 x 16 x 32 row GEMM at three workgroups per CU for 129..224 output columns); 12: mrg_act_grad_transpose (the [B, N] scorer's output gradient, activation folded in, as [N, B] rows); 11: mrg_gemm_set_wide8 (eight-tile column block for D = 256); 10: mrg_gemm_set_epilogue(2) (transposed accumulators: a tested comparison point); 9: mrg_gated_branch (the MixedOp epilogue recomputes f_dense_comp's output from its gate and f_sparse_comp's from its row factor), mrg_gate_row_fwd / _bwd, mrg_sum_rows_gather, mrg_wgrad_set_variant, mrg_dense_filter_fwd3 out == NULL; 8: mrg_zero_* (cell-zero MixedOp recomputed from the tables), mrg_linear_bwd_input3_pair, mrg_sample_edge_neighborhood; 7: mrg_gemm_set_epilogue (row-order stores of the split-core row GEMM), mrg_set_stream_blocks, mrg_gemm_set_mode(2); 6: fused a_mean (run-sum epilogue, heads reducer, bit-mask backward), mrg_mix_stats_coef; 5: three-segment dense filter entry points; 4: mrg_linear_relu_segmax_fwd (fused a_max); 3: device graph / plan builders, samplers, [B, N] scorers, ranking; 2: GEMM workspaces, span_gcs ext_scal */
 
 #define MRG_OK            0
 #define MRG_E_NULLPTR    -1   /* a required pointer is NULL */
@@ -757,6 +757,44 @@ int mrg_distmult_bce_fwd(const float *q, const float *ent, const int64_t *qkey, 
 int mrg_distmult_bce_dlogit(const float *q, const float *ent, const int64_t *qkey, const int64_t *keys, const int32_t *rowptr,
                             const int32_t *objs, int64_t U, float v_zero, float v_one, int64_t B, int64_t N, int D, int64_t c0,
                             int64_t c1, const float *gscale, float *dl, void *ws, int64_t ws_bytes, void *stream);
+/* mrg_distmult_rank for query rows the caller already holds (q [Q][D]: DistMult's ent[a] * rel[r], ConvE's hidden vector after BN2 + ReLU):
+ * candidate e scores x_e = sum_c q[i, c] * ent[e, c]; everything else -- target rows gathered, rule, filter, cores, workspace
+ * (mrg_distmult_rank_workspace_bytes), errors -- is mrg_distmult_rank's.  Rows that are not 16-byte aligned run the exact-f32 core.
+ * Additive: ABI 23. */
+int mrg_rows_rank(const float *q, const float *ent, const int32_t *t_idx, const int64_t *qkey, const int32_t *when, const int64_t *keys,
+                  const int32_t *rowptr, const int32_t *members, const int32_t *gone_at, int64_t U, int64_t Q, int64_t N, int D,
+                  int64_t *ranks, void *ws, int64_t ws_bytes, void *stream);
+/* The 1-N loss, its logit gradient and the filtered ranks of sf_TransE_op without a [B, N] tensor (csrc/transe_1n.hip).  Additive: ABI 23.
+ *   dist[b, e] = sum_c |obj[b, c] - ent[e, c]|  (obj [B][D] = sub + rel in float32, formed by the caller),  x = gamma - dist,
+ *   p = sigmoid(x) in float32.  Every distance is one float32 accumulator over c ascending: bit-identical with mrg_transe_score_fwd's.
+ * mrg_transe_bce_fwd / mrg_transe_bce_dlogit: mrg_distmult_bce_fwd / _dlogit on this x -- same labels (index keys / rowptr / objs, key
+ *   qkey[b]), same terms, same saturation, float64 partials per workgroup added in a fixed order (bitwise repeatable), gscale on the
+ *   device.  Workspace: mrg_transe_bce_workspace_bytes(B, N, D) for the forward and (B, c1 - c0, D) for the logit gradient: two integers
+ *   per query and one float64 per tile of 64 x 64 elements.
+ * mrg_transe_dist_bwd: the gradients that one slice dl [B][nc] (leading dimension ld >= nc) of the loss gradient with respect to x
+ *   contributes, for the nc entity rows at ent_c: d loss / d dist = -dl,
+ *     gobj[b, c]   (+)= sum_e (-dl[b, e]) * sgn(obj[b, c] - ent_c[e, c])      (accumulate != 0: added to gobj)
+ *     gent_c[e, c]   = -sum_b (-dl[b, e]) * sgn(obj[b, c] - ent_c[e, c])      sgn(0) = 0
+ *   either output may be NULL.  Sums in a fixed order.
+ * mrg_transe_rank: ranks[i] = 1 + #(dist_e < dist_t) + #(dist_e == dist_t, e < t) over candidates e != t = t_idx[i] that are not filtered:
+ *   mrg_distmult_rank's rule on the score gamma - dist and its filter (index, gone_at > when), compared on dist itself; the target's
+ *   distance is formed by the same float32 chain, so a duplicate of the target's row ties exactly.  Integer atomics only.
+ *   Workspace: mrg_transe_rank_workspace_bytes(Q, N, D), O(Q) bytes.
+ * 1 <= D <= 1024, N bounded as for mrg_distmult_rank; indices are trusted.  Argument errors are returned before any HIP call; B == 0 /
+ * Q == 0 returns MRG_OK with nothing launched. */
+int64_t mrg_transe_bce_workspace_bytes(int64_t B, int64_t ncols, int D);
+int mrg_transe_bce_fwd(const float *obj, const float *ent, const int64_t *qkey, const int64_t *keys, const int32_t *rowptr,
+                       const int32_t *objs, int64_t U, float gamma, float v_zero, float v_one, int64_t B, int64_t N, int D, float *loss,
+                       void *ws, int64_t ws_bytes, void *stream);
+int mrg_transe_bce_dlogit(const float *obj, const float *ent, const int64_t *qkey, const int64_t *keys, const int32_t *rowptr,
+                          const int32_t *objs, int64_t U, float gamma, float v_zero, float v_one, int64_t B, int64_t N, int D,
+                          int64_t c0, int64_t c1, const float *gscale, float *dl, void *ws, int64_t ws_bytes, void *stream);
+int mrg_transe_dist_bwd(const float *ent_c, const float *obj, const float *dl, int64_t ld, float *gent_c, float *gobj, int accumulate,
+                        int64_t B, int64_t nc, int D, void *stream);
+int64_t mrg_transe_rank_workspace_bytes(int64_t Q, int64_t N, int D);
+int mrg_transe_rank(const float *obj, const float *ent, const int32_t *t_idx, const int64_t *qkey, const int32_t *when,
+                    const int64_t *keys, const int32_t *rowptr, const int32_t *members, const int32_t *gone_at, int64_t U, int64_t Q,
+                    int64_t N, int D, int64_t *ranks, void *ws, int64_t ws_bytes, void *stream);
 /* sf_TransE_op.forward, reference models/operations_lp.py:101-112:
  *   score[b, n] = sigmoid(gamma - sum_c |sub[b, c] + rel[b, c] - ent[n, c]|)
  * backward: gobj [B][D] (the gradient of both sub and rel) and gent [N][D]; either may be NULL.

@@ -10,10 +10,9 @@
 // Split-bf16 core (rowgemm_x3s_k) for D > 48 with D % 4 == 0, the entity rows pre-split per block of BCE_COLS columns (so the split
 // table is O(BCE_COLS * D) whatever N is); every other D on the exact-f32 core (rowgemm_k).  Rows go in chunks of RANK_CHUNK.
 #include "gemm_dispatch.hpp"
+#include "sweep_prep.hpp"      // bce_prep_k, bce_finish_k
 
 namespace mrg {
-
-constexpr int64_t BCE_COLS = (int64_t)RANK_NT * 32 * 128;      // entity columns per sweep launch (28 672): bounds the split table
 
 struct BcePlan { size_t ent_split, qlist, partial, total; int64_t nrb, ncb; };
 inline size_t bce_up(size_t x) { return (x + 255) & ~(size_t)255; }
@@ -30,38 +29,6 @@ inline BcePlan bce_plan(int64_t B, int64_t ncols, int D) {
   p.partial = off; off += bce_up((size_t)p.nrb * p.ncb * sizeof(double));
   p.total = off;
   return p;
-}
-
-// qlist[i] = {begin, end} of the object list of qkey[i] (empty when the key is unknown)
-__global__ void bce_prep_k(const int64_t* __restrict__ qkey, const int64_t* __restrict__ keys, const int32_t* __restrict__ rowptr, int64_t U,
-                           int64_t B, int32_t* __restrict__ qlist) {
-  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= B) return;
-  int lo = 0, hi = 0;
-  if (U > 0) {
-    const int64_t key = qkey[i];
-    int64_t b = 0, e = U;
-    while (b < e) {
-      const int64_t mid = b + ((e - b) >> 1);
-      if (keys[mid] < key) b = mid + 1; else e = mid;
-    }
-    if (b < U && keys[b] == key) { lo = rowptr[b]; hi = rowptr[b + 1]; }
-  }
-  *reinterpret_cast<int2*>(qlist + i * 2) = make_int2(lo, hi);
-}
-
-// loss = scale * (the n partials added in a fixed order: thread t adds partial[t], partial[t + 256], ..., then a tree over the threads)
-__global__ __launch_bounds__(256) void bce_finish_k(const double* __restrict__ partial, int64_t n, double scale, float* __restrict__ loss) {
-  __shared__ double s[256];
-  double acc = 0.0;
-  for (int64_t i = threadIdx.x; i < n; i += 256) acc += partial[i];
-  s[threadIdx.x] = acc;
-  __syncthreads();
-  for (int w = 128; w > 0; w >>= 1) {
-    if ((int)threadIdx.x < w) s[threadIdx.x] += s[threadIdx.x + w];
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) loss[0] = (float)(s[0] * scale);
 }
 
 // one launch: g.A1 / rows, the columns' count g.N and the epilogue's values are set; ent_c points at the first column's entity row

@@ -11,6 +11,7 @@
 // The persistent transposed-accumulator kernel and the two-waves-per-SIMD kernel of rounds 2-3 live in tools/lab/ (tools/gemm_x3_lab.hip
 // still times them).  The switches that move a launch off its default kernel are GemmSwitches (x3_parts.hpp).
 #pragma once
+#include "sweep_limits.hpp"
 #include "gemm_x3.hpp"
 #include "gemm_x3s.hpp"
 #include "gemm_x3s8.hpp"
@@ -125,9 +126,7 @@ inline int launch_rowgemm_x3_mode_colsum(GemmArgs a, const void* Bp, hipStream_t
 }
 
 // ---- queries x all entities (rank.hip, bce.hip): the sweeps that launch rowgemm_x3s_k / rowgemm_k themselves -------------------------
-constexpr int64_t RANK_CHUNK = 8192;          // queries per sweep launch: bounds the [chunk, D] operands of the workspace and grid.x
-constexpr int RANK_NT = 7;                    // column tiles per block of the sweep
-constexpr int64_t RANK_MAX_N = 65535LL * RANK_NT * 32;     // grid.y
+// (RANK_CHUNK, RANK_NT, RANK_MAX_N, BCE_COLS: sweep_limits.hpp, shared with the L1 sweeps of transe_1n.hip)
 inline bool rank_split_core(int D) { return gemm_mode() != 1 && D > 48 && D % 4 == 0; }
 
 inline size_t gemm_workspace_bytes(int K, int N) {

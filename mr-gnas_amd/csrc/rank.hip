@@ -10,7 +10,10 @@
 //   3. EPI_RANK sweeps all entities and adds, per (row, workgroup), the number of unfiltered candidates that beat the target.
 // Split-bf16 core (rowgemm_x3s_k, the entity table pre-split once per call) where it takes the shape, D > 48 and D % 4 == 0;
 // every other D runs the same two epilogues on the exact-f32 core (rowgemm_k).
+// mrg_rows_rank is the same body for query rows the caller already holds (ConvE's hidden vector, any "dot" scorer): step 1 gathers
+// the target rows only.  rank_prep_k / rank_finish_k live in sweep_prep.hpp, shared with the L1 sweeps of transe_1n.hip.
 #include "gemm_dispatch.hpp"
+#include "sweep_prep.hpp"      // rank_prep_k, rank_finish_k
 
 namespace mrg {
 
@@ -30,31 +33,6 @@ inline RankPlan rank_plan(int64_t Q, int64_t N, int D) {
   p.counts = off; off += rank_up((size_t)Q * sizeof(unsigned));
   p.total = off;
   return p;
-}
-
-// qinfo[i] = {target, begin, end of the list of qkey[i] (empty when the key is -1 or unknown), when}; counts[i] = 0
-__global__ void rank_prep_k(const int32_t* __restrict__ t_idx, const int64_t* __restrict__ qkey, const int32_t* __restrict__ when,
-                            const int64_t* __restrict__ keys, const int32_t* __restrict__ rowptr, int64_t U, int64_t Q,
-                            int32_t* __restrict__ qinfo, unsigned* __restrict__ counts) {
-  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= Q) return;
-  int lo = 0, hi = 0;
-  const int64_t key = (qkey && U > 0) ? qkey[i] : -1;
-  if (key >= 0) {
-    int64_t b = 0, e = U;
-    while (b < e) {
-      const int64_t mid = b + ((e - b) >> 1);
-      if (keys[mid] < key) b = mid + 1; else e = mid;
-    }
-    if (b < U && keys[b] == key) { lo = rowptr[b]; hi = rowptr[b + 1]; }
-  }
-  *reinterpret_cast<int4*>(qinfo + i * 4) = make_int4(t_idx[i], lo, hi, when ? when[i] : -1);
-  counts[i] = 0;
-}
-
-__global__ void rank_finish_k(const unsigned* __restrict__ counts, int64_t* __restrict__ ranks, int64_t Q) {
-  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < Q) ranks[i] = 1 + (int64_t)counts[i];
 }
 
 // one chunk: target scores, then the sweep.  g: A1 / K1 / rows and the rank pointers of the chunk are set
@@ -93,13 +71,11 @@ extern "C" int64_t mrg_distmult_rank_workspace_bytes(int64_t Q, int64_t N, int D
   return (int64_t)rank_plan(Q, N, D).total;
 }
 
-extern "C" int mrg_distmult_rank(const float* ent, const float* rel, const int32_t* a_idx, const int32_t* r_idx, const int32_t* t_idx,
-                                 const int64_t* qkey, const int32_t* when, const int64_t* keys, const int32_t* rowptr, const int32_t* members,
-                                 const int32_t* gone_at, int64_t U, int64_t Q, int64_t N, int D, int64_t* ranks, void* ws, int64_t ws_bytes,
-                                 void* stream) {
-  if (U < 0 || !rank_shape_ok(Q, N, D)) return MRG_E_SHAPE;
-  if (Q == 0) return MRG_OK;
-  if (!ent || !rel || !a_idx || !r_idx || !t_idx || !ranks) return MRG_E_NULLPTR;
+// The body of both entry points.  rows_q == NULL: the chunk's query rows are ent[a] * rel[r] (mrg_distmult_rank); else they are the
+// caller's rows_q + q0 * D (mrg_rows_rank).  The target rows are gathered in both.
+static int rank_run(const float* rows_q, const float* ent, const float* rel, const int32_t* a_idx, const int32_t* r_idx, const int32_t* t_idx,
+                    const int64_t* qkey, const int32_t* when, const int64_t* keys, const int32_t* rowptr, const int32_t* members,
+                    const int32_t* gone_at, int64_t U, int64_t Q, int64_t N, int D, int64_t* ranks, void* ws, int64_t ws_bytes, void* stream) {
   if (U > 0 && (!qkey || !when || !keys || !rowptr || !members || !gone_at)) return MRG_E_NULLPTR;
   const RankPlan p = rank_plan(Q, N, D);
   if (!ws || ws_bytes < (int64_t)p.total) return MRG_E_WORKSPACE;
@@ -110,20 +86,24 @@ extern "C" int mrg_distmult_rank(const float* ent, const float* rel, const int32
   int32_t* qinfo = (int32_t*)(w + p.qinfo);
   float* tscore = (float*)(w + p.tscore);
   unsigned* counts = (unsigned*)(w + p.counts);
-  const bool split = rank_split_core(D);
-  const bool vec = D % 4 == 0 && aligned16(ent);
+  const bool qal = !rows_q || aligned16(rows_q);                            // the workspace's rows are aligned; a caller's may not be
+  const bool split = rank_split_core(D) && qal;
+  const bool vec = D % 4 == 0 && aligned16(ent) && qal;
 
   hipLaunchKernelGGL(rank_prep_k, dim3((unsigned)((Q + 255) / 256)), dim3(256), 0, st, t_idx, qkey, when, keys, rowptr, U, Q, qinfo, counts);
   MRG_LAUNCH_CHECK();
   if (split) launch_bsplit(ent, D, 1, (int)N, D, RANK_NT, w + p.ent_split, st);
   for (int64_t q0 = 0; q0 < Q; q0 += RANK_CHUNK) {
     const int64_t rows = Q - q0 < RANK_CHUNK ? Q - q0 : RANK_CHUNK;
-    int rc = mrg_gather_compose_fwd(MRG_COMPOSE_MULT, ent, rel, a_idx + q0, r_idx + q0, A, rows, D, stream);
+    int rc = MRG_OK;
+    const float* Aq = A;
+    if (rows_q) Aq = rows_q + q0 * D;
+    else rc = mrg_gather_compose_fwd(MRG_COMPOSE_MULT, ent, rel, a_idx + q0, r_idx + q0, A, rows, D, stream);
     if (rc != MRG_OK) return rc;
-    rc = mrg_gather_compose_fwd(-1, ent, rel, t_idx + q0, r_idx + q0, T, rows, D, stream);
+    rc = mrg_gather_compose_fwd(-1, ent, rel, t_idx + q0, rows_q ? nullptr : r_idx + q0, T, rows, D, stream);
     if (rc != MRG_OK) return rc;
     GemmArgs g{};
-    g.A1 = A; g.A2 = A; g.K1 = D; g.K2 = 0; g.rows = rows;
+    g.A1 = Aq; g.A2 = Aq; g.K1 = D; g.K2 = 0; g.rows = rows;
     gemm_set_rank(g, RankEpi{tscore + q0, tscore + q0, qinfo + q0 * 4, members, gone_at, counts + q0});
     if (split) rc = rank_chunk_split(g, T, w + p.t_split, w + p.ent_split, N, D, st);
     else if (vec) rc = rank_chunk_exact<true>(g, T, ent, N, D, st);
@@ -133,4 +113,23 @@ extern "C" int mrg_distmult_rank(const float* ent, const float* rel, const int32
   hipLaunchKernelGGL(rank_finish_k, dim3((unsigned)((Q + 255) / 256)), dim3(256), 0, st, counts, ranks, Q);
   MRG_LAUNCH_CHECK();
   return MRG_OK;
+}
+
+extern "C" int mrg_distmult_rank(const float* ent, const float* rel, const int32_t* a_idx, const int32_t* r_idx, const int32_t* t_idx,
+                                 const int64_t* qkey, const int32_t* when, const int64_t* keys, const int32_t* rowptr, const int32_t* members,
+                                 const int32_t* gone_at, int64_t U, int64_t Q, int64_t N, int D, int64_t* ranks, void* ws, int64_t ws_bytes,
+                                 void* stream) {
+  if (U < 0 || !rank_shape_ok(Q, N, D)) return MRG_E_SHAPE;
+  if (Q == 0) return MRG_OK;
+  if (!ent || !rel || !a_idx || !r_idx || !t_idx || !ranks) return MRG_E_NULLPTR;
+  return rank_run(nullptr, ent, rel, a_idx, r_idx, t_idx, qkey, when, keys, rowptr, members, gone_at, U, Q, N, D, ranks, ws, ws_bytes, stream);
+}
+
+extern "C" int mrg_rows_rank(const float* q, const float* ent, const int32_t* t_idx, const int64_t* qkey, const int32_t* when, const int64_t* keys,
+                             const int32_t* rowptr, const int32_t* members, const int32_t* gone_at, int64_t U, int64_t Q, int64_t N, int D,
+                             int64_t* ranks, void* ws, int64_t ws_bytes, void* stream) {
+  if (U < 0 || !rank_shape_ok(Q, N, D)) return MRG_E_SHAPE;
+  if (Q == 0) return MRG_OK;
+  if (!q || !ent || !t_idx || !ranks) return MRG_E_NULLPTR;
+  return rank_run(q, ent, nullptr, nullptr, nullptr, t_idx, qkey, when, keys, rowptr, members, gone_at, U, Q, N, D, ranks, ws, ws_bytes, stream);
 }

@@ -5,6 +5,8 @@
 // An L1 distance has no matrix form, so this is VALU work: B*N*D absolute differences (744 M at B = 256, FB15k-237,
 // D = 200).  Tiles of 64 entity rows x 8 query rows are staged through LDS in 64-column slices (coalesced global reads,
 // conflict-free LDS reads: the entity tile is padded to 65 floats per row, the query tile is read as a broadcast).
+// The two backward kernels also serve the 1-N TransE loss that keeps no [B, N] tensor (transe_1n.hip): their SLICE instances read
+// d loss / d dist from a [B, nc] slice of the logit gradient (mrg_transe_dist_bwd).
 #include <hip/hip_runtime.h>
 #include "common.hpp"
 
@@ -50,9 +52,12 @@ __device__ __forceinline__ float sgn(float x) { return (x > 0.f) - (x < 0.f); }
 // dd[b, n] = d loss / d dist[b, n] = -g[b, n] * s (1 - s)
 // gobj[b, c] = sum_n dd[b, n] * sign(obj[b, c] - ent[n, c])            (returned for both sub and rel)
 // block: 8 query rows x 64 columns; 4 n-lanes per column; every n is visited by exactly one lane, lanes combined in order
+// SLICE (mrg_transe_dist_bwd): dd[b, n] = -g[b * ld + n], g the [B, N] slice of the loss gradient with respect to gamma - dist of the N
+// entity rows at `ent`; `sub` is obj itself (rel, score unused); accumulate: gobj += instead of gobj =.
+template <bool SLICE>
 __global__ __launch_bounds__(256) void transe_bwd_obj_k(const float* __restrict__ ent, const float* __restrict__ sub, const float* __restrict__ rel,
                                                         const float* __restrict__ g, const float* __restrict__ score, float* __restrict__ gobj,
-                                                        int64_t B, int64_t N, int D) {
+                                                        int64_t B, int64_t N, int D, int64_t ld, int accumulate) {
   __shared__ float sdd[TE_B][256];
   __shared__ float red[4][TE_B][TE_C];
   const int64_t b0 = (int64_t)blockIdx.y * TE_B;
@@ -60,14 +65,19 @@ __global__ __launch_bounds__(256) void transe_bwd_obj_k(const float* __restrict_
   float o[TE_B], acc[TE_B];
 #pragma unroll
   for (int b = 0; b < TE_B; ++b) {
-    o[b] = (b0 + b < B && c < D) ? sub[(b0 + b) * D + c] + rel[(b0 + b) * D + c] : 0.f;
+    if constexpr (SLICE) o[b] = (b0 + b < B && c < D) ? sub[(b0 + b) * D + c] : 0.f;
+    else o[b] = (b0 + b < B && c < D) ? sub[(b0 + b) * D + c] + rel[(b0 + b) * D + c] : 0.f;
     acc[b] = 0.f;
   }
   for (int64_t n0 = 0; n0 < N; n0 += 256) {
     for (int i = threadIdx.x; i < TE_B * 256; i += 256) {
       const int b = i >> 8, n = i & 255;
       float v = 0.f;
-      if (b0 + b < B && n0 + n < N) { const float s = score[(b0 + b) * N + n0 + n]; v = -g[(b0 + b) * N + n0 + n] * s * (1.f - s); }
+      if constexpr (SLICE) {
+        if (b0 + b < B && n0 + n < N) v = -g[(b0 + b) * ld + n0 + n];
+      } else {
+        if (b0 + b < B && n0 + n < N) { const float s = score[(b0 + b) * N + n0 + n]; v = -g[(b0 + b) * N + n0 + n] * s * (1.f - s); }
+      }
       sdd[b][n] = v;
     }
     __syncthreads();
@@ -84,23 +94,33 @@ __global__ __launch_bounds__(256) void transe_bwd_obj_k(const float* __restrict_
   if (q == 0 && c < D) {
 #pragma unroll
     for (int b = 0; b < TE_B; ++b)
-      if (b0 + b < B) gobj[(b0 + b) * D + c] = ((red[0][b][threadIdx.x] + red[1][b][threadIdx.x]) + red[2][b][threadIdx.x]) + red[3][b][threadIdx.x];
+      if (b0 + b < B) {
+        const float v = ((red[0][b][threadIdx.x] + red[1][b][threadIdx.x]) + red[2][b][threadIdx.x]) + red[3][b][threadIdx.x];
+        if constexpr (SLICE) gobj[(b0 + b) * D + c] = accumulate ? gobj[(b0 + b) * D + c] + v : v;
+        else gobj[(b0 + b) * D + c] = v;
+      }
   }
 }
 
 // gent[n, c] = -sum_b dd[b, n] * sign(obj[b, c] - ent[n, c]);   block: 4 entity rows x 64 columns, loop over b in order
+// SLICE: as in transe_bwd_obj_k
+template <bool SLICE>
 __global__ __launch_bounds__(256) void transe_bwd_ent_k(const float* __restrict__ ent, const float* __restrict__ sub, const float* __restrict__ rel,
                                                         const float* __restrict__ g, const float* __restrict__ score, float* __restrict__ gent,
-                                                        int64_t B, int64_t N, int D) {
+                                                        int64_t B, int64_t N, int D, int64_t ld) {
   const int64_t n = (int64_t)blockIdx.y * 4 + (threadIdx.x >> 6);
   const int c = blockIdx.x * TE_C + (threadIdx.x & 63);
   if (n >= N || c >= D) return;
   const float e = ent[n * D + c];
   float acc = 0.f;
   for (int64_t b = 0; b < B; ++b) {
-    const float s = score[b * N + n];
-    const float dd = -g[b * N + n] * s * (1.f - s);
-    acc -= dd * sgn(sub[b * D + c] + rel[b * D + c] - e);
+    if constexpr (SLICE) {
+      acc -= -g[b * ld + n] * sgn(sub[b * D + c] - e);
+    } else {
+      const float s = score[b * N + n];
+      const float dd = -g[b * N + n] * s * (1.f - s);
+      acc -= dd * sgn(sub[b * D + c] + rel[b * D + c] - e);
+    }
   }
   gent[n * D + c] = acc;
 }
@@ -166,11 +186,39 @@ extern "C" int mrg_transe_score_bwd(const float* ent, const float* sub, const fl
   if (!ent || !sub || !rel || !gscore || !score) return MRG_E_NULLPTR;
   if (gobj) {
     dim3 grid((unsigned)((D + TE_C - 1) / TE_C), (unsigned)((B + TE_B - 1) / TE_B));
-    hipLaunchKernelGGL(transe_bwd_obj_k, grid, dim3(256), 0, st, ent, sub, rel, gscore, score, gobj, B, N, D);
+    hipLaunchKernelGGL(transe_bwd_obj_k<false>, grid, dim3(256), 0, st, ent, sub, rel, gscore, score, gobj, B, N, D, N, 0);
   }
   if (gent) {
     dim3 grid((unsigned)((D + TE_C - 1) / TE_C), (unsigned)((N + 3) / 4));
-    hipLaunchKernelGGL(transe_bwd_ent_k, grid, dim3(256), 0, st, ent, sub, rel, gscore, score, gent, B, N, D);
+    hipLaunchKernelGGL(transe_bwd_ent_k<false>, grid, dim3(256), 0, st, ent, sub, rel, gscore, score, gent, B, N, D, N);
+  }
+  MRG_LAUNCH_CHECK();
+  return MRG_OK;
+}
+
+// The two gradients of the fused 1-N TransE loss (transe_1n.hip) from one [B, nc] slice dl of the loss gradient with respect to
+// x = gamma - dist: the kernels above with dd = -dl read from the slice.  ent_c / gent_c: the slice's first entity row.
+extern "C" int mrg_transe_dist_bwd(const float* ent_c, const float* obj, const float* dl, int64_t ld, float* gent_c, float* gobj, int accumulate,
+                                   int64_t B, int64_t nc, int D, void* stream) {
+  if (B < 0 || nc < 1 || D <= 0 || ld < nc || (B + TE_B - 1) / TE_B > 65535) return MRG_E_SHAPE;
+  if (B == 0) return MRG_OK;
+  if (!ent_c || !obj || !dl) return MRG_E_NULLPTR;
+  hipStream_t st = (hipStream_t)stream;
+  if (gobj) {
+    dim3 grid((unsigned)((D + TE_C - 1) / TE_C), (unsigned)((B + TE_B - 1) / TE_B));
+    hipLaunchKernelGGL(transe_bwd_obj_k<true>, grid, dim3(256), 0, st, ent_c, obj, (const float*)nullptr, dl, (const float*)nullptr, gobj, B, nc, D, ld,
+                       accumulate);
+  }
+  if (gent_c) {
+    const float* e = ent_c;
+    float* ge = gent_c;
+    const float* d = dl;
+    for (int64_t n0 = 0; n0 < nc; n0 += 65535LL * 4) {              // grid.y
+      const int64_t n = nc - n0 < 65535LL * 4 ? nc - n0 : 65535LL * 4;
+      dim3 grid((unsigned)((D + TE_C - 1) / TE_C), (unsigned)((n + 3) / 4));
+      hipLaunchKernelGGL(transe_bwd_ent_k<true>, grid, dim3(256), 0, st, e + n0 * D, obj, (const float*)nullptr, d + n0, (const float*)nullptr, ge + n0 * D,
+                         B, n, D, ld);
+    }
   }
   MRG_LAUNCH_CHECK();
   return MRG_OK;

@@ -1,0 +1,370 @@
+// The 1-N TransE loss, its logit gradient and the filtered ranks without a [B, N] tensor (reference models/operations_lp.py:101-112
+// sf_TransE_op, train/mr_lp_train.py Network._loss and predict; labels utils/data_set.py:21-33).
+//   dist[b, e] = sum_c |obj[b, c] - ent[e, c]|     obj = sub + rel, float32, formed by the caller
+//   x[b, e]    = gamma - dist[b, e]                p = sigmoid(x) in float32 (sigmoidf_fast)
+//   mrg_transe_bce_fwd     loss = mean over b, e of (y - 1) * max(log1p(-p), -100) - y * max(log p, -100)      (EPI_BCE's term, gemm.hpp)
+//   mrg_transe_bce_dlogit  dl   = gscale * (p - y) * (p (1 - p) / max(p (1 - p), 1e-12)) for the entities [c0, c1)   (EPI_BCE_GRAD's)
+//   mrg_transe_rank        rank = 1 + #{e != t, not filtered : dist_e < dist_t or (dist_e == dist_t and e < t)}
+// An L1 distance has no matrix form (scoring.hip): this is VALU work.  The dense transe_fwd_k reads two LDS words per absolute
+// difference and is bound by LDS; l1_sweep_k is register-tiled: 256 threads own a tile of 64 queries x 64 entities as a 16 x 16 grid of
+// 4 x 4 micro-tiles, operands staged through LDS in slices of 32 columns laid out [c][row], so that a thread fetches its four query
+// values and its four entity values of a column with two 16-byte LDS reads (the 16 lanes of a micro-tile row cover one 256-byte bank
+// row, the four micro-tile rows of a wave read broadcasts) for 16 subtract / |.|-add pairs.
+// Every distance is ONE float32 accumulator, acc += fabsf(o - e) over c ascending from 0, padding adding exact zeros: the chain of
+// transe_fwd_k, so fused and dense agree bit for bit on dist, and so does l1_target_k (one thread per query, same chain), whose target
+// distance therefore ties exactly with a duplicate of the target's entity row.  Ranks compare dist itself (gamma - dist and
+// sigmoid(gamma - dist) are monotone non-increasing in dist and only merge values).
+// No float atomics: the loss leaves one float64 partial per workgroup (lane sums in register order, butterfly per wave, the four waves
+// added in order), bce_finish_k adds the partials in a fixed order; counts are integer atomics, one per (row, workgroup).
+// Labels / filters of a tile: thread r < 64 walks the slice of tile row r's ascending list that falls into the tile's 64 entities
+// (binary search for its start, as gemm_bce_label_words does) and leaves a 64-bit mask in LDS.
+#include <hip/hip_runtime.h>
+#include "common.hpp"
+#include "sweep_limits.hpp"
+#include "sweep_prep.hpp"      // bce_prep_k, bce_finish_k, rank_prep_k, rank_finish_k
+
+namespace mrg {
+
+constexpr int L1_T = 64;            // tile: 64 queries x 64 entities
+constexpr int L1_C = 32;            // columns per LDS slice
+enum { L1_LOSS = 0, L1_DLOGIT = 1, L1_RANK = 2 };
+
+struct L1Args {
+  const float* obj;           // [rows][D]: the launch's query rows
+  const float* ent;           // the entity row of the launch's column 0
+  int64_t rows;
+  int ncols, D;
+  int e0;                     // entity id of the launch's column 0
+  float gamma;
+  const int32_t* qlist;       // L1_LOSS / L1_DLOGIT: [rows][2] begin and end of the query's object list in `list`
+  const int32_t* qinfo;       // L1_RANK: [rows][4] target, begin and end of the filter list in `list` / gone_at, `when`
+  const int32_t* list;        // entity ids, ascending inside a list
+  const int32_t* gone_at;     // L1_RANK: per member, filtered iff gone_at > when
+  float v_zero, v_one;
+  double* partial;            // L1_LOSS: [gridDim.y][gridDim.x]
+  const float* gscale;        // L1_DLOGIT: [1] on the device
+  float* dl;                  // L1_DLOGIT: element (row 0, column 0) of the launch
+  int64_t ld;
+  const float* tdist;         // L1_RANK: [rows] the target's distance (l1_target_k)
+  unsigned* counts;           // L1_RANK: [rows], zeroed
+};
+
+// tdist[i] = sum_c |obj[i, c] - ent[target_i, c]|, the sweep's chain
+__global__ void l1_target_k(const float* __restrict__ obj, const float* __restrict__ ent, const int32_t* __restrict__ qinfo, int64_t Q, int D,
+                            float* __restrict__ tdist) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= Q) return;
+  const float* __restrict__ o = obj + i * D;
+  const float* __restrict__ e = ent + (int64_t)qinfo[i * 4] * D;
+  float acc = 0.f;
+  for (int c = 0; c < D; ++c) acc += fabsf(o[c] - e[c]);
+  tdist[i] = acc;
+}
+
+template <int EPI, bool VEC4>
+__global__ __launch_bounds__(256) void l1_sweep_k(const L1Args a) {
+  __shared__ __attribute__((aligned(16))) float so[L1_C][L1_T];
+  __shared__ __attribute__((aligned(16))) float se[L1_C][L1_T];
+  __shared__ unsigned long long smask[L1_T];
+  __shared__ unsigned scnt[L1_T];
+  __shared__ double sred[4];
+  const int tid = threadIdx.x, tx = tid & 15, ty = tid >> 4;
+  const int col0 = blockIdx.x * L1_T;
+  const int64_t row0 = (int64_t)blockIdx.y * L1_T;
+  const int D = a.D;
+
+  if (tid < L1_T) {                                          // the tile row's labels (filtered members) as bits
+    unsigned long long m = 0ull;
+    const int64_t row = row0 + tid;
+    if (row < a.rows) {
+      int lo, hi, when = 0;
+      if constexpr (EPI == L1_RANK) {
+        const int4 qi = *reinterpret_cast<const int4*>(a.qinfo + row * 4);
+        lo = qi.y; hi = qi.z; when = qi.w;
+      } else {
+        const int2 q = *reinterpret_cast<const int2*>(a.qlist + row * 2);
+        lo = q.x; hi = q.y;
+      }
+      if (lo < hi) {
+        const int cbeg = a.e0 + col0, cend = cbeg + L1_T;
+        int b = lo, e = hi;
+        while (b < e) {                                      // first member >= cbeg
+          const int mid = b + ((e - b) >> 1);
+          if (a.list[mid] < cbeg) b = mid + 1; else e = mid;
+        }
+        for (; b < hi; ++b) {
+          const int id = a.list[b];
+          if (id >= cend) break;
+          if constexpr (EPI == L1_RANK) { if (a.gone_at[b] > when) m |= 1ull << (id - cbeg); }
+          else m |= 1ull << (id - cbeg);
+        }
+      }
+    }
+    smask[tid] = m;
+  }
+
+  // staging: thread (r = tid & 63, part = tid >> 6) carries row r of both operands; per slice 8 of its 32 columns
+  const int r = tid & 63, part = tid >> 6;
+  const bool qok = row0 + r < a.rows, eok = col0 + r < a.ncols;
+  const float* __restrict__ qp = a.obj + (qok ? (row0 + r) * D : 0);
+  const float* __restrict__ ep = a.ent + (eok ? (int64_t)(col0 + r) * D : 0);
+  float pq[8], pe[8];
+  auto fetch = [&](int c0) {
+    if constexpr (VEC4) {                                    // D % 4 == 0, 16-byte aligned rows: columns c .. c + 3
+#pragma unroll
+      for (int h = 0; h < 2; ++h) {
+        const int c = c0 + (part + 4 * h) * 4;
+        float4 vq = make_float4(0.f, 0.f, 0.f, 0.f), ve = vq;
+        if (c < D) {
+          if (qok) vq = *reinterpret_cast<const float4*>(qp + c);
+          if (eok) ve = *reinterpret_cast<const float4*>(ep + c);
+        }
+        pq[h * 4] = vq.x; pq[h * 4 + 1] = vq.y; pq[h * 4 + 2] = vq.z; pq[h * 4 + 3] = vq.w;
+        pe[h * 4] = ve.x; pe[h * 4 + 1] = ve.y; pe[h * 4 + 2] = ve.z; pe[h * 4 + 3] = ve.w;
+      }
+    } else {
+#pragma unroll
+      for (int k = 0; k < 8; ++k) {
+        const int c = c0 + part + 4 * k;
+        pq[k] = (qok && c < D) ? qp[c] : 0.f;
+        pe[k] = (eok && c < D) ? ep[c] : 0.f;
+      }
+    }
+  };
+  auto stash = [&]() {                                       // lanes of a wave write 64 consecutive floats of one [c] row: conflict free
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {
+      const int c = VEC4 ? (part + 4 * (k >> 2)) * 4 + (k & 3) : part + 4 * k;
+      so[c][r] = pq[k];
+      se[c][r] = pe[k];
+    }
+  };
+
+  float acc[4][4];
+#pragma unroll
+  for (int i = 0; i < 4; ++i)
+#pragma unroll
+    for (int j = 0; j < 4; ++j) acc[i][j] = 0.f;
+
+  fetch(0);
+  for (int c0 = 0; c0 < D; c0 += L1_C) {
+    stash();
+    __syncthreads();
+    if (c0 + L1_C < D) fetch(c0 + L1_C);                     // the next slice travels while this one is consumed
+    const int cn = D - c0 < L1_C ? D - c0 : L1_C;
+#pragma unroll 8
+    for (int c = 0; c < cn; ++c) {
+      const float4 o = *reinterpret_cast<const float4*>(&so[c][ty * 4]);
+      const float4 e = *reinterpret_cast<const float4*>(&se[c][tx * 4]);
+      const float ov[4] = {o.x, o.y, o.z, o.w}, ev[4] = {e.x, e.y, e.z, e.w};
+#pragma unroll
+      for (int i = 0; i < 4; ++i)
+#pragma unroll
+        for (int j = 0; j < 4; ++j) acc[i][j] += fabsf(ov[i] - ev[j]);
+    }
+    __syncthreads();
+  }
+
+  // ---- epilogues: element (i, j) of the thread is (row0 + ty * 4 + i, col0 + tx * 4 + j) ----
+  unsigned long long mrow[4];
+  bool rok[4], cok[4];
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    mrow[i] = smask[ty * 4 + i] >> (tx * 4);
+    rok[i] = row0 + ty * 4 + i < a.rows;
+    cok[i] = col0 + tx * 4 + i < a.ncols;
+  }
+
+  if constexpr (EPI == L1_LOSS) {
+    double s = 0.0;
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const float y = ((mrow[i] >> j) & 1ull) ? a.v_one : a.v_zero;
+        const float p = sigmoidf_fast(a.gamma - acc[i][j]);
+        const float lp = fmaxf(logf(p), -100.f), lq = fmaxf(log1pf(-p), -100.f);
+        const float t = (y - 1.f) * lq - y * lp;
+        s += (rok[i] && cok[j]) ? (double)t : 0.0;
+      }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) s += __shfl_xor(s, off);
+    if ((tid & 63) == 0) sred[tid >> 6] = s;
+    __syncthreads();
+    if (tid == 0) a.partial[(int64_t)blockIdx.y * gridDim.x + blockIdx.x] = ((sred[0] + sred[1]) + sred[2]) + sred[3];
+  } else if constexpr (EPI == L1_DLOGIT) {
+    const float gs = a.gscale[0];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      if (!rok[i]) continue;
+      float* __restrict__ out = a.dl + (row0 + ty * 4 + i) * a.ld + col0 + tx * 4;
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const float y = ((mrow[i] >> j) & 1ull) ? a.v_one : a.v_zero;
+        const float p = sigmoidf_fast(a.gamma - acc[i][j]);
+        const float pq1 = p * (1.f - p);
+        if (cok[j]) out[j] = gs * (p - y) * (pq1 / fmaxf(pq1, 1e-12f));
+      }
+    }
+  } else {
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      const int64_t row = row0 + ty * 4 + i;
+      const int64_t rc = rok[i] ? row : a.rows - 1;
+      const float td = a.tdist[rc];
+      const int tg = a.qinfo[rc * 4];
+      unsigned n = 0;
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const int id = a.e0 + col0 + tx * 4 + j;
+        const float d = acc[i][j];
+        const bool hit = rok[i] && cok[j] && id != tg && !((mrow[i] >> j) & 1ull) && (d < td || (d == td && id < tg));
+        n += hit ? 1u : 0u;
+      }
+#pragma unroll
+      for (int off = 8; off > 0; off >>= 1) n += __shfl_xor(n, off);       // the 16 lanes tx of micro-tile row ty are consecutive
+      if (tx == 0) scnt[ty * 4 + i] = n;
+    }
+    __syncthreads();
+    if (tid < L1_T && row0 + tid < a.rows && scnt[tid]) atomicAdd(a.counts + row0 + tid, scnt[tid]);
+  }
+}
+
+struct L1Plan { size_t qlist, partial, total; int64_t nrb, ncb; };
+inline size_t l1_up(size_t x) { return (x + 255) & ~(size_t)255; }
+// ncols: the columns a call sweeps (N for the forward, c1 - c0 for the logit gradient)
+inline L1Plan l1_bce_plan(int64_t B, int64_t ncols) {
+  L1Plan p{};
+  p.nrb = (B / RANK_CHUNK) * (RANK_CHUNK / L1_T) + (B % RANK_CHUNK + L1_T - 1) / L1_T;                 // workgroups along the rows ...
+  p.ncb = (ncols / BCE_COLS) * (BCE_COLS / L1_T) + (ncols % BCE_COLS + L1_T - 1) / L1_T;               // ... and the columns
+  size_t off = 256;                                          // slack: the workspace pointer is rounded up to 256 bytes
+  p.qlist = off; off += l1_up((size_t)B * 2 * sizeof(int32_t));
+  p.partial = off; off += l1_up((size_t)p.nrb * p.ncb * sizeof(double));
+  p.total = off;
+  return p;
+}
+
+struct L1RankPlan { size_t qinfo, tdist, counts, total; };
+inline L1RankPlan l1_rank_plan(int64_t Q) {
+  L1RankPlan p{};
+  size_t off = 256;
+  p.qinfo = off; off += l1_up((size_t)Q * 4 * sizeof(int32_t));
+  p.tdist = off; off += l1_up((size_t)Q * sizeof(float));
+  p.counts = off; off += l1_up((size_t)Q * sizeof(unsigned));
+  p.total = off;
+  return p;
+}
+
+// The sweep over the columns [c0, c1) of all rows: column blocks of BCE_COLS outermost, row chunks of RANK_CHUNK inside.  `a` carries what
+// does not change from launch to launch; L1_LOSS appends its launches' partials at a.partial.
+template <int EPI>
+inline int l1_sweep(L1Args a, const float* obj, const float* ent, int64_t rows_all, int64_t c0, int64_t c1, hipStream_t st) {
+  const bool vec = a.D % 4 == 0 && aligned16(obj) && aligned16(ent);
+  const int32_t* qlist = a.qlist;
+  const int32_t* qinfo = a.qinfo;
+  const float* tdist = a.tdist;
+  unsigned* counts = a.counts;
+  float* dl = a.dl;
+  for (int64_t c = c0; c < c1; c += BCE_COLS) {
+    const int64_t nc = c1 - c < BCE_COLS ? c1 - c : BCE_COLS;
+    for (int64_t q0 = 0; q0 < rows_all; q0 += RANK_CHUNK) {
+      const int64_t rows = rows_all - q0 < RANK_CHUNK ? rows_all - q0 : RANK_CHUNK;
+      a.obj = obj + q0 * a.D; a.ent = ent + c * a.D; a.rows = rows; a.ncols = (int)nc; a.e0 = (int)c;
+      if (EPI == L1_RANK) { a.qinfo = qinfo + q0 * 4; a.tdist = tdist + q0; a.counts = counts + q0; }
+      else a.qlist = qlist + q0 * 2;
+      if (EPI == L1_DLOGIT) a.dl = dl + q0 * a.ld + (c - c0);
+      const dim3 grid((unsigned)((nc + L1_T - 1) / L1_T), (unsigned)((rows + L1_T - 1) / L1_T));
+      if (vec) hipLaunchKernelGGL((l1_sweep_k<EPI, true>), grid, dim3(256), 0, st, a);
+      else hipLaunchKernelGGL((l1_sweep_k<EPI, false>), grid, dim3(256), 0, st, a);
+      MRG_LAUNCH_CHECK();
+      if (EPI == L1_LOSS) a.partial += (int64_t)grid.x * grid.y;
+    }
+  }
+  return MRG_OK;
+}
+
+}  // namespace mrg
+
+using namespace mrg;
+
+static bool l1_shape_ok(int64_t B, int64_t N, int D) { return B >= 0 && N >= 1 && N <= RANK_MAX_N && D >= 1 && D <= 1024; }
+
+extern "C" int64_t mrg_transe_bce_workspace_bytes(int64_t B, int64_t ncols, int D) {
+  if (!l1_shape_ok(B, ncols, D)) return MRG_E_SHAPE;
+  return (int64_t)l1_bce_plan(B, ncols).total;
+}
+
+extern "C" int mrg_transe_bce_fwd(const float* obj, const float* ent, const int64_t* qkey, const int64_t* keys, const int32_t* rowptr,
+                                  const int32_t* objs, int64_t U, float gamma, float v_zero, float v_one, int64_t B, int64_t N, int D, float* loss,
+                                  void* ws, int64_t ws_bytes, void* stream) {
+  if (U < 0 || !l1_shape_ok(B, N, D)) return MRG_E_SHAPE;
+  if (B == 0) return MRG_OK;
+  if (!obj || !ent || !loss) return MRG_E_NULLPTR;
+  if (U > 0 && (!qkey || !keys || !rowptr || !objs)) return MRG_E_NULLPTR;
+  const L1Plan p = l1_bce_plan(B, N);
+  if (!ws || ws_bytes < (int64_t)p.total) return MRG_E_WORKSPACE;
+  hipStream_t st = (hipStream_t)stream;
+  char* w = (char*)(((uintptr_t)ws + 255) & ~(uintptr_t)255) - 256;        // the plan's offsets start at 256
+  int32_t* qlist = (int32_t*)(w + p.qlist);
+  double* partial = (double*)(w + p.partial);
+  hipLaunchKernelGGL(bce_prep_k, dim3((unsigned)((B + 255) / 256)), dim3(256), 0, st, qkey, keys, rowptr, U, B, qlist);
+  MRG_LAUNCH_CHECK();
+  L1Args a{};
+  a.D = D; a.gamma = gamma; a.qlist = qlist; a.list = objs; a.v_zero = v_zero; a.v_one = v_one; a.partial = partial;
+  const int rc = l1_sweep<L1_LOSS>(a, obj, ent, B, 0, N, st);
+  if (rc != MRG_OK) return rc;
+  hipLaunchKernelGGL(bce_finish_k, dim3(1), dim3(256), 0, st, partial, p.nrb * p.ncb, 1.0 / ((double)B * (double)N), loss);
+  MRG_LAUNCH_CHECK();
+  return MRG_OK;
+}
+
+extern "C" int mrg_transe_bce_dlogit(const float* obj, const float* ent, const int64_t* qkey, const int64_t* keys, const int32_t* rowptr,
+                                     const int32_t* objs, int64_t U, float gamma, float v_zero, float v_one, int64_t B, int64_t N, int D,
+                                     int64_t c0, int64_t c1, const float* gscale, float* dl, void* ws, int64_t ws_bytes, void* stream) {
+  if (U < 0 || !l1_shape_ok(B, N, D) || c0 < 0 || c1 <= c0 || c1 > N) return MRG_E_SHAPE;
+  if (B == 0) return MRG_OK;
+  if (!obj || !ent || !gscale || !dl) return MRG_E_NULLPTR;
+  if (U > 0 && (!qkey || !keys || !rowptr || !objs)) return MRG_E_NULLPTR;
+  const L1Plan p = l1_bce_plan(B, c1 - c0);
+  if (!ws || ws_bytes < (int64_t)p.total) return MRG_E_WORKSPACE;
+  hipStream_t st = (hipStream_t)stream;
+  char* w = (char*)(((uintptr_t)ws + 255) & ~(uintptr_t)255) - 256;
+  int32_t* qlist = (int32_t*)(w + p.qlist);
+  hipLaunchKernelGGL(bce_prep_k, dim3((unsigned)((B + 255) / 256)), dim3(256), 0, st, qkey, keys, rowptr, U, B, qlist);
+  MRG_LAUNCH_CHECK();
+  L1Args a{};
+  a.D = D; a.gamma = gamma; a.qlist = qlist; a.list = objs; a.v_zero = v_zero; a.v_one = v_one; a.gscale = gscale; a.dl = dl; a.ld = c1 - c0;
+  return l1_sweep<L1_DLOGIT>(a, obj, ent, B, c0, c1, st);
+}
+
+extern "C" int64_t mrg_transe_rank_workspace_bytes(int64_t Q, int64_t N, int D) {
+  if (!l1_shape_ok(Q, N, D)) return MRG_E_SHAPE;
+  return (int64_t)l1_rank_plan(Q).total;
+}
+
+extern "C" int mrg_transe_rank(const float* obj, const float* ent, const int32_t* t_idx, const int64_t* qkey, const int32_t* when,
+                               const int64_t* keys, const int32_t* rowptr, const int32_t* members, const int32_t* gone_at, int64_t U, int64_t Q,
+                               int64_t N, int D, int64_t* ranks, void* ws, int64_t ws_bytes, void* stream) {
+  if (U < 0 || !l1_shape_ok(Q, N, D)) return MRG_E_SHAPE;
+  if (Q == 0) return MRG_OK;
+  if (!obj || !ent || !t_idx || !ranks) return MRG_E_NULLPTR;
+  if (U > 0 && (!qkey || !when || !keys || !rowptr || !members || !gone_at)) return MRG_E_NULLPTR;
+  const L1RankPlan p = l1_rank_plan(Q);
+  if (!ws || ws_bytes < (int64_t)p.total) return MRG_E_WORKSPACE;
+  hipStream_t st = (hipStream_t)stream;
+  char* w = (char*)(((uintptr_t)ws + 255) & ~(uintptr_t)255) - 256;
+  int32_t* qinfo = (int32_t*)(w + p.qinfo);
+  float* tdist = (float*)(w + p.tdist);
+  unsigned* counts = (unsigned*)(w + p.counts);
+  hipLaunchKernelGGL(rank_prep_k, dim3((unsigned)((Q + 255) / 256)), dim3(256), 0, st, t_idx, qkey, when, keys, rowptr, U, Q, qinfo, counts);
+  MRG_LAUNCH_CHECK();
+  hipLaunchKernelGGL(l1_target_k, dim3((unsigned)((Q + 255) / 256)), dim3(256), 0, st, obj, ent, qinfo, Q, D, tdist);
+  MRG_LAUNCH_CHECK();
+  L1Args a{};
+  a.D = D; a.qinfo = qinfo; a.list = members; a.gone_at = gone_at; a.tdist = tdist; a.counts = counts;
+  const int rc = l1_sweep<L1_RANK>(a, obj, ent, Q, 0, N, st);
+  if (rc != MRG_OK) return rc;
+  hipLaunchKernelGGL(rank_finish_k, dim3((unsigned)((Q + 255) / 256)), dim3(256), 0, st, counts, ranks, Q);
+  MRG_LAUNCH_CHECK();
+  return MRG_OK;
+}

@@ -9,6 +9,9 @@ reference's functions of the same role so a driver can swap them in.
 The search driver's evaluation (reference utils/utils_rgcn.py:212-380, search/mr_lp_search.py:258-278) is the second half of the
 module: ``calc_mrr`` / ``calc_raw_mrr`` / ``calc_filtered_mrr`` / ``infer_graph`` over ``KnownTriples`` and ``distmult_ranks``
 (``mrg_distmult_rank``: the DistMult product as a row GEMM whose epilogue counts; no [Q, N] tensor).
+
+``predict_fused`` (DistMult) and ``predict_1n`` (every scorer with ``query`` / ``score_kind``: DistMult, ConvE, TransE) are ``predict``
+without a [B, N] tensor, over ``query_ranks`` (``mrg_rows_rank`` / ``mrg_transe_rank``).
 """
 import torch
 import torch.nn.functional as F
@@ -76,12 +79,28 @@ def predict_fused(val_test_loader, g, model, label_index, device):
     Ranks are taken on the logits, as calc_mrr takes them, where predict ranks float32 sigmoid(x): sigmoid is monotone, ties follow
     the same rule (equal score at a lower entity id), and where float32 sigmoid ties two different logits the value returned here
     lies inside predict's tie interval."""
-    from . import functional as K
     from .operations_lp import sf_DisMult_op
     if torch.device(device).type != "cuda" or not next(model.parameters()).is_cuda:
         raise MrgnasError("predict_fused runs on a HIP device (no CPU fallback); got " + str(device))
     if not isinstance(model.score_func, sf_DisMult_op):
         raise MrgnasError(f"predict_fused covers the DistMult scorer only; this network scores with {type(model.score_func).__name__}")
+    return predict_1n(val_test_loader, g, model, label_index, device)
+
+
+def predict_1n(val_test_loader, g, model, label_index, device):
+    """predict_fused for every scorer that follows the scorer protocol (operations_lp: ``query`` and ``score_kind``): DistMult, ConvE
+    ("dot") and TransE ("l1").  Per batch one model.embed(g) and one score_func.query(ent[s], rel_emb[r]); the ranks come from
+    query_ranks with label_index as the filter and when = -1, the batch's mean BCE from mrg_distmult_bce_fwd / mrg_transe_bce_fwd on the
+    unsmoothed labels.  "dot" ranks are taken on the logits, "l1" ranks on the distances: where predict's float32 sigmoid ties
+    different logits -- with gamma = 40 and realistic L1 distances it saturates to exactly 0 and ties whole rows -- the value
+    returned here lies inside predict's tie interval."""
+    from . import functional as K
+    if torch.device(device).type != "cuda" or not next(model.parameters()).is_cuda:
+        raise MrgnasError("predict_1n runs on a HIP device (no CPU fallback); got " + str(device))
+    sf = model.score_func
+    kind = getattr(sf, "score_kind", None)
+    if not hasattr(sf, "query") or kind not in ("dot", "l1"):
+        raise MrgnasError(f"predict_1n needs a scorer with query() and a score_kind of 'dot' or 'l1'; this network scores with {type(sf).__name__}")
     side = _LabelSide(label_index)
     v_zero, v_one = label_index.label_values(0.0)
     ks = torch.tensor(_HITS, dtype=torch.float64, device=device)
@@ -92,10 +111,15 @@ def predict_fused(val_test_loader, g, model, label_index, device):
             triplets = (batch[0] if isinstance(batch, (tuple, list)) else batch).to(device)
             s, r, o = (triplets[:, i].int().contiguous() for i in range(3))
             ent, rel_emb = model.embed(g)
+            ent = f32c(ent)
+            q = f32c(sf.query(K.gather_rows(ent, s), K.gather_rows(f32c(rel_emb), r)))
             when = torch.full((s.numel(),), -1, dtype=torch.int32, device=device)
-            ranks = distmult_ranks(ent, rel_emb, s, r, o, side, when).double()
             qkey = (s.long() * side.num_rels + r.long()).contiguous()
-            loss = K.distmult_bce_mean(K.gather_rows(f32c(ent), s, f32c(rel_emb), r, "mult"), f32c(ent), label_index, qkey, v_zero, v_one)
+            ranks = query_ranks(q, ent, o, side, when, qkey, kind).double()
+            if kind == "l1":
+                loss = K.transe_bce_mean(q, ent, sf.gamma, label_index, qkey, v_zero, v_one)
+            else:
+                loss = K.distmult_bce_mean(q, ent, label_index, qkey, v_zero, v_one)
             batch_acc = torch.cat((torch.stack((ranks.new_tensor(float(ranks.numel())), ranks.sum(), ranks.reciprocal().sum(), loss.double())),
                                    (ranks.unsqueeze(0) <= ks.unsqueeze(1)).sum(dim=1).double()))
             acc += batch_acc
@@ -212,6 +236,42 @@ def distmult_ranks(embedding, w, a, r, target, known_side=None, when=None):
     call("mrg_distmult_rank", (ptr(embedding), ptr(w), ptr(a), ptr(r), ptr(target), ptr(qkey), ptr(when), ptr(keys), ptr(rowptr),
                                ptr(members), ptr(gone_at), U, Q, N, D, ptr(ranks), ptr(ws), int(nbytes), stream_of(embedding)),
          nbytes=4 * (Q + N) * D, flops=2 * Q * N * D)
+    return ranks
+
+
+def query_ranks(q, ent, target, known_side=None, when=None, qkey=None, kind="dot"):
+    """ranks [Q] int64 (1-based) of `target` among all entities for query rows q [Q, D] the caller holds (a scorer's ``query``).
+    kind "dot": the score is q . ent[e] (mrg_rows_rank: distmult_ranks from the point where the rows exist); kind "l1": the score is
+    -||q - ent[e]||_1, compared on the distance itself (mrg_transe_rank).  known_side / when as in distmult_ranks, with qkey [Q] int64
+    the queries' keys into known_side (fixed entity * num_rels + relation); None for raw ranks."""
+    if kind not in ("dot", "l1"):
+        raise ValueError("query_ranks: kind is 'dot' or 'l1'")
+    if not (q.is_cuda and ent.is_cuda and target.is_cuda):
+        raise MrgnasError("query_ranks runs on a HIP device (no CPU fallback)")
+    q, ent, target = f32c(q), f32c(ent), target.int().contiguous()
+    require_hip(q, ent, target)
+    (Q, D), N = q.shape, ent.shape[0]
+    if ent.shape[1] != D or target.numel() != Q:
+        raise ValueError("query_ranks: q [Q, D], ent [N, D] and target [Q] expected")
+    keys = rowptr = members = gone_at = None
+    U = 0
+    if known_side is not None and known_side.keys.numel() > 0:
+        if when is None or when.numel() != Q or qkey is None or qkey.numel() != Q:
+            raise ValueError("query_ranks: a filtered call needs when [Q] and qkey [Q]")
+        k = known_side
+        qkey, when = qkey.long().contiguous(), when.int().contiguous()
+        require_hip(k.keys, k.rowptr, k.members, k.gone_at, qkey, when)
+        keys, rowptr, members, gone_at, U = k.keys, k.rowptr, k.members, k.gone_at, k.keys.numel()
+    else:
+        qkey = when = None
+    ranks = torch.empty(Q, dtype=torch.int64, device=q.device)
+    name = "mrg_rows_rank" if kind == "dot" else "mrg_transe_rank"
+    nbytes = getattr(load(), "mrg_distmult_rank_workspace_bytes" if kind == "dot" else "mrg_transe_rank_workspace_bytes")(Q, N, D)
+    if nbytes < 0:
+        check(int(nbytes), name)
+    ws = torch.empty(max(int(nbytes), 1), dtype=torch.uint8, device=q.device)
+    call(name, (ptr(q), ptr(ent), ptr(target), ptr(qkey), ptr(when), ptr(keys), ptr(rowptr), ptr(members), ptr(gone_at), U, Q, N, D,
+                ptr(ranks), ptr(ws), int(nbytes), stream_of(q)), nbytes=4 * (Q + N) * D, flops=2 * Q * N * D)
     return ranks
 
 

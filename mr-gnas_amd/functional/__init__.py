@@ -18,7 +18,8 @@ This package re-exports every name of its modules, so callers keep writing ``fro
   dense       Dense (per-feature) filters f_dense_comp / f_comp / f_dense_last on the MFMA row GEMM (csrc/dense.hip, linear.hip, wgrad.hip).
   mixed       X: the MixedOp epilogue  out = sum_k w_k * ReLU(BatchNorm_k(y_k))  (csrc/mixedop.hip).
   cell_zero   Cell zero: the MixedOp over the compose candidates, recomputed from the entity / relation tables (csrc/cell_zero.hip).
-  scoring     The step after the path: DistMult triple scoring and the [B, N] score functions (csrc/scoring.hip).
+  scoring     The step after the path: DistMult triple scoring, the [B, N] score functions and the 1-N losses without [B, N] tensors
+              (csrc/scoring.hip, bce.hip, transe_1n.hip).
   ccorr       Standalone circular correlation ccorr(a, b): per-row kernel, or a shared row's circulant on the row GEMM (csrc/ccorr.hip).
   conve       ConvE feature path: BN0 -> conv -> BN1 -> ReLU -> fc of the (subject, relation) image, and the ConvE scorer (csrc/conve.hip).
   nc          Node-classification aggregators on a block: a_std (csrc/segstd.hip) and a_sum / a_mean / a_max without self rows.
@@ -65,13 +66,14 @@ from .cell_zero import (  # noqa: F401
 )
 from .scoring import (  # noqa: F401
     ScorePlan, _DistMult, distmult_score, distmult_scores_all, _TransE, transe_scores_all,
-    _DistMultBCE, distmult_bce_all, distmult_bce_mean, distmult_bce_dlogit, bce_default_col_chunk,
+    _DistMultBCE, distmult_bce_all, distmult_bce_mean, distmult_bce_dlogit, bce_default_col_chunk, dot_bce_all,
+    _TransEBCE, transe_bce_all, transe_bce_mean, transe_bce_dlogit,
 )
 from .ccorr import (  # noqa: F401
     _CCorrRows, _Circulant, ccorr,
 )
 from .conve import (  # noqa: F401
-    _ConvEFeatures, conve_features, conve_scores, drop_masks, hip_path_ok,
+    _ConvEFeatures, conve_features, conve_query, conve_scores, drop_masks, hip_path_ok,
 )
 from .nc import (  # noqa: F401
     _SegStd, aggregate_std, inv_in_degree, aggregate_nc, linear_relu_aggregate_nc,

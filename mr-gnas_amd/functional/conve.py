@@ -153,12 +153,11 @@ def hip_path_ok(modules, bns, tensors):
     return all(b.track_running_stats and b.affine and isinstance(b.momentum, float) and b.training == bns[0].training for b in bns)
 
 
-def conve_scores(sub, rel, layout, img_hw, bn0, conv, bn1, feature_drop, fc, hidden_drop, bn2, one, ent, bias):
-    """sigmoid(relu(bn2(conve_features(...))) @ ent^T + bias): the whole ConvE scorer, BN2 + ReLU on the one-branch MixedOp epilogue
-    and the [B, N] product on the row GEMM (what distmult_scores_all runs)."""
+def conve_query(sub, rel, layout, img_hw, bn0, conv, bn1, feature_drop, fc, hidden_drop, bn2, one):
+    """relu(bn2(conve_features(...))) [B, D]: the row every entity is scored against -- the ConvE scorer up to its [B, N] product, BN2 +
+    ReLU on the one-branch MixedOp epilogue.  Draws the dropout masks and updates the BatchNorm statistics as conve_scores does."""
     from .mixed import mixed_epilogue
-    from .row_linear import linear
-    sub, rel, ent = LZ.real(sub), LZ.real(rel), LZ.real(ent)
+    sub, rel = LZ.real(sub), LZ.real(rel)
     B, D = sub.shape
     if bn2.training and B == 1:                       # what F.batch_norm raises for BatchNorm1d on one row
         raise ValueError(f"Expected more than 1 value per channel when training, got input size {torch.Size([B, D])}")
@@ -166,5 +165,12 @@ def conve_scores(sub, rel, layout, img_hw, bn0, conv, bn1, feature_drop, fc, hid
     F, ks = conv.weight.shape[0], conv.weight.shape[-1]
     keep1, keep2 = drop_masks(feature_drop, hidden_drop, B, F, Hi - ks + 1, Wi - ks + 1, D, sub.device)
     h = conve_features(sub, rel, layout, img_hw, bn0, conv, bn1, keep1, fc, keep2)
-    x = mixed_epilogue([h], [bn2], one if one.device == h.device else one.to(h.device))
-    return linear(x, ent, bias, "sigmoid")
+    return mixed_epilogue([h], [bn2], one if one.device == h.device else one.to(h.device))
+
+
+def conve_scores(sub, rel, layout, img_hw, bn0, conv, bn1, feature_drop, fc, hidden_drop, bn2, one, ent, bias):
+    """sigmoid(conve_query(...) @ ent^T + bias): the whole ConvE scorer, the [B, N] product on the row GEMM (what distmult_scores_all
+    runs)."""
+    from .row_linear import linear
+    x = conve_query(sub, rel, layout, img_hw, bn0, conv, bn1, feature_drop, fc, hidden_drop, bn2, one)
+    return linear(x, LZ.real(ent), bias, "sigmoid")

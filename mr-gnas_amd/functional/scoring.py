@@ -1,5 +1,5 @@
-"""The step after the path: DistMult triple scoring, the [B, N] score functions (csrc/scoring.hip) and the 1-N DistMult loss that needs
-no [B, N] tensor (csrc/bce.hip).
+"""The step after the path: DistMult triple scoring, the [B, N] score functions (csrc/scoring.hip) and the 1-N losses that need no
+[B, N] tensor: the "dot" scorers' (DistMult, ConvE: csrc/bce.hip) and TransE's (csrc/transe_1n.hip).
 
 Part of ``mr_gnas_amd.functional`` (autograd Functions over the C ABI, include/mrgnas.h): every Function enqueues HIP kernels of
 libmrgnas_hip.so on torch's current stream through ctypes; every call site states the algorithmic bytes / flops of the launch."""
@@ -172,6 +172,34 @@ class _DistMultBCE(torch.autograd.Function):
         return g_q, g_ent, None, None, None, None, None
 
 
+def _bce_all_args(what, tensors, B, N, label_index, subj, rel, label_smooth, col_chunk):
+    """The checks and the derived arguments the 1-N losses share: (qkey, v_zero, v_one, col_chunk)."""
+    for t in tensors:
+        if not t.is_cuda:
+            raise MrgnasError(f"{what} runs on a HIP device (no CPU fallback); got a tensor on " + str(t.device))
+    if B == 0 or N == 0 or N != label_index.num_ent or subj.numel() != B or rel.numel() != B:
+        raise ValueError(f"{what}: all_ent [num_ent, D], query rows [B, D], subj / rel [B] with B > 0 expected")
+    if col_chunk is None:
+        col_chunk = bce_default_col_chunk(B)
+    col_chunk = int(col_chunk)
+    if col_chunk < 1:
+        raise ValueError(f"{what}: col_chunk must be positive")
+    v_zero, v_one = label_index.label_values(label_smooth)
+    qkey = (subj.long() * (2 * label_index.num_rel) + rel.long()).contiguous()
+    return qkey, v_zero, v_one, col_chunk
+
+
+def dot_bce_all(all_ent, q, label_index, subj, rel, label_smooth=0.0, col_chunk=None, _what="dot_bce_all"):
+    """distmult_bce_all from the point where the query rows exist: the mean over [B, N] of BCELoss(sigmoid(q all_ent^T),
+    label_index.labels(subj, rel, label_smooth)) for rows q [B, D] the caller formed -- DistMult's sub * rel, ConvE's hidden vector
+    after BN2 + ReLU (the scorers' ``query``).  Same kernels, same memory, no host synchronisation."""
+    if q.dim() != 2 or all_ent.dim() != 2 or q.shape[1] != all_ent.shape[1]:
+        raise ValueError(f"{_what}: all_ent [num_ent, D] and query rows [B, D] expected")
+    B, N = int(q.shape[0]), int(all_ent.shape[0])
+    qkey, v_zero, v_one, col_chunk = _bce_all_args(_what, (all_ent, q, subj, rel), B, N, label_index, subj, rel, label_smooth, col_chunk)
+    return _DistMultBCE.apply(q, all_ent, label_index, qkey, v_zero, v_one, col_chunk)
+
+
 def distmult_bce_all(all_ent, sub_emb, rel_emb, label_index, subj, rel, label_smooth=0.0, col_chunk=None):
     """The fixed-genotype driver's training loss (reference train/mr_lp_train.py Network._loss with sf_DisMult_op): the mean over [B, N]
     of BCELoss(sigmoid((sub_emb * rel_emb) all_ent^T), label_index.labels(subj, rel, label_smooth)) as a float32 scalar, with no [B, N]
@@ -180,17 +208,9 @@ def distmult_bce_all(all_ent, sub_emb, rel_emb, label_index, subj, rel, label_sm
     for t in (all_ent, sub_emb, rel_emb, subj, rel):
         if not t.is_cuda:
             raise MrgnasError("distmult_bce_all runs on a HIP device (no CPU fallback); got a tensor on " + str(t.device))
-    B, N = int(sub_emb.shape[0]), int(all_ent.shape[0])
-    if B == 0 or N == 0 or N != label_index.num_ent or subj.numel() != B or rel.numel() != B:
+    if int(sub_emb.shape[0]) == 0:
         raise ValueError("distmult_bce_all: all_ent [num_ent, D], sub_emb / rel_emb [B, D], subj / rel [B] with B > 0 expected")
-    if col_chunk is None:
-        col_chunk = bce_default_col_chunk(B)
-    col_chunk = int(col_chunk)
-    if col_chunk < 1:
-        raise ValueError("distmult_bce_all: col_chunk must be positive")
-    v_zero, v_one = label_index.label_values(label_smooth)
-    qkey = (subj.long() * (2 * label_index.num_rel) + rel.long()).contiguous()
-    return _DistMultBCE.apply(compose("mult", sub_emb, rel_emb), all_ent, label_index, qkey, v_zero, v_one, col_chunk)
+    return dot_bce_all(all_ent, compose("mult", sub_emb, rel_emb), label_index, subj, rel, label_smooth, col_chunk, _what="distmult_bce_all")
 
 
 class _TransE(torch.autograd.Function):
@@ -221,3 +241,86 @@ class _TransE(torch.autograd.Function):
 def transe_scores_all(all_ent, sub_emb, rel_emb, gamma):
     """sf_TransE_op (reference models/operations_lp.py:101-112): sigmoid(gamma - ||sub + rel - ent||_1) for all entities."""
     return _TransE.apply(all_ent, sub_emb, rel_emb, gamma)
+
+
+def _l1_ws(name, B, cols, D, like):
+    nbytes = _ws_bytes(name, B, cols, D)
+    if nbytes < 0:
+        check(int(nbytes), name)
+    return _ws(nbytes, like), int(nbytes)
+
+
+def transe_bce_mean(obj, ent, gamma, label_index, qkey, v_zero, v_one):
+    """mrg_transe_bce_fwd, no autograd: mean over [B, N] of BCE(sigmoid(gamma - ||obj - ent||_1), labels) as a float32 device scalar."""
+    li = label_index
+    (B, D), N = obj.shape, ent.shape[0]
+    loss = torch.empty((), dtype=torch.float32, device=obj.device)
+    ws, nbytes = _l1_ws("mrg_transe_bce_workspace_bytes", B, N, D, obj)
+    call("mrg_transe_bce_fwd", (ptr(obj), ptr(ent), ptr(qkey), ptr(li.keys), ptr(li.rowptr), ptr(li.objs), int(li.keys.numel()),
+                                float(gamma), v_zero, v_one, B, N, D, ptr(loss), ptr(ws), nbytes, stream_of(obj)),
+         nbytes=4 * (B + N) * D, flops=2 * B * N * D)
+    return loss
+
+
+def transe_bce_dlogit(obj, ent, gamma, label_index, qkey, v_zero, v_one, c0, c1, gscale, out=None):
+    """mrg_transe_bce_dlogit, no autograd: the loss gradient with respect to x = gamma - dist of the entities [c0, c1) as [B, c1 - c0],
+    written into the first B * (c1 - c0) floats of `out` when given.  gscale: float32 [1] on the device (upstream gradient / (B N))."""
+    li = label_index
+    (B, D), N, nc = obj.shape, ent.shape[0], c1 - c0
+    if out is None:
+        out = torch.empty(B * nc, dtype=torch.float32, device=obj.device)
+    ws, nbytes = _l1_ws("mrg_transe_bce_workspace_bytes", B, nc, D, obj)
+    call("mrg_transe_bce_dlogit", (ptr(obj), ptr(ent), ptr(qkey), ptr(li.keys), ptr(li.rowptr), ptr(li.objs), int(li.keys.numel()),
+                                   float(gamma), v_zero, v_one, B, N, D, c0, c1, ptr(gscale), ptr(out), ptr(ws), nbytes, stream_of(obj)),
+         nbytes=4 * (B + nc) * D + 4 * B * nc, flops=2 * B * nc * D)
+    return out[:B * nc].view(B, nc)
+
+
+class _TransEBCE(torch.autograd.Function):
+    """loss(obj, ent) of transe_bce_all, shaped like _DistMultBCE.  Forward: one sweep that stores nothing per element.  Backward: per
+    column chunk the slice dl [B, chunk] of the gradient with respect to gamma - dist (mrg_transe_bce_dlogit, the tile recomputed) and
+    mrg_transe_dist_bwd on it: g_ent[c0:c1] written, g_obj accumulated in chunk order.  One dl slice, no transpose."""
+
+    @staticmethod
+    def forward(ctx, obj, ent, gamma, label_index, qkey, v_zero, v_one, col_chunk):
+        obj, ent = f32c(obj), f32c(ent)
+        li = label_index
+        require_hip(obj, ent, qkey, li.keys, li.rowptr, li.objs)
+        ctx.li, ctx.v, ctx.col_chunk, ctx.gamma = li, (v_zero, v_one), col_chunk, float(gamma)
+        ctx.save_for_backward(obj, ent, qkey)
+        return transe_bce_mean(obj, ent, gamma, li, qkey, v_zero, v_one)
+
+    @staticmethod
+    def backward(ctx, g):
+        obj, ent, qkey = ctx.saved_tensors
+        li, (v_zero, v_one), step = ctx.li, ctx.v, ctx.col_chunk
+        (B, D), N, st = obj.shape, ent.shape[0], stream_of(obj)
+        step = min(step, N)
+        need_obj, need_ent = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        gscale = (g.detach().float().reshape(1) / float(B * N)).contiguous()          # stays on the device: no host synchronisation
+        dl = torch.empty(B * step, dtype=torch.float32, device=obj.device)             # ONE slice, reused by every chunk
+        g_obj = torch.empty_like(obj) if need_obj else None
+        g_ent = torch.empty_like(ent) if need_ent else None
+        esz = ent.element_size()
+        for c0 in range(0, N, step):
+            c1 = min(N, c0 + step)
+            nc = c1 - c0
+            transe_bce_dlogit(obj, ent, ctx.gamma, li, qkey, v_zero, v_one, c0, c1, gscale, out=dl)
+            call("mrg_transe_dist_bwd", (ctypes.c_void_p(ent.data_ptr() + c0 * D * esz), ptr(obj), ptr(dl), nc,
+                                         ctypes.c_void_p(g_ent.data_ptr() + c0 * D * esz) if need_ent else None, ptr(g_obj),
+                                         1 if c0 > 0 else 0, B, nc, D, st),
+                 nbytes=4 * (B * nc + (B + nc) * D), flops=(int(need_obj) + int(need_ent)) * 2 * B * nc * D)
+        return g_obj, g_ent, None, None, None, None, None, None
+
+
+def transe_bce_all(all_ent, sub_emb, rel_emb, gamma, label_index, subj, rel, label_smooth=0.0, col_chunk=None):
+    """The fixed-genotype driver's training loss with sf_TransE_op: the mean over [B, N] of BCELoss(sigmoid(gamma - ||sub_emb + rel_emb -
+    all_ent||_1), label_index.labels(subj, rel, label_smooth)) as a float32 scalar with no [B, N] tensor (csrc/transe_1n.hip).  The
+    backward holds one [B, col_chunk] slice (default: bce_default_col_chunk(B)) and no transpose; the gradient of obj = sub_emb + rel_emb
+    goes to both.  No host synchronisation."""
+    if sub_emb.dim() != 2 or sub_emb.shape != rel_emb.shape or all_ent.dim() != 2 or sub_emb.shape[1] != all_ent.shape[1]:
+        raise ValueError("transe_bce_all: all_ent [num_ent, D] and sub_emb / rel_emb [B, D] expected")
+    B, N = int(sub_emb.shape[0]), int(all_ent.shape[0])
+    qkey, v_zero, v_one, col_chunk = _bce_all_args("transe_bce_all", (all_ent, sub_emb, rel_emb, subj, rel), B, N, label_index, subj, rel,
+                                                   label_smooth, col_chunk)
+    return _TransEBCE.apply(compose("add", sub_emb, rel_emb), all_ent, gamma, label_index, qkey, v_zero, v_one, col_chunk)

@@ -279,18 +279,31 @@ class a_sum_op(_Operator):
 
 
 # ---- score functions (the step after the path): HIP kernels as well (compose + MFMA GEMM with a sigmoid epilogue; L1 kernel) ----
+# The scorer protocol of the paths that keep no [B, N] tensor (FixedNetwork.loss_1n, evaluation.predict_1n): ``query(sub_emb, rel_emb)``
+# returns the [B, D] row every entity is scored against, and ``score_kind`` says how: "dot" (logit = query . entity: DistMult, ConvE)
+# or "l1" (logit = gamma - ||query - entity||_1: TransE).  forward is sigmoid of that logit over all entities.
 class sf_TransE_op(nn.Module):
+    score_kind = "l1"
+
     def __init__(self, args):
         super().__init__()
         self.gamma = args.get('gamma', 40)
+
+    def query(self, sub_emb, rel_emb):
+        return K.compose("add", sub_emb, rel_emb) if sub_emb.is_cuda else sub_emb + rel_emb
 
     def forward(self, all_ent, sub_emb, rel_emb):
         return K.transe_scores_all(all_ent, sub_emb, rel_emb, self.gamma)
 
 
 class sf_DisMult_op(nn.Module):
+    score_kind = "dot"
+
     def __init__(self, args):
         super().__init__()
+
+    def query(self, sub_emb, rel_emb):
+        return K.compose("mult", sub_emb, rel_emb) if sub_emb.is_cuda else sub_emb * rel_emb
 
     def forward(self, all_ent, sub_emb, rel_emb):
         return K.distmult_scores_all(all_ent, sub_emb, rel_emb)
@@ -315,18 +328,33 @@ class sf_ConvE_op(nn.Module):
 
         self.register_buffer("_one", torch.ones(1), persistent=False)      # the one-branch epilogue's weight (not in state_dict)
 
-    def forward(self, all_ent, sub_emb, rel_emb):
+    score_kind = "dot"
+
+    def _hip_ok(self, tensors):
         if self.embed_dim != self.k_h * self.k_w:
             raise AssertionError("embed_dim must equal k_h * k_w")
         mods = (self.bn0, self.conv2d, self.bn1, self.feature_drop, self.fc, self.hidden_drop, self.bn2)
-        if K.conve.hip_path_ok(mods, (self.bn0, self.bn1, self.bn2), (all_ent, sub_emb, rel_emb)):
+        return K.conve.hip_path_ok(mods, (self.bn0, self.bn1, self.bn2), tensors)
+
+    def _query_torch(self, sub_emb, rel_emb):
+        x = torch.stack([sub_emb, rel_emb], dim=1).reshape(-1, 1, 2 * self.k_h, self.k_w)
+        x = self.feature_drop(F.relu(self.bn1(self.conv2d(self.bn0(x)))))
+        return F.relu(self.bn2(self.hidden_drop(self.fc(x.flatten(1)))))
+
+    def query(self, sub_emb, rel_emb):
+        """The hidden vector after bn2 + ReLU [B, D]: forward without its last product and sigmoid.  Like forward it draws the dropout
+        masks and, in train mode, updates the BatchNorm statistics: one call per step."""
+        if self._hip_ok((sub_emb, rel_emb)):
+            return K.conve_query(sub_emb, rel_emb, K.conve.STACKED, (2 * self.k_h, self.k_w), self.bn0, self.conv2d, self.bn1,
+                                 self.feature_drop, self.fc, self.hidden_drop, self.bn2, self._one)
+        return self._query_torch(sub_emb, rel_emb)
+
+    def forward(self, all_ent, sub_emb, rel_emb):
+        if self._hip_ok((all_ent, sub_emb, rel_emb)):
             # the stacked image (reference :167-178) on csrc/conve.hip; BN2 + ReLU on the epilogue kernels, the product on the row GEMM
             return K.conve_scores(sub_emb, rel_emb, K.conve.STACKED, (2 * self.k_h, self.k_w), self.bn0, self.conv2d, self.bn1,
                                   self.feature_drop, self.fc, self.hidden_drop, self.bn2, self._one, all_ent, None)
-        x = torch.stack([sub_emb, rel_emb], dim=1).reshape(-1, 1, 2 * self.k_h, self.k_w)
-        x = self.feature_drop(F.relu(self.bn1(self.conv2d(self.bn0(x)))))
-        x = F.relu(self.bn2(self.hidden_drop(self.fc(x.flatten(1)))))
-        return torch.sigmoid(x @ all_ent.t())
+        return torch.sigmoid(self._query_torch(sub_emb, rel_emb) @ all_ent.t())
 
 
 MIXED_OPS = {

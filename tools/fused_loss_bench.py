@@ -2,16 +2,21 @@
 """The fixed-genotype driver's 1-N loss alone -- forward plus backward down to the gradients of the entity table, the subject rows and
 the relation rows -- two ways, in one process:
 
-  dense  LabelIndex.labels ([B, N] targets) -> distmult_scores_all ([B, N] probabilities) -> F.binary_cross_entropy
-  fused  functional.distmult_bce_all: mrg_distmult_bce_fwd / mrg_distmult_bce_dlogit (csrc/bce.hip), no [B, N] tensor
+  dense  LabelIndex.labels ([B, N] targets) -> the scorer's forward ([B, N] probabilities) -> F.binary_cross_entropy
+  fused  no [B, N] tensor: functional.distmult_bce_all (--scorer distmult: csrc/bce.hip), functional.transe_bce_all (--scorer transe:
+         csrc/transe_1n.hip, gamma = the rounded median distance of the batch), or sf_ConvE_op.query + functional.dot_bce_all
+         (--scorer conve: dropout 0, 32 filters; the scorer's own parameters receive gradients in both legs)
 
 at FB15k-237's shape (N = 14 541, B = 256, D = 64 and 200) and at the project's largest configuration (N = 1 000 000, B = 256,
 D = 256).  The legs alternate (dense, fused, dense, ...) after --warmup rounds each; a leg's time is the device time between two
 events around it, reported as median and min..max; its memory is the peak of torch.cuda.max_memory_allocated over the leg minus the
 allocation before it and minus the gradients it leaves.  --col-chunk takes a list: every value is one more fused leg (0 = the default,
-functional.bce_default_col_chunk).  Prints one JSON line per shape.  Needs a HIP device: there is no fallback.
+functional.bce_default_col_chunk).  After the timed rounds every leg runs once more under the library's per-entry-point meter
+("entry_ms": device time per C-ABI entry point of that round).  Prints one JSON line per shape.  Needs a HIP device: there is no fallback.
 
-    python tools/fused_loss_bench.py [--rounds 7] [--warmup 2] [--col-chunk 0,14560] [--shapes fb64,fb200,c5]
+A leg the library does not cover (the dense TransE backward stops at N = 262 140) is not run and reported as such.
+
+    python tools/fused_loss_bench.py [--scorer distmult|transe|conve] [--rounds 7] [--warmup 2] [--col-chunk 0,14560] [--shapes fb64,fb200,c5]
 """
 import argparse
 import json
@@ -23,15 +28,18 @@ import torch
 import torch.nn.functional as F
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from mr_gnas_amd import functional as K  # noqa: E402
+from mr_gnas_amd import _lib, functional as K, operations_lp as O  # noqa: E402
 from mr_gnas_amd.sampler import LabelIndex  # noqa: E402
 
 SHAPES = {"fb64": (14541, 237, 256, 64, 272115), "fb200": (14541, 237, 256, 200, 272115), "c5": (1_000_000, 64, 256, 256, 4_000_000)}
 SMOOTH = 0.1
+CONVE_IMAGE = {64: (8, 8, 3), 200: (20, 10, 7), 256: (16, 16, 7)}        # D: k_h, k_w, ker_sz
 
 
-def leg(fn, ent, sub, relb):
+def leg(fn, ent, sub, relb, params=()):
     e, s, r = (t.detach().requires_grad_(True) for t in (ent, sub, relb))
+    for p in params:
+        p.grad = None
     torch.cuda.synchronize()
     torch.cuda.reset_peak_memory_stats()
     before = torch.cuda.memory_allocated()
@@ -41,7 +49,7 @@ def leg(fn, ent, sub, relb):
     loss.backward()
     b.record()
     torch.cuda.synchronize()
-    peak = torch.cuda.max_memory_allocated() - before - sum(t.grad.numel() * 4 for t in (e, s, r))
+    peak = torch.cuda.max_memory_allocated() - before - sum(t.grad.numel() * 4 for t in (e, s, r) + tuple(params) if t.grad is not None)
     return a.elapsed_time(b), peak, float(loss.detach())
 
 
@@ -55,6 +63,7 @@ def main():
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--col-chunk", default="0")
     ap.add_argument("--shapes", default="fb64,fb200,c5")
+    ap.add_argument("--scorer", default="distmult", choices=("distmult", "transe", "conve"))
     args = ap.parse_args()
     if args.rounds < 5:
         raise SystemExit("fused_loss_bench: at least 5 rounds")
@@ -70,20 +79,50 @@ def main():
         subj, rel = tri[:B, 0].to(dev), tri[:B, 1].to(dev)
         scale = 0.3 if D <= 64 else 0.15
         ent, sub, relb = ((scale * torch.randn(n, D, generator=g)).to(dev) for n in (N, B, B))
-        legs = {"dense": lambda e, s, r: F.binary_cross_entropy(K.distmult_scores_all(e, s, r), index.labels(subj, rel, SMOOTH))}
+        params, extra = (), {}
+        if args.scorer == "distmult":
+            score = K.distmult_scores_all
+            fused = lambda e, s, r, cc: K.distmult_bce_all(e, s, r, index, subj, rel, SMOOTH, cc)
+        elif args.scorer == "transe":
+            with torch.no_grad():
+                o = sub + relb
+                gamma = float(torch.round((o.unsqueeze(1) - ent[:1024].unsqueeze(0)).abs().sum(-1).median()))   # over the first 1024 entities
+            extra = {"gamma": gamma}
+            score = lambda e, s, r: K.transe_scores_all(e, s, r, gamma)
+            fused = lambda e, s, r, cc: K.transe_bce_all(e, s, r, gamma, index, subj, rel, SMOOTH, cc)
+        else:
+            k_h, k_w, ks = CONVE_IMAGE[D]
+            torch.manual_seed(0)
+            op = O.sf_ConvE_op({"embed_dim": D, "k_h": k_h, "k_w": k_w, "ker_sz": ks, "num_filt": 32, "conve_hid_drop": 0.0,
+                                "feat_drop": 0.0}).to(dev).train()
+            params, score = tuple(op.parameters()), op
+            fused = lambda e, s, r, cc: K.dot_bce_all(e, op.query(s, r), index, subj, rel, SMOOTH, cc)
+        legs = {"dense": lambda e, s, r: F.binary_cross_entropy(score(e, s, r), index.labels(subj, rel, SMOOTH))}
         for c in chunks:
             cc = c or K.bce_default_col_chunk(B)
-            legs[f"fused_col_chunk_{cc}"] = (lambda e, s, r, cc=cc: K.distmult_bce_all(e, s, r, index, subj, rel, SMOOTH, cc))
-        times, peaks, losses = {k: [] for k in legs}, {k: 0 for k in legs}, {}
+            legs[f"fused_col_chunk_{cc}"] = (lambda e, s, r, cc=cc: fused(e, s, r, cc))
+        times, peaks, losses, errors = {k: [] for k in legs}, {k: 0 for k in legs}, {}, {}
+        if args.scorer == "transe" and N > 4 * 65535:           # transe_bwd_ent_k's grid.y: the leg is not attempted
+            errors["dense"] = "mrg_transe_score_bwd covers N <= 262 140"
         for rnd in range(args.warmup + args.rounds):
             for k, fn in legs.items():                          # alternating: one leg of each kind per round
-                ms, peak, loss = leg(fn, ent, sub, relb)
+                if k in errors:
+                    continue
+                ms, peak, loss = leg(fn, ent, sub, relb, params)
                 if rnd >= args.warmup:
                     times[k].append(ms)
                     peaks[k] = max(peaks[k], peak)
                     losses[k] = loss
-        print(json.dumps({"shape": {"name": name, "N": N, "B": B, "D": D, "label_smooth": SMOOTH, "matrix_MiB": B * N * 4 / 2 ** 20},
-                          "legs": {k: {**spread(times[k]), "peak_MiB": peaks[k] / 2 ** 20, "loss": losses[k]} for k in legs}}), flush=True)
+        entry_ms = {}
+        for k, fn in legs.items():                              # one more round per leg under the per-entry-point meter
+            if k not in errors:
+                _lib.meter.start()
+                leg(fn, ent, sub, relb, params)
+                entry_ms[k] = {n: round(r["ms"], 4) for n, r in sorted(_lib.meter.stop().items())}
+        print(json.dumps({"shape": {"name": name, "scorer": args.scorer, "N": N, "B": B, "D": D, "label_smooth": SMOOTH,
+                                    "matrix_MiB": B * N * 4 / 2 ** 20, **extra},
+                          "legs": {k: ({"error": errors[k]} if k in errors else
+                                       {**spread(times[k]), "peak_MiB": peaks[k] / 2 ** 20, "loss": losses[k], "entry_ms": entry_ms[k]}) for k in legs}}), flush=True)
         del index, ent, sub, relb, legs
         torch.cuda.empty_cache()
 
