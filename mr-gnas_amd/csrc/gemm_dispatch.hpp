@@ -11,7 +11,6 @@
 // The persistent transposed-accumulator kernel and the two-waves-per-SIMD kernel of rounds 2-3 live in tools/lab/ (tools/gemm_x3_lab.hip
 // still times them).  The switches that move a launch off its default kernel are GemmSwitches (x3_parts.hpp).
 #pragma once
-#include "sweep_limits.hpp"
 #include "gemm_x3.hpp"
 #include "gemm_x3s.hpp"
 #include "gemm_x3s8.hpp"
@@ -126,7 +125,7 @@ inline int launch_rowgemm_x3_mode_colsum(GemmArgs a, const void* Bp, hipStream_t
 }
 
 // ---- queries x all entities (rank.hip, bce.hip): the sweeps that launch rowgemm_x3s_k / rowgemm_k themselves -------------------------
-// (RANK_CHUNK, RANK_NT, RANK_MAX_N, BCE_COLS: sweep_limits.hpp, shared with the L1 sweeps of transe_1n.hip)
+// (RANK_CHUNK, RANK_NT, RANK_MAX_N, BCE_COLS: sweep_host.hpp, shared with the L1 sweeps of transe_1n.hip)
 inline bool rank_split_core(int D) { return gemm_mode() != 1 && D > 48 && D % 4 == 0; }
 
 inline size_t gemm_workspace_bytes(int K, int N) {

@@ -11,26 +11,26 @@
 // Split-bf16 core (rowgemm_x3s_k, the entity table pre-split once per call) where it takes the shape, D > 48 and D % 4 == 0;
 // every other D runs the same two epilogues on the exact-f32 core (rowgemm_k).
 // mrg_rows_rank is the same body for query rows the caller already holds (ConvE's hidden vector, any "dot" scorer): step 1 gathers
-// the target rows only.  rank_prep_k / rank_finish_k live in sweep_prep.hpp, shared with the L1 sweeps of transe_1n.hip.
+// the target rows only.  rank_prep_k / rank_finish_k live in sweep_prep.hpp and the host code around them in
+// sweep_host.hpp, shared with the L1 sweeps of transe_1n.hip.
 #include "gemm_dispatch.hpp"
-#include "sweep_prep.hpp"      // rank_prep_k, rank_finish_k
+#include "sweep_host.hpp"      // the launch bounds, the workspace's rounding and base, the checks; rank_prep_k, rank_finish_k
 
 namespace mrg {
 
 struct RankPlan { size_t ent_split, a, t, t_split, qinfo, tscore, counts, total; };
-inline size_t rank_up(size_t x) { return (x + 255) & ~(size_t)255; }
 inline RankPlan rank_plan(int64_t Q, int64_t N, int D) {
   RankPlan p{};
   const int64_t qc = Q < RANK_CHUNK ? Q : RANK_CHUNK;
   const bool split = D > 48 && D % 4 == 0;                  // (sized for the split core whatever mrg_gemm_set_mode says)
   size_t off = 256;                                          // slack: the workspace pointer is rounded up to 256 bytes
-  p.ent_split = off; off += rank_up(split ? x3_bsplit_bytes((int)N, D, RANK_NT) : 0);
-  p.a = off; off += rank_up((size_t)qc * D * sizeof(float));
-  p.t = off; off += rank_up((size_t)qc * D * sizeof(float));
-  p.t_split = off; off += rank_up(split ? x3_bsplit_bytes((int)qc, D, 4) : 0);
-  p.qinfo = off; off += rank_up((size_t)Q * 4 * sizeof(int32_t));
-  p.tscore = off; off += rank_up((size_t)Q * sizeof(float));
-  p.counts = off; off += rank_up((size_t)Q * sizeof(unsigned));
+  p.ent_split = off; off += sweep_up(split ? x3_bsplit_bytes((int)N, D, RANK_NT) : 0);
+  p.a = off; off += sweep_up((size_t)qc * D * sizeof(float));
+  p.t = off; off += sweep_up((size_t)qc * D * sizeof(float));
+  p.t_split = off; off += sweep_up(split ? x3_bsplit_bytes((int)qc, D, 4) : 0);
+  p.qinfo = off; off += sweep_up((size_t)Q * 4 * sizeof(int32_t));
+  p.tscore = off; off += sweep_up((size_t)Q * sizeof(float));
+  p.counts = off; off += sweep_up((size_t)Q * sizeof(unsigned));
   p.total = off;
   return p;
 }
@@ -64,10 +64,8 @@ inline int rank_chunk_exact(GemmArgs g, const float* T, const float* ent, int64_
 
 using namespace mrg;
 
-static bool rank_shape_ok(int64_t Q, int64_t N, int D) { return Q >= 0 && N >= 1 && N <= RANK_MAX_N && D >= 1 && D <= 1024 && (D <= 256 || D % 4 == 0); }
-
 extern "C" int64_t mrg_distmult_rank_workspace_bytes(int64_t Q, int64_t N, int D) {
-  if (!rank_shape_ok(Q, N, D)) return MRG_E_SHAPE;
+  if (!sweep_shape_ok(Q, N, D, true)) return MRG_E_SHAPE;
   return (int64_t)rank_plan(Q, N, D).total;
 }
 
@@ -76,11 +74,11 @@ extern "C" int64_t mrg_distmult_rank_workspace_bytes(int64_t Q, int64_t N, int D
 static int rank_run(const float* rows_q, const float* ent, const float* rel, const int32_t* a_idx, const int32_t* r_idx, const int32_t* t_idx,
                     const int64_t* qkey, const int32_t* when, const int64_t* keys, const int32_t* rowptr, const int32_t* members,
                     const int32_t* gone_at, int64_t U, int64_t Q, int64_t N, int D, int64_t* ranks, void* ws, int64_t ws_bytes, void* stream) {
-  if (U > 0 && (!qkey || !when || !keys || !rowptr || !members || !gone_at)) return MRG_E_NULLPTR;
+  if (!sweep_labels_ok(U, qkey, when, keys, rowptr, members, gone_at)) return MRG_E_NULLPTR;
   const RankPlan p = rank_plan(Q, N, D);
   if (!ws || ws_bytes < (int64_t)p.total) return MRG_E_WORKSPACE;
   hipStream_t st = (hipStream_t)stream;
-  char* w = (char*)(((uintptr_t)ws + 255) & ~(uintptr_t)255) - 256;        // the plan's offsets start at 256
+  char* w = sweep_ws_base(ws);
   float* A = (float*)(w + p.a);
   float* T = (float*)(w + p.t);
   int32_t* qinfo = (int32_t*)(w + p.qinfo);
@@ -90,12 +88,11 @@ static int rank_run(const float* rows_q, const float* ent, const float* rel, con
   const bool split = rank_split_core(D) && qal;
   const bool vec = D % 4 == 0 && aligned16(ent) && qal;
 
-  hipLaunchKernelGGL(rank_prep_k, dim3((unsigned)((Q + 255) / 256)), dim3(256), 0, st, t_idx, qkey, when, keys, rowptr, U, Q, qinfo, counts);
-  MRG_LAUNCH_CHECK();
+  int rc = sweep_launch_rows(rank_prep_k, Q, st, t_idx, qkey, when, keys, rowptr, U, Q, qinfo, counts);
+  if (rc != MRG_OK) return rc;
   if (split) launch_bsplit(ent, D, 1, (int)N, D, RANK_NT, w + p.ent_split, st);
   for (int64_t q0 = 0; q0 < Q; q0 += RANK_CHUNK) {
     const int64_t rows = Q - q0 < RANK_CHUNK ? Q - q0 : RANK_CHUNK;
-    int rc = MRG_OK;
     const float* Aq = A;
     if (rows_q) Aq = rows_q + q0 * D;
     else rc = mrg_gather_compose_fwd(MRG_COMPOSE_MULT, ent, rel, a_idx + q0, r_idx + q0, A, rows, D, stream);
@@ -110,16 +107,14 @@ static int rank_run(const float* rows_q, const float* ent, const float* rel, con
     else rc = rank_chunk_exact<false>(g, T, ent, N, D, st);
     if (rc != MRG_OK) return rc;
   }
-  hipLaunchKernelGGL(rank_finish_k, dim3((unsigned)((Q + 255) / 256)), dim3(256), 0, st, counts, ranks, Q);
-  MRG_LAUNCH_CHECK();
-  return MRG_OK;
+  return sweep_launch_rows(rank_finish_k, Q, st, counts, ranks, Q);
 }
 
 extern "C" int mrg_distmult_rank(const float* ent, const float* rel, const int32_t* a_idx, const int32_t* r_idx, const int32_t* t_idx,
                                  const int64_t* qkey, const int32_t* when, const int64_t* keys, const int32_t* rowptr, const int32_t* members,
                                  const int32_t* gone_at, int64_t U, int64_t Q, int64_t N, int D, int64_t* ranks, void* ws, int64_t ws_bytes,
                                  void* stream) {
-  if (U < 0 || !rank_shape_ok(Q, N, D)) return MRG_E_SHAPE;
+  if (U < 0 || !sweep_shape_ok(Q, N, D, true)) return MRG_E_SHAPE;
   if (Q == 0) return MRG_OK;
   if (!ent || !rel || !a_idx || !r_idx || !t_idx || !ranks) return MRG_E_NULLPTR;
   return rank_run(nullptr, ent, rel, a_idx, r_idx, t_idx, qkey, when, keys, rowptr, members, gone_at, U, Q, N, D, ranks, ws, ws_bytes, stream);
@@ -128,7 +123,7 @@ extern "C" int mrg_distmult_rank(const float* ent, const float* rel, const int32
 extern "C" int mrg_rows_rank(const float* q, const float* ent, const int32_t* t_idx, const int64_t* qkey, const int32_t* when, const int64_t* keys,
                              const int32_t* rowptr, const int32_t* members, const int32_t* gone_at, int64_t U, int64_t Q, int64_t N, int D,
                              int64_t* ranks, void* ws, int64_t ws_bytes, void* stream) {
-  if (U < 0 || !rank_shape_ok(Q, N, D)) return MRG_E_SHAPE;
+  if (U < 0 || !sweep_shape_ok(Q, N, D, true)) return MRG_E_SHAPE;
   if (Q == 0) return MRG_OK;
   if (!q || !ent || !t_idx || !ranks) return MRG_E_NULLPTR;
   return rank_run(q, ent, nullptr, nullptr, nullptr, t_idx, qkey, when, keys, rowptr, members, gone_at, U, Q, N, D, ranks, ws, ws_bytes, stream);

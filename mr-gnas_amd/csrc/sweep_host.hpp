@@ -1,0 +1,70 @@
+// Host code the [queries, entities] sweeps that keep no [B, N] tensor share (bce.hip, rank.hip on the row GEMM; transe_1n.hip): the launch
+// bounds, the workspace's rounding and base, the argument checks, the launch grid of a blocked sweep and the launch of sweep_prep.hpp's
+// kernels.  Which core a shape takes (rank_split_core, the aligned16 conditions, VEC4) stays in the file that owns the core.
+#pragma once
+#include "common.hpp"
+#include "sweep_prep.hpp"
+
+namespace mrg {
+
+constexpr int64_t RANK_CHUNK = 8192;          // queries per sweep launch: bounds the [chunk, D] operands of the workspace and grid.x
+constexpr int RANK_NT = 7;                    // column tiles per block of the row GEMM's sweep
+constexpr int64_t RANK_MAX_N = 65535LL * RANK_NT * 32;     // grid.y
+constexpr int64_t BCE_COLS = (int64_t)RANK_NT * 32 * 128;      // entity columns per sweep launch (28 672): bounds the split table
+
+inline size_t sweep_up(size_t x) { return (x + 255) & ~(size_t)255; }
+
+// The base the plans' offsets count from.  They start at 256: the slack that lets the workspace pointer be rounded up to 256 bytes.
+inline char* sweep_ws_base(void* ws) { return (char*)(((uintptr_t)ws + 255) & ~(uintptr_t)255) - 256; }
+
+// row_gemm: the row GEMM's cores take D <= 256, or beyond it a multiple of 4
+inline bool sweep_shape_ok(int64_t rows, int64_t N, int D, bool row_gemm) {
+  return rows >= 0 && N >= 1 && N <= RANK_MAX_N && D >= 1 && D <= 1024 && (!row_gemm || D <= 256 || D % 4 == 0);
+}
+
+// the label (filter) pointers may be NULL only when there is no list at all
+template <class... P>
+inline bool sweep_labels_ok(int64_t U, const P*... p) { return U <= 0 || (... && (p != nullptr)); }
+
+// The launch grid of a blocked sweep over the columns [c0, c1) of rows_all rows in workgroup tiles of tile_rows x tile_cols: column blocks
+// of BCE_COLS outermost (the row GEMM splits the entity rows once per block), row chunks of RANK_CHUNK inside.  The ONE definition of
+// it: a sweep launches through each(), a plan sizes the per-workgroup partials with workgroups(), which walks the same loop.
+struct SweepGrid {
+  int64_t rows_all, c0, c1;
+  int tile_rows, tile_cols;
+  unsigned row_tiles(int64_t rows) const { return (unsigned)((rows + tile_rows - 1) / tile_rows); }
+  unsigned col_tiles(int64_t nc) const { return (unsigned)((nc + tile_cols - 1) / tile_cols); }
+  // launch(q0, rows, c, nc, wg0): rows [q0, q0 + rows) x columns [c, c + nc) on a grid of row_tiles(rows) x col_tiles(nc) workgroups;
+  // wg0 counts the workgroups of the launches before it (where a launch appends its partials).  An error ends the walk and is returned.
+  template <class F>
+  int each(F&& launch, int64_t* total = nullptr) const {
+    int64_t wg = 0;
+    for (int64_t c = c0; c < c1; c += BCE_COLS) {
+      const int64_t nc = c1 - c < BCE_COLS ? c1 - c : BCE_COLS;
+      for (int64_t q0 = 0; q0 < rows_all; q0 += RANK_CHUNK) {
+        const int64_t rows = rows_all - q0 < RANK_CHUNK ? rows_all - q0 : RANK_CHUNK;
+        const int rc = launch(q0, rows, c, nc, wg);
+        if (rc != MRG_OK) return rc;
+        wg += (int64_t)row_tiles(rows) * col_tiles(nc);
+      }
+    }
+    if (total) *total = wg;
+    return MRG_OK;
+  }
+  int64_t workgroups() const {
+    int64_t n = 0;
+    each([](int64_t, int64_t, int64_t, int64_t, int64_t) { return (int)MRG_OK; }, &n);
+    return n;
+  }
+};
+
+// kernel<<<ceil(n / 256), 256>>>(args...): the launch of sweep_prep.hpp's kernels, one thread per row (bce_finish_k: n = 1, its one
+// workgroup).  The kernels are `static`, so each translation unit launches its own copy.  MRG_OK or the HIP error.
+template <class... KARGS, class... ARGS>
+static inline int sweep_launch_rows(void (*kernel)(KARGS...), int64_t n, hipStream_t st, ARGS... args) {
+  hipLaunchKernelGGL(kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, static_cast<KARGS>(args)...);
+  MRG_LAUNCH_CHECK();
+  return MRG_OK;
+}
+
+}  // namespace mrg

@@ -18,10 +18,7 @@
 // added in order), bce_finish_k adds the partials in a fixed order; counts are integer atomics, one per (row, workgroup).
 // Labels / filters of a tile: thread r < 64 walks the slice of tile row r's ascending list that falls into the tile's 64 entities
 // (binary search for its start, as gemm_bce_label_words does) and leaves a 64-bit mask in LDS.
-#include <hip/hip_runtime.h>
-#include "common.hpp"
-#include "sweep_limits.hpp"
-#include "sweep_prep.hpp"      // bce_prep_k, bce_finish_k, rank_prep_k, rank_finish_k
+#include "sweep_host.hpp"      // the launch bounds, SweepGrid, the workspace's rounding and base, the checks; the prep / finish kernels
 
 namespace mrg {
 
@@ -230,16 +227,16 @@ __global__ __launch_bounds__(256) void l1_sweep_k(const L1Args a) {
   }
 }
 
-struct L1Plan { size_t qlist, partial, total; int64_t nrb, ncb; };
-inline size_t l1_up(size_t x) { return (x + 255) & ~(size_t)255; }
+inline SweepGrid l1_grid(int64_t rows_all, int64_t c0, int64_t c1) { return SweepGrid{rows_all, c0, c1, L1_T, L1_T}; }
+
+struct L1Plan { size_t qlist, partial, total; int64_t nparts; };
 // ncols: the columns a call sweeps (N for the forward, c1 - c0 for the logit gradient)
 inline L1Plan l1_bce_plan(int64_t B, int64_t ncols) {
   L1Plan p{};
-  p.nrb = (B / RANK_CHUNK) * (RANK_CHUNK / L1_T) + (B % RANK_CHUNK + L1_T - 1) / L1_T;                 // workgroups along the rows ...
-  p.ncb = (ncols / BCE_COLS) * (BCE_COLS / L1_T) + (ncols % BCE_COLS + L1_T - 1) / L1_T;               // ... and the columns
+  p.nparts = l1_grid(B, 0, ncols).workgroups();              // one float64 partial per workgroup of the sweep
   size_t off = 256;                                          // slack: the workspace pointer is rounded up to 256 bytes
-  p.qlist = off; off += l1_up((size_t)B * 2 * sizeof(int32_t));
-  p.partial = off; off += l1_up((size_t)p.nrb * p.ncb * sizeof(double));
+  p.qlist = off; off += sweep_up((size_t)B * 2 * sizeof(int32_t));
+  p.partial = off; off += sweep_up((size_t)p.nparts * sizeof(double));
   p.total = off;
   return p;
 }
@@ -248,123 +245,113 @@ struct L1RankPlan { size_t qinfo, tdist, counts, total; };
 inline L1RankPlan l1_rank_plan(int64_t Q) {
   L1RankPlan p{};
   size_t off = 256;
-  p.qinfo = off; off += l1_up((size_t)Q * 4 * sizeof(int32_t));
-  p.tdist = off; off += l1_up((size_t)Q * sizeof(float));
-  p.counts = off; off += l1_up((size_t)Q * sizeof(unsigned));
+  p.qinfo = off; off += sweep_up((size_t)Q * 4 * sizeof(int32_t));
+  p.tdist = off; off += sweep_up((size_t)Q * sizeof(float));
+  p.counts = off; off += sweep_up((size_t)Q * sizeof(unsigned));
   p.total = off;
   return p;
 }
 
-// The sweep over the columns [c0, c1) of all rows: column blocks of BCE_COLS outermost, row chunks of RANK_CHUNK inside.  `a` carries what
-// does not change from launch to launch; L1_LOSS appends its launches' partials at a.partial.
+// The sweep over the columns [c0, c1) of all rows on l1_grid: column blocks of BCE_COLS outermost, row chunks of RANK_CHUNK inside.  `all`
+// carries what does not change from launch to launch; L1_LOSS appends its launches' partials at all.partial.
 template <int EPI>
-inline int l1_sweep(L1Args a, const float* obj, const float* ent, int64_t rows_all, int64_t c0, int64_t c1, hipStream_t st) {
-  const bool vec = a.D % 4 == 0 && aligned16(obj) && aligned16(ent);
-  const int32_t* qlist = a.qlist;
-  const int32_t* qinfo = a.qinfo;
-  const float* tdist = a.tdist;
-  unsigned* counts = a.counts;
-  float* dl = a.dl;
-  for (int64_t c = c0; c < c1; c += BCE_COLS) {
-    const int64_t nc = c1 - c < BCE_COLS ? c1 - c : BCE_COLS;
-    for (int64_t q0 = 0; q0 < rows_all; q0 += RANK_CHUNK) {
-      const int64_t rows = rows_all - q0 < RANK_CHUNK ? rows_all - q0 : RANK_CHUNK;
-      a.obj = obj + q0 * a.D; a.ent = ent + c * a.D; a.rows = rows; a.ncols = (int)nc; a.e0 = (int)c;
-      if (EPI == L1_RANK) { a.qinfo = qinfo + q0 * 4; a.tdist = tdist + q0; a.counts = counts + q0; }
-      else a.qlist = qlist + q0 * 2;
-      if (EPI == L1_DLOGIT) a.dl = dl + q0 * a.ld + (c - c0);
-      const dim3 grid((unsigned)((nc + L1_T - 1) / L1_T), (unsigned)((rows + L1_T - 1) / L1_T));
-      if (vec) hipLaunchKernelGGL((l1_sweep_k<EPI, true>), grid, dim3(256), 0, st, a);
-      else hipLaunchKernelGGL((l1_sweep_k<EPI, false>), grid, dim3(256), 0, st, a);
-      MRG_LAUNCH_CHECK();
-      if (EPI == L1_LOSS) a.partial += (int64_t)grid.x * grid.y;
-    }
-  }
-  return MRG_OK;
+static int l1_sweep(const L1Args& all, const float* obj, const float* ent, int64_t rows_all, int64_t c0, int64_t c1, hipStream_t st) {
+  const bool vec = all.D % 4 == 0 && aligned16(obj) && aligned16(ent);
+  const SweepGrid sg = l1_grid(rows_all, c0, c1);
+  return sg.each([&](int64_t q0, int64_t rows, int64_t c, int64_t nc, int64_t wg0) {
+    L1Args a = all;
+    a.obj = obj + q0 * a.D; a.ent = ent + c * a.D; a.rows = rows; a.ncols = (int)nc; a.e0 = (int)c;
+    if (EPI == L1_RANK) { a.qinfo = all.qinfo + q0 * 4; a.tdist = all.tdist + q0; a.counts = all.counts + q0; }
+    else a.qlist = all.qlist + q0 * 2;
+    if (EPI == L1_DLOGIT) a.dl = all.dl + q0 * a.ld + (c - c0);
+    if (EPI == L1_LOSS) a.partial = all.partial + wg0;
+    const dim3 grid(sg.col_tiles(nc), sg.row_tiles(rows));
+    if (vec) hipLaunchKernelGGL((l1_sweep_k<EPI, true>), grid, dim3(256), 0, st, a);
+    else hipLaunchKernelGGL((l1_sweep_k<EPI, false>), grid, dim3(256), 0, st, a);
+    MRG_LAUNCH_CHECK();
+    return (int)MRG_OK;
+  });
 }
 
 }  // namespace mrg
 
 using namespace mrg;
 
-static bool l1_shape_ok(int64_t B, int64_t N, int D) { return B >= 0 && N >= 1 && N <= RANK_MAX_N && D >= 1 && D <= 1024; }
-
 extern "C" int64_t mrg_transe_bce_workspace_bytes(int64_t B, int64_t ncols, int D) {
-  if (!l1_shape_ok(B, ncols, D)) return MRG_E_SHAPE;
+  if (!sweep_shape_ok(B, ncols, D, false)) return MRG_E_SHAPE;
   return (int64_t)l1_bce_plan(B, ncols).total;
+}
+
+// The body of both entry points from the label pointers on.  dl == NULL: the loss over the columns [0, N) = [c0, c1)
+// (mrg_transe_bce_fwd); else the logit gradient of the columns [c0, c1) (mrg_transe_bce_dlogit).
+static int l1_bce_run(const float* obj, const float* ent, const int64_t* qkey, const int64_t* keys, const int32_t* rowptr, const int32_t* objs,
+                      int64_t U, float gamma, float v_zero, float v_one, int64_t B, int64_t N, int D, int64_t c0, int64_t c1, float* loss,
+                      const float* gscale, float* dl, void* ws, int64_t ws_bytes, void* stream) {
+  if (!sweep_labels_ok(U, qkey, keys, rowptr, objs)) return MRG_E_NULLPTR;
+  const L1Plan p = l1_bce_plan(B, c1 - c0);
+  if (!ws || ws_bytes < (int64_t)p.total) return MRG_E_WORKSPACE;
+  hipStream_t st = (hipStream_t)stream;
+  char* w = sweep_ws_base(ws);
+  int32_t* qlist = (int32_t*)(w + p.qlist);
+  double* partial = (double*)(w + p.partial);
+  int rc = sweep_launch_rows(bce_prep_k, B, st, qkey, keys, rowptr, U, B, qlist);
+  if (rc != MRG_OK) return rc;
+  L1Args a{};
+  a.D = D; a.gamma = gamma; a.qlist = qlist; a.list = objs; a.v_zero = v_zero; a.v_one = v_one;
+  if (dl) {
+    a.gscale = gscale; a.dl = dl; a.ld = c1 - c0;
+    return l1_sweep<L1_DLOGIT>(a, obj, ent, B, c0, c1, st);
+  }
+  a.partial = partial;
+  rc = l1_sweep<L1_LOSS>(a, obj, ent, B, c0, c1, st);
+  if (rc != MRG_OK) return rc;
+  return sweep_launch_rows(bce_finish_k, 1, st, partial, p.nparts, 1.0 / ((double)B * (double)N), loss);
 }
 
 extern "C" int mrg_transe_bce_fwd(const float* obj, const float* ent, const int64_t* qkey, const int64_t* keys, const int32_t* rowptr,
                                   const int32_t* objs, int64_t U, float gamma, float v_zero, float v_one, int64_t B, int64_t N, int D, float* loss,
                                   void* ws, int64_t ws_bytes, void* stream) {
-  if (U < 0 || !l1_shape_ok(B, N, D)) return MRG_E_SHAPE;
+  if (U < 0 || !sweep_shape_ok(B, N, D, false)) return MRG_E_SHAPE;
   if (B == 0) return MRG_OK;
   if (!obj || !ent || !loss) return MRG_E_NULLPTR;
-  if (U > 0 && (!qkey || !keys || !rowptr || !objs)) return MRG_E_NULLPTR;
-  const L1Plan p = l1_bce_plan(B, N);
-  if (!ws || ws_bytes < (int64_t)p.total) return MRG_E_WORKSPACE;
-  hipStream_t st = (hipStream_t)stream;
-  char* w = (char*)(((uintptr_t)ws + 255) & ~(uintptr_t)255) - 256;        // the plan's offsets start at 256
-  int32_t* qlist = (int32_t*)(w + p.qlist);
-  double* partial = (double*)(w + p.partial);
-  hipLaunchKernelGGL(bce_prep_k, dim3((unsigned)((B + 255) / 256)), dim3(256), 0, st, qkey, keys, rowptr, U, B, qlist);
-  MRG_LAUNCH_CHECK();
-  L1Args a{};
-  a.D = D; a.gamma = gamma; a.qlist = qlist; a.list = objs; a.v_zero = v_zero; a.v_one = v_one; a.partial = partial;
-  const int rc = l1_sweep<L1_LOSS>(a, obj, ent, B, 0, N, st);
-  if (rc != MRG_OK) return rc;
-  hipLaunchKernelGGL(bce_finish_k, dim3(1), dim3(256), 0, st, partial, p.nrb * p.ncb, 1.0 / ((double)B * (double)N), loss);
-  MRG_LAUNCH_CHECK();
-  return MRG_OK;
+  return l1_bce_run(obj, ent, qkey, keys, rowptr, objs, U, gamma, v_zero, v_one, B, N, D, 0, N, loss, nullptr, nullptr, ws, ws_bytes, stream);
 }
 
 extern "C" int mrg_transe_bce_dlogit(const float* obj, const float* ent, const int64_t* qkey, const int64_t* keys, const int32_t* rowptr,
                                      const int32_t* objs, int64_t U, float gamma, float v_zero, float v_one, int64_t B, int64_t N, int D,
                                      int64_t c0, int64_t c1, const float* gscale, float* dl, void* ws, int64_t ws_bytes, void* stream) {
-  if (U < 0 || !l1_shape_ok(B, N, D) || c0 < 0 || c1 <= c0 || c1 > N) return MRG_E_SHAPE;
+  if (U < 0 || !sweep_shape_ok(B, N, D, false) || c0 < 0 || c1 <= c0 || c1 > N) return MRG_E_SHAPE;
   if (B == 0) return MRG_OK;
   if (!obj || !ent || !gscale || !dl) return MRG_E_NULLPTR;
-  if (U > 0 && (!qkey || !keys || !rowptr || !objs)) return MRG_E_NULLPTR;
-  const L1Plan p = l1_bce_plan(B, c1 - c0);
-  if (!ws || ws_bytes < (int64_t)p.total) return MRG_E_WORKSPACE;
-  hipStream_t st = (hipStream_t)stream;
-  char* w = (char*)(((uintptr_t)ws + 255) & ~(uintptr_t)255) - 256;
-  int32_t* qlist = (int32_t*)(w + p.qlist);
-  hipLaunchKernelGGL(bce_prep_k, dim3((unsigned)((B + 255) / 256)), dim3(256), 0, st, qkey, keys, rowptr, U, B, qlist);
-  MRG_LAUNCH_CHECK();
-  L1Args a{};
-  a.D = D; a.gamma = gamma; a.qlist = qlist; a.list = objs; a.v_zero = v_zero; a.v_one = v_one; a.gscale = gscale; a.dl = dl; a.ld = c1 - c0;
-  return l1_sweep<L1_DLOGIT>(a, obj, ent, B, c0, c1, st);
+  return l1_bce_run(obj, ent, qkey, keys, rowptr, objs, U, gamma, v_zero, v_one, B, N, D, c0, c1, nullptr, gscale, dl, ws, ws_bytes, stream);
 }
 
 extern "C" int64_t mrg_transe_rank_workspace_bytes(int64_t Q, int64_t N, int D) {
-  if (!l1_shape_ok(Q, N, D)) return MRG_E_SHAPE;
+  if (!sweep_shape_ok(Q, N, D, false)) return MRG_E_SHAPE;
   return (int64_t)l1_rank_plan(Q).total;
 }
 
 extern "C" int mrg_transe_rank(const float* obj, const float* ent, const int32_t* t_idx, const int64_t* qkey, const int32_t* when,
                                const int64_t* keys, const int32_t* rowptr, const int32_t* members, const int32_t* gone_at, int64_t U, int64_t Q,
                                int64_t N, int D, int64_t* ranks, void* ws, int64_t ws_bytes, void* stream) {
-  if (U < 0 || !l1_shape_ok(Q, N, D)) return MRG_E_SHAPE;
+  if (U < 0 || !sweep_shape_ok(Q, N, D, false)) return MRG_E_SHAPE;
   if (Q == 0) return MRG_OK;
   if (!obj || !ent || !t_idx || !ranks) return MRG_E_NULLPTR;
-  if (U > 0 && (!qkey || !when || !keys || !rowptr || !members || !gone_at)) return MRG_E_NULLPTR;
+  if (!sweep_labels_ok(U, qkey, when, keys, rowptr, members, gone_at)) return MRG_E_NULLPTR;
   const L1RankPlan p = l1_rank_plan(Q);
   if (!ws || ws_bytes < (int64_t)p.total) return MRG_E_WORKSPACE;
   hipStream_t st = (hipStream_t)stream;
-  char* w = (char*)(((uintptr_t)ws + 255) & ~(uintptr_t)255) - 256;
+  char* w = sweep_ws_base(ws);
   int32_t* qinfo = (int32_t*)(w + p.qinfo);
   float* tdist = (float*)(w + p.tdist);
   unsigned* counts = (unsigned*)(w + p.counts);
-  hipLaunchKernelGGL(rank_prep_k, dim3((unsigned)((Q + 255) / 256)), dim3(256), 0, st, t_idx, qkey, when, keys, rowptr, U, Q, qinfo, counts);
-  MRG_LAUNCH_CHECK();
-  hipLaunchKernelGGL(l1_target_k, dim3((unsigned)((Q + 255) / 256)), dim3(256), 0, st, obj, ent, qinfo, Q, D, tdist);
-  MRG_LAUNCH_CHECK();
+  int rc = sweep_launch_rows(rank_prep_k, Q, st, t_idx, qkey, when, keys, rowptr, U, Q, qinfo, counts);
+  if (rc != MRG_OK) return rc;
+  rc = sweep_launch_rows(l1_target_k, Q, st, obj, ent, qinfo, Q, D, tdist);
+  if (rc != MRG_OK) return rc;
   L1Args a{};
   a.D = D; a.qinfo = qinfo; a.list = members; a.gone_at = gone_at; a.tdist = tdist; a.counts = counts;
-  const int rc = l1_sweep<L1_RANK>(a, obj, ent, Q, 0, N, st);
+  rc = l1_sweep<L1_RANK>(a, obj, ent, Q, 0, N, st);
   if (rc != MRG_OK) return rc;
-  hipLaunchKernelGGL(rank_finish_k, dim3((unsigned)((Q + 255) / 256)), dim3(256), 0, st, counts, ranks, Q);
-  MRG_LAUNCH_CHECK();
-  return MRG_OK;
+  return sweep_launch_rows(rank_finish_k, Q, st, counts, ranks, Q);
 }

@@ -11,7 +11,9 @@ module: ``calc_mrr`` / ``calc_raw_mrr`` / ``calc_filtered_mrr`` / ``infer_graph`
 (``mrg_distmult_rank``: the DistMult product as a row GEMM whose epilogue counts; no [Q, N] tensor).
 
 ``predict_fused`` (DistMult) and ``predict_1n`` (every scorer with ``query`` / ``score_kind``: DistMult, ConvE, TransE) are ``predict``
-without a [B, N] tensor, over ``query_ranks`` (``mrg_rows_rank`` / ``mrg_transe_rank``).
+without a [B, N] tensor, over ``query_ranks`` (``mrg_rows_rank`` / ``mrg_transe_rank``).  ``distmult_ranks`` and ``query_ranks`` share
+their filter side and their call (``_filter_side``, ``_rank_call``); the three ``predict`` passes share their per-batch statistics
+vector and their one device -> host copy (``_stats_begin``, ``_batch_stats``, ``_stats_end``).
 """
 import torch
 import torch.nn.functional as F
@@ -34,28 +36,40 @@ def filtered_ranks(pred, labels, obj):
 _HITS = (1, 3, 10)
 
 
+def _stats_begin(device):
+    """(ks, acc): the hit thresholds and the zeroed float64 device vector [count, mr, mrr, loss, hits@k ...] an evaluation pass adds to."""
+    return torch.tensor(_HITS, dtype=torch.float64, device=device), torch.zeros(4 + len(_HITS), dtype=torch.float64, device=device)
+
+
+def _batch_stats(ranks, loss, ks):
+    """One batch's [count, mr, mrr, loss, hits@k ...] from its float64 ranks and its mean loss, on the device."""
+    return torch.cat((torch.stack((ranks.new_tensor(float(ranks.numel())), ranks.sum(), ranks.reciprocal().sum(), loss.double())),
+                      (ranks.unsqueeze(0) <= ks.unsqueeze(1)).sum(dim=1).double()))
+
+
+def _stats_end(acc):
+    """(results, summed loss) of a pass: the pass's only device -> host copy."""
+    tot = acc.tolist()
+    results = {'count': int(tot[0]), 'mr': tot[1], 'mrr': tot[2]}
+    results.update({f'hits@{k}': int(tot[4 + i]) for i, k in enumerate(_HITS)})
+    return results, tot[3]
+
+
 def predict(val_test_loader, g, model, device):
     """The evaluation pass of the fixed-genotype driver (reference train/mr_lp_train.py:269-314) with its bookkeeping on the device:
     the per-batch rank statistics (number of predictions, sum of ranks, sum of reciprocal ranks, hits at 1 / 3 / 10) and the summed
     BCE loss are accumulated in ONE float64 device vector and read back by ONE copy when the loader is exhausted -- the reference
     synchronises three times per batch (`.item()`).  Returns (results, summed loss), results keyed 'count', 'mr', 'mrr', 'hits@k'
     like the reference's, counts as int."""
-    ks = torch.tensor(_HITS, dtype=torch.float64, device=device)
-    acc = torch.zeros(4 + len(_HITS), dtype=torch.float64, device=device)       # [count, mr, mrr, loss, hits@k ...]
+    ks, acc = _stats_begin(device)
     with torch.no_grad():
         model.eval()
         for triplets, labels in val_test_loader:
             triplets, labels = triplets.to(device), labels.to(device)
             pred = model(g, triplets[:, 0], triplets[:, 1])
             ranks = filtered_ranks(pred, labels, triplets[:, 2]).double()
-            batch = torch.cat((torch.stack((ranks.new_tensor(float(ranks.numel())), ranks.sum(), ranks.reciprocal().sum(),
-                                            F.binary_cross_entropy(pred, labels).double())),
-                               (ranks.unsqueeze(0) <= ks.unsqueeze(1)).sum(dim=1).double()))
-            acc += batch
-    tot = acc.tolist()                                                          # the pass's only device -> host copy
-    results = {'count': int(tot[0]), 'mr': tot[1], 'mrr': tot[2]}
-    results.update({f'hits@{k}': int(tot[4 + i]) for i, k in enumerate(_HITS)})
-    return results, tot[3]
+            acc += _batch_stats(ranks, F.binary_cross_entropy(pred, labels), ks)
+    return _stats_end(acc)
 
 
 class _LabelSide:
@@ -103,8 +117,7 @@ def predict_1n(val_test_loader, g, model, label_index, device):
         raise MrgnasError(f"predict_1n needs a scorer with query() and a score_kind of 'dot' or 'l1'; this network scores with {type(sf).__name__}")
     side = _LabelSide(label_index)
     v_zero, v_one = label_index.label_values(0.0)
-    ks = torch.tensor(_HITS, dtype=torch.float64, device=device)
-    acc = torch.zeros(4 + len(_HITS), dtype=torch.float64, device=device)       # [count, mr, mrr, loss, hits@k ...]
+    ks, acc = _stats_begin(device)
     with torch.no_grad():
         model.eval()
         for batch in val_test_loader:
@@ -120,13 +133,8 @@ def predict_1n(val_test_loader, g, model, label_index, device):
                 loss = K.transe_bce_mean(q, ent, sf.gamma, label_index, qkey, v_zero, v_one)
             else:
                 loss = K.distmult_bce_mean(q, ent, label_index, qkey, v_zero, v_one)
-            batch_acc = torch.cat((torch.stack((ranks.new_tensor(float(ranks.numel())), ranks.sum(), ranks.reciprocal().sum(), loss.double())),
-                                   (ranks.unsqueeze(0) <= ks.unsqueeze(1)).sum(dim=1).double()))
-            acc += batch_acc
-    tot = acc.tolist()                                                          # the pass's only device -> host copy
-    results = {'count': int(tot[0]), 'mr': tot[1], 'mrr': tot[2]}
-    results.update({f'hits@{k}': int(tot[4 + i]) for i, k in enumerate(_HITS)})
-    return results, tot[3]
+            acc += _batch_stats(ranks, loss, ks)
+    return _stats_end(acc)
 
 
 def combine_results(left, right):
@@ -206,6 +214,32 @@ class KnownTriples:
         self.object = _KnownSide(s * num_rels + r, o, gone, num_ent, num_rels)
 
 
+def _filter_side(msg, known_side, when, qkey, Q):
+    """The filter side of a rank call: (qkey, when, keys, rowptr, members, gone_at, U) on the HIP device, or all None and U = 0 for raw
+    ranks (no known_side, or an empty one).  qkey: the queries' keys [Q], or a function of known_side that forms them."""
+    k = known_side
+    if k is None or k.keys.numel() == 0:
+        return None, None, None, None, None, None, 0
+    if when is None or when.numel() != Q or qkey is None or not (callable(qkey) or qkey.numel() == Q):
+        raise ValueError(msg)
+    qkey, when = (qkey(k) if callable(qkey) else qkey).long().contiguous(), when.int().contiguous()
+    require_hip(k.keys, k.rowptr, k.members, k.gone_at, qkey, when)
+    return qkey, when, k.keys, k.rowptr, k.members, k.gone_at, k.keys.numel()
+
+
+def _rank_call(name, ws_name, ws_err, head, side, Q, N, D, like):
+    """ranks [Q] of entry point `name`(*head, *side, Q, N, D, ranks, workspace, stream): the workspace queried (ws_name; an error code is
+    raised under ws_err) and allocated beside `like`."""
+    ranks = torch.empty(Q, dtype=torch.int64, device=like.device)
+    nbytes = getattr(load(), ws_name)(Q, N, D)
+    if nbytes < 0:
+        check(int(nbytes), ws_err)
+    ws = torch.empty(max(int(nbytes), 1), dtype=torch.uint8, device=like.device)
+    call(name, (*(ptr(t) for t in head), *(ptr(t) for t in side[:6]), side[6], Q, N, D, ptr(ranks), ptr(ws), int(nbytes), stream_of(like)),
+         nbytes=4 * (Q + N) * D, flops=2 * Q * N * D)
+    return ranks
+
+
 def distmult_ranks(embedding, w, a, r, target, known_side=None, when=None):
     """ranks [Q] int64 (1-based) of `target` among all entities for the DistMult queries (fixed entity a, relation r), through
     mrg_distmult_rank.  known_side: a KnownTriples side (`.subject` when the subject is perturbed, `.object` when the object is) with
@@ -216,27 +250,9 @@ def distmult_ranks(embedding, w, a, r, target, known_side=None, when=None):
     Q, (N, D) = a.numel(), embedding.shape
     if r.numel() != Q or target.numel() != Q or w.shape[1] != D:
         raise ValueError("distmult_ranks: a / r / target [Q] and w [R, D] expected")
-    qkey = keys = rowptr = members = gone_at = None
-    U = 0
-    if known_side is not None and known_side.keys.numel() > 0:
-        if when is None or when.numel() != Q:
-            raise ValueError("distmult_ranks: a filtered call needs when [Q]")
-        k = known_side
-        require_hip(k.keys, k.rowptr, k.members, k.gone_at)
-        qkey, when = (a.long() * k.num_rels + r.long()).contiguous(), when.int().contiguous()
-        require_hip(when)
-        keys, rowptr, members, gone_at, U = k.keys, k.rowptr, k.members, k.gone_at, k.keys.numel()
-    else:
-        when = None
-    ranks = torch.empty(Q, dtype=torch.int64, device=embedding.device)
-    nbytes = load().mrg_distmult_rank_workspace_bytes(Q, N, D)
-    if nbytes < 0:
-        check(int(nbytes), "mrg_distmult_rank_workspace_bytes")
-    ws = torch.empty(max(int(nbytes), 1), dtype=torch.uint8, device=embedding.device)
-    call("mrg_distmult_rank", (ptr(embedding), ptr(w), ptr(a), ptr(r), ptr(target), ptr(qkey), ptr(when), ptr(keys), ptr(rowptr),
-                               ptr(members), ptr(gone_at), U, Q, N, D, ptr(ranks), ptr(ws), int(nbytes), stream_of(embedding)),
-         nbytes=4 * (Q + N) * D, flops=2 * Q * N * D)
-    return ranks
+    side = _filter_side("distmult_ranks: a filtered call needs when [Q]", known_side, when, lambda k: a.long() * k.num_rels + r.long(), Q)
+    return _rank_call("mrg_distmult_rank", "mrg_distmult_rank_workspace_bytes", "mrg_distmult_rank_workspace_bytes",
+                      (embedding, w, a, r, target), side, Q, N, D, embedding)
 
 
 def query_ranks(q, ent, target, known_side=None, when=None, qkey=None, kind="dot"):
@@ -253,26 +269,9 @@ def query_ranks(q, ent, target, known_side=None, when=None, qkey=None, kind="dot
     (Q, D), N = q.shape, ent.shape[0]
     if ent.shape[1] != D or target.numel() != Q:
         raise ValueError("query_ranks: q [Q, D], ent [N, D] and target [Q] expected")
-    keys = rowptr = members = gone_at = None
-    U = 0
-    if known_side is not None and known_side.keys.numel() > 0:
-        if when is None or when.numel() != Q or qkey is None or qkey.numel() != Q:
-            raise ValueError("query_ranks: a filtered call needs when [Q] and qkey [Q]")
-        k = known_side
-        qkey, when = qkey.long().contiguous(), when.int().contiguous()
-        require_hip(k.keys, k.rowptr, k.members, k.gone_at, qkey, when)
-        keys, rowptr, members, gone_at, U = k.keys, k.rowptr, k.members, k.gone_at, k.keys.numel()
-    else:
-        qkey = when = None
-    ranks = torch.empty(Q, dtype=torch.int64, device=q.device)
-    name = "mrg_rows_rank" if kind == "dot" else "mrg_transe_rank"
-    nbytes = getattr(load(), "mrg_distmult_rank_workspace_bytes" if kind == "dot" else "mrg_transe_rank_workspace_bytes")(Q, N, D)
-    if nbytes < 0:
-        check(int(nbytes), name)
-    ws = torch.empty(max(int(nbytes), 1), dtype=torch.uint8, device=q.device)
-    call(name, (ptr(q), ptr(ent), ptr(target), ptr(qkey), ptr(when), ptr(keys), ptr(rowptr), ptr(members), ptr(gone_at), U, Q, N, D,
-                ptr(ranks), ptr(ws), int(nbytes), stream_of(q)), nbytes=4 * (Q + N) * D, flops=2 * Q * N * D)
-    return ranks
+    side = _filter_side("query_ranks: a filtered call needs when [Q] and qkey [Q]", known_side, when, qkey, Q)
+    name, ws_name = ("mrg_rows_rank", "mrg_distmult_rank_workspace_bytes") if kind == "dot" else ("mrg_transe_rank", "mrg_transe_rank_workspace_bytes")
+    return _rank_call(name, ws_name, name, (q, ent, target), side, Q, N, D, q)
 
 
 def _both_passes(embedding, w, test, eval_bz, known, protocol):

@@ -66,8 +66,8 @@ from .cell_zero import (  # noqa: F401
 )
 from .scoring import (  # noqa: F401
     ScorePlan, _DistMult, distmult_score, distmult_scores_all, _TransE, transe_scores_all,
-    _DistMultBCE, distmult_bce_all, distmult_bce_mean, distmult_bce_dlogit, bce_default_col_chunk, dot_bce_all,
-    _TransEBCE, transe_bce_all, transe_bce_mean, transe_bce_dlogit,
+    _BCE1N, rows_bce_all, dot_bce_all, distmult_bce_all, distmult_bce_mean, distmult_bce_dlogit, bce_default_col_chunk,
+    transe_bce_all, transe_bce_mean, transe_bce_dlogit,
 )
 from .ccorr import (  # noqa: F401
     _CCorrRows, _Circulant, ccorr,

@@ -71,7 +71,7 @@ def distmult_scores_all(all_ent, sub_emb, rel_emb):
     return linear(compose("mult", sub_emb, rel_emb), all_ent, None, "sigmoid")
 
 
-BCE_COL_BLOCK = 7 * 32              # the sweep's column block (csrc/gemm_dispatch.hpp: RANK_NT tiles of 32)
+BCE_COL_BLOCK = 7 * 32              # the sweep's column block (csrc/sweep_host.hpp: RANK_NT tiles of 32)
 BCE_DL_BYTES = 64 << 20             # default bound of the backward's [B, col_chunk] logit-gradient slice
 
 
@@ -80,103 +80,155 @@ def bce_default_col_chunk(B):
     return max(BCE_COL_BLOCK, BCE_DL_BYTES // (4 * max(int(B), 1)) // BCE_COL_BLOCK * BCE_COL_BLOCK)
 
 
-def _bce_ws(B, cols, D, like):
-    nbytes = _ws_bytes("mrg_distmult_bce_workspace_bytes", B, cols, D)
+# The C entry points of the 1-N losses by score kind: "dot" (logit = q . entity, csrc/bce.hip) and "l1" (logit = gamma - ||q - entity||_1,
+# csrc/transe_1n.hip).  The "l1" calls take gamma in front of v_zero; everything else is the same argument list.
+_BCE_ENTRY = {"dot": ("mrg_distmult_bce_workspace_bytes", "mrg_distmult_bce_fwd", "mrg_distmult_bce_dlogit"),
+              "l1": ("mrg_transe_bce_workspace_bytes", "mrg_transe_bce_fwd", "mrg_transe_bce_dlogit")}
+
+
+def _checked_ws(name, B, cols, D, like):
+    nbytes = _ws_bytes(name, B, cols, D)
     if nbytes < 0:
-        check(int(nbytes), "mrg_distmult_bce_workspace_bytes")
+        check(int(nbytes), name)
     return _ws(nbytes, like), int(nbytes)
+
+
+def _bce_mean(kind, gamma, q, ent, li, qkey, v_zero, v_one):
+    ws_name, fwd, _ = _BCE_ENTRY[kind]
+    (B, D), N = q.shape, ent.shape[0]
+    loss = torch.empty((), dtype=torch.float32, device=q.device)
+    ws, nbytes = _checked_ws(ws_name, B, N, D, q)
+    values = (float(gamma), v_zero, v_one) if kind == "l1" else (v_zero, v_one)
+    call(fwd, (ptr(q), ptr(ent), ptr(qkey), ptr(li.keys), ptr(li.rowptr), ptr(li.objs), int(li.keys.numel()), *values, B, N, D,
+               ptr(loss), ptr(ws), nbytes, stream_of(q)),
+         nbytes=4 * (B + N) * D, flops=2 * B * N * D)
+    return loss
+
+
+def _bce_dlogit(kind, gamma, q, ent, li, qkey, v_zero, v_one, c0, c1, gscale, out):
+    ws_name, _, dlogit = _BCE_ENTRY[kind]
+    (B, D), N, nc = q.shape, ent.shape[0], c1 - c0
+    if out is None:
+        out = torch.empty(B * nc, dtype=torch.float32, device=q.device)
+    ws, nbytes = _checked_ws(ws_name, B, nc, D, q)
+    values = (float(gamma), v_zero, v_one) if kind == "l1" else (v_zero, v_one)
+    call(dlogit, (ptr(q), ptr(ent), ptr(qkey), ptr(li.keys), ptr(li.rowptr), ptr(li.objs), int(li.keys.numel()), *values, B, N, D,
+                  c0, c1, ptr(gscale), ptr(out), ptr(ws), nbytes, stream_of(q)),
+         nbytes=4 * (B + nc) * D + 4 * B * nc, flops=2 * B * nc * D)
+    return out[:B * nc].view(B, nc)
 
 
 def distmult_bce_mean(q, ent, label_index, qkey, v_zero, v_one):
     """mrg_distmult_bce_fwd, no autograd: mean over [B, N] of BCE(sigmoid(q ent^T), labels) as a float32 device scalar."""
-    li = label_index
-    B, D = q.shape
-    N = ent.shape[0]
-    loss = torch.empty((), dtype=torch.float32, device=q.device)
-    ws, nbytes = _bce_ws(B, N, D, q)
-    call("mrg_distmult_bce_fwd", (ptr(q), ptr(ent), ptr(qkey), ptr(li.keys), ptr(li.rowptr), ptr(li.objs), int(li.keys.numel()),
-                                  v_zero, v_one, B, N, D, ptr(loss), ptr(ws), nbytes, stream_of(q)),
-         nbytes=4 * (B + N) * D, flops=2 * B * N * D)
-    return loss
+    return _bce_mean("dot", None, q, ent, label_index, qkey, v_zero, v_one)
+
+
+def transe_bce_mean(obj, ent, gamma, label_index, qkey, v_zero, v_one):
+    """mrg_transe_bce_fwd, no autograd: mean over [B, N] of BCE(sigmoid(gamma - ||obj - ent||_1), labels) as a float32 device scalar."""
+    return _bce_mean("l1", gamma, obj, ent, label_index, qkey, v_zero, v_one)
 
 
 def distmult_bce_dlogit(q, ent, label_index, qkey, v_zero, v_one, c0, c1, gscale, out=None):
     """mrg_distmult_bce_dlogit, no autograd: the loss gradient with respect to the logits of the entities [c0, c1) as [B, c1 - c0],
     written into the first B * (c1 - c0) floats of `out` when given.  gscale: float32 [1] on the device (upstream gradient / (B N))."""
-    li = label_index
-    (B, D), N, nc = q.shape, ent.shape[0], c1 - c0
-    if out is None:
-        out = torch.empty(B * nc, dtype=torch.float32, device=q.device)
-    ws, nbytes = _bce_ws(B, nc, D, q)
-    call("mrg_distmult_bce_dlogit", (ptr(q), ptr(ent), ptr(qkey), ptr(li.keys), ptr(li.rowptr), ptr(li.objs), int(li.keys.numel()),
-                                     v_zero, v_one, B, N, D, c0, c1, ptr(gscale), ptr(out), ptr(ws), nbytes, stream_of(q)),
-         nbytes=4 * (B + nc) * D + 4 * B * nc, flops=2 * B * nc * D)
-    return out[:B * nc].view(B, nc)
+    return _bce_dlogit("dot", None, q, ent, label_index, qkey, v_zero, v_one, c0, c1, gscale, out)
 
 
-class _DistMultBCE(torch.autograd.Function):
-    """loss(q, ent) of distmult_bce_all.  Forward: one sweep that stores nothing per element.  Backward: per column chunk the logit
-    gradient slice dl [B, chunk] (mrg_distmult_bce_dlogit, the tile recomputed) and the two gradient GEMMs of `linear` on it:
-    g_q += dl ent[c0:c1] (mrg_linear_bwd_input, accumulating) and g_ent[c0:c1] = dl^T q (mrg_linear_fwd on the transposed operands)."""
+def transe_bce_dlogit(obj, ent, gamma, label_index, qkey, v_zero, v_one, c0, c1, gscale, out=None):
+    """mrg_transe_bce_dlogit, no autograd: the loss gradient with respect to x = gamma - dist of the entities [c0, c1) as [B, c1 - c0],
+    written into the first B * (c1 - c0) floats of `out` when given.  gscale: float32 [1] on the device (upstream gradient / (B N))."""
+    return _bce_dlogit("l1", gamma, obj, ent, label_index, qkey, v_zero, v_one, c0, c1, gscale, out)
+
+
+def _dot_chunk_bwd(q, ent, dl, c0, nc, g_q, g_ent, pre, st):
+    """One column chunk of the "dot" backward: the two gradient GEMMs of `linear` on dl [B, nc]: g_q += dl ent[c0:c1]
+    (mrg_linear_bwd_input, accumulating) and g_ent[c0:c1] = dl^T q (mrg_linear_fwd on the transposed operands).  pre: (q^T, the row
+    GEMM's workspace) when g_ent is wanted."""
+    (B, D), esz = q.shape, ent.element_size()
+    need_q, need_ent = g_q is not None, g_ent is not None
+    work = dict(nbytes=4 * B * (D + nc) + 4 * D * nc, flops=2 * B * D * nc)
+    ent_c = ctypes.c_void_p(ent.data_ptr() + c0 * D * esz)
+    # a wide chunk: both gradients run on the transposed slice dl^T [nc, B], as `linear`'s backward does for Nout = N >> rows
+    wide_q = need_q and nc > 1024 and B <= 1024 and (B <= 128 or (B % 4 == 0 and D % 4 == 0))
+    dlT = dl[:B * nc].view(B, nc).t().contiguous() if (need_ent or wide_q) else None
+    if wide_q:
+        # g_q (+)= dl ent[c0:c1] is a reduction over the chunk's entities into a [B, D] block, the shape of a weight gradient
+        # (rows := nc, gY := dl^T, X := ent[c0:c1]): the split-over-rows kernel spreads it over the chip, where the row GEMM
+        # would give the whole reduction to ceil(B / 128) workgroups
+        out = g_q if c0 == 0 else torch.empty_like(g_q)
+        ws = _ws(_ws_bytes("mrg_linear_bwd_weight_workspace_bytes", nc, D, B), q)
+        call("mrg_linear_bwd_weight", (ptr(dlT), ent_c, None, ptr(out), None, ptr(ws), nc, D, 0, B, st), **work)
+        if c0 > 0:
+            g_q += out
+    elif need_q:                  # g_q (+)= dl ent[c0:c1]
+        wt = _ws(_ws_bytes("mrg_linear_bwd_input_workspace_bytes", D, nc), q)
+        call("mrg_linear_bwd_input", (ptr(dl), ent_c, ptr(g_q), ptr(wt), B, D, nc, D, 1 if c0 > 0 else 0, st), **work)
+    if need_ent:
+        # g_ent[c0:c1] = dl^T q: a tall-skinny row GEMM over the transposed operands (the split-over-rows weight-gradient
+        # kernel keeps all of gW's row tiles in registers: it does not cover thousands of output rows, nor a chunk whose
+        # width is no multiple of 4)
+        qT, gws = pre
+        call("mrg_linear_fwd", (ptr(dlT), ptr(qT), None, ctypes.c_void_p(g_ent.data_ptr() + c0 * D * esz), ptr(gws), nc, B, D, 0, st),
+             **work)
+
+
+def _l1_chunk_bwd(obj, ent, dl, c0, nc, g_obj, g_ent, pre, st):
+    """One column chunk of the "l1" backward: mrg_transe_dist_bwd on dl [B, nc], the gradient with respect to gamma - dist:
+    g_ent[c0:c1] written, g_obj accumulated in chunk order.  No transpose."""
+    (B, D), esz = obj.shape, ent.element_size()
+    need_obj, need_ent = g_obj is not None, g_ent is not None
+    call("mrg_transe_dist_bwd", (ctypes.c_void_p(ent.data_ptr() + c0 * D * esz), ptr(obj), ptr(dl), nc,
+                                 ctypes.c_void_p(g_ent.data_ptr() + c0 * D * esz) if need_ent else None, ptr(g_obj),
+                                 1 if c0 > 0 else 0, B, nc, D, st),
+         nbytes=4 * (B * nc + (B + nc) * D), flops=(int(need_obj) + int(need_ent)) * 2 * B * nc * D)
+
+
+class _BCE1N(torch.autograd.Function):
+    """loss(q, ent) of the 1-N losses, kind "dot" or "l1".  Forward: one sweep that stores nothing per element.  Backward: per column
+    chunk the logit gradient slice dl [B, chunk] (mrg_distmult_bce_dlogit / mrg_transe_bce_dlogit, the tile recomputed) and the
+    kind's work on it (_dot_chunk_bwd / _l1_chunk_bwd)."""
 
     @staticmethod
-    def forward(ctx, q, ent, label_index, qkey, v_zero, v_one, col_chunk):
+    def forward(ctx, kind, gamma, q, ent, label_index, qkey, v_zero, v_one, col_chunk):
         q, ent = f32c(q), f32c(ent)
         li = label_index
         require_hip(q, ent, qkey, li.keys, li.rowptr, li.objs)
+        ctx.kind, ctx.gamma = kind, None if gamma is None else float(gamma)
         ctx.li, ctx.v, ctx.col_chunk = li, (v_zero, v_one), col_chunk
         ctx.save_for_backward(q, ent, qkey)
-        return distmult_bce_mean(q, ent, li, qkey, v_zero, v_one)
+        return _bce_mean(kind, gamma, q, ent, li, qkey, v_zero, v_one)
 
     @staticmethod
     def backward(ctx, g):
         q, ent, qkey = ctx.saved_tensors
-        li, (v_zero, v_one), step = ctx.li, ctx.v, ctx.col_chunk
+        kind, li, (v_zero, v_one), step = ctx.kind, ctx.li, ctx.v, ctx.col_chunk
         (B, D), N, st = q.shape, ent.shape[0], stream_of(q)
         step = min(step, N)
-        need_q, need_ent = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        need_q, need_ent = ctx.needs_input_grad[2], ctx.needs_input_grad[3]
         gscale = (g.detach().float().reshape(1) / float(B * N)).contiguous()          # stays on the device: no host synchronisation
         dl = torch.empty(B * step, dtype=torch.float32, device=q.device)               # ONE slice, reused by every chunk
         g_q = torch.empty_like(q) if need_q else None
         g_ent = torch.empty_like(ent) if need_ent else None
-        esz = ent.element_size()
-        if need_ent:
-            qT, gws = q.t().contiguous(), _ws(_ws_bytes("mrg_gemm_workspace_bytes", B, D), q)
+        pre = None
+        if kind == "dot" and need_ent:
+            pre = q.t().contiguous(), _ws(_ws_bytes("mrg_gemm_workspace_bytes", B, D), q)
+        chunk_bwd = _dot_chunk_bwd if kind == "dot" else _l1_chunk_bwd
         for c0 in range(0, N, step):
             c1 = min(N, c0 + step)
-            nc = c1 - c0
-            distmult_bce_dlogit(q, ent, li, qkey, v_zero, v_one, c0, c1, gscale, out=dl)
-            work = dict(nbytes=4 * B * (D + nc) + 4 * D * nc, flops=2 * B * D * nc)
-            ent_c = ctypes.c_void_p(ent.data_ptr() + c0 * D * esz)
-            # a wide chunk: both gradients run on the transposed slice dl^T [nc, B], as `linear`'s backward does for Nout = N >> rows
-            wide_q = need_q and nc > 1024 and B <= 1024 and (B <= 128 or (B % 4 == 0 and D % 4 == 0))
-            dlT = dl[:B * nc].view(B, nc).t().contiguous() if (need_ent or wide_q) else None
-            if wide_q:
-                # g_q (+)= dl ent[c0:c1] is a reduction over the chunk's entities into a [B, D] block, the shape of a weight gradient
-                # (rows := nc, gY := dl^T, X := ent[c0:c1]): the split-over-rows kernel spreads it over the chip, where the row GEMM
-                # would give the whole reduction to ceil(B / 128) workgroups
-                out = g_q if c0 == 0 else torch.empty_like(g_q)
-                ws = _ws(_ws_bytes("mrg_linear_bwd_weight_workspace_bytes", nc, D, B), q)
-                call("mrg_linear_bwd_weight", (ptr(dlT), ent_c, None, ptr(out), None, ptr(ws), nc, D, 0, B, st), **work)
-                if c0 > 0:
-                    g_q += out
-            elif need_q:                  # g_q (+)= dl ent[c0:c1]
-                wt = _ws(_ws_bytes("mrg_linear_bwd_input_workspace_bytes", D, nc), q)
-                call("mrg_linear_bwd_input", (ptr(dl), ent_c, ptr(g_q), ptr(wt), B, D, nc, D, 1 if c0 > 0 else 0, st), **work)
-            if need_ent:
-                # g_ent[c0:c1] = dl^T q: a tall-skinny row GEMM over the transposed operands (the split-over-rows weight-gradient
-                # kernel keeps all of gW's row tiles in registers: it does not cover thousands of output rows, nor a chunk whose
-                # width is no multiple of 4)
-                call("mrg_linear_fwd", (ptr(dlT), ptr(qT), None, ctypes.c_void_p(g_ent.data_ptr() + c0 * D * esz), ptr(gws), nc, B, D, 0, st),
-                     **work)
-        return g_q, g_ent, None, None, None, None, None
+            _bce_dlogit(kind, ctx.gamma, q, ent, li, qkey, v_zero, v_one, c0, c1, gscale, dl)
+            chunk_bwd(q, ent, dl, c0, c1 - c0, g_q, g_ent, pre, st)
+        return None, None, g_q, g_ent, None, None, None, None, None
+
+
+def _require_cuda(what, tensors):
+    for t in tensors:
+        if not t.is_cuda:
+            raise MrgnasError(f"{what} runs on a HIP device (no CPU fallback); got a tensor on " + str(t.device))
 
 
 def _bce_all_args(what, tensors, B, N, label_index, subj, rel, label_smooth, col_chunk):
     """The checks and the derived arguments the 1-N losses share: (qkey, v_zero, v_one, col_chunk)."""
-    for t in tensors:
-        if not t.is_cuda:
-            raise MrgnasError(f"{what} runs on a HIP device (no CPU fallback); got a tensor on " + str(t.device))
+    _require_cuda(what, tensors)
     if B == 0 or N == 0 or N != label_index.num_ent or subj.numel() != B or rel.numel() != B:
         raise ValueError(f"{what}: all_ent [num_ent, D], query rows [B, D], subj / rel [B] with B > 0 expected")
     if col_chunk is None:
@@ -189,15 +241,21 @@ def _bce_all_args(what, tensors, B, N, label_index, subj, rel, label_smooth, col
     return qkey, v_zero, v_one, col_chunk
 
 
-def dot_bce_all(all_ent, q, label_index, subj, rel, label_smooth=0.0, col_chunk=None, _what="dot_bce_all"):
-    """distmult_bce_all from the point where the query rows exist: the mean over [B, N] of BCELoss(sigmoid(q all_ent^T),
-    label_index.labels(subj, rel, label_smooth)) for rows q [B, D] the caller formed -- DistMult's sub * rel, ConvE's hidden vector
-    after BN2 + ReLU (the scorers' ``query``).  Same kernels, same memory, no host synchronisation."""
+def rows_bce_all(kind, gamma, all_ent, q, label_index, subj, rel, label_smooth=0.0, col_chunk=None, _what="rows_bce_all"):
+    """The 1-N losses from the point where the query rows exist (the scorers' ``query``): the mean over [B, N] of BCELoss(sigmoid(x),
+    label_index.labels(subj, rel, label_smooth)) for rows q [B, D] the caller formed, with x = q all_ent^T for kind "dot" (DistMult's
+    sub * rel, ConvE's hidden vector after BN2 + ReLU; gamma unused) and x = gamma - ||q - all_ent||_1 for kind "l1" (TransE's
+    sub + rel).  No [B, N] tensor, no host synchronisation."""
     if q.dim() != 2 or all_ent.dim() != 2 or q.shape[1] != all_ent.shape[1]:
         raise ValueError(f"{_what}: all_ent [num_ent, D] and query rows [B, D] expected")
     B, N = int(q.shape[0]), int(all_ent.shape[0])
     qkey, v_zero, v_one, col_chunk = _bce_all_args(_what, (all_ent, q, subj, rel), B, N, label_index, subj, rel, label_smooth, col_chunk)
-    return _DistMultBCE.apply(q, all_ent, label_index, qkey, v_zero, v_one, col_chunk)
+    return _BCE1N.apply(kind, gamma, q, all_ent, label_index, qkey, v_zero, v_one, col_chunk)
+
+
+def dot_bce_all(all_ent, q, label_index, subj, rel, label_smooth=0.0, col_chunk=None, _what="dot_bce_all"):
+    """distmult_bce_all from the point where the query rows exist: rows_bce_all for the "dot" scorers.  Same kernels, same memory."""
+    return rows_bce_all("dot", None, all_ent, q, label_index, subj, rel, label_smooth, col_chunk, _what=_what)
 
 
 def distmult_bce_all(all_ent, sub_emb, rel_emb, label_index, subj, rel, label_smooth=0.0, col_chunk=None):
@@ -205,12 +263,24 @@ def distmult_bce_all(all_ent, sub_emb, rel_emb, label_index, subj, rel, label_sm
     of BCELoss(sigmoid((sub_emb * rel_emb) all_ent^T), label_index.labels(subj, rel, label_smooth)) as a float32 scalar, with no [B, N]
     tensor -- neither the labels, nor the predictions, nor the loss terms.  The backward holds one [B, col_chunk] slice of the logit
     gradient and its transpose (default: bce_default_col_chunk(B)).  label_index: sampler.LabelIndex on the same device.  No host synchronisation."""
-    for t in (all_ent, sub_emb, rel_emb, subj, rel):
-        if not t.is_cuda:
-            raise MrgnasError("distmult_bce_all runs on a HIP device (no CPU fallback); got a tensor on " + str(t.device))
+    _require_cuda("distmult_bce_all", (all_ent, sub_emb, rel_emb, subj, rel))
     if int(sub_emb.shape[0]) == 0:
         raise ValueError("distmult_bce_all: all_ent [num_ent, D], sub_emb / rel_emb [B, D], subj / rel [B] with B > 0 expected")
     return dot_bce_all(all_ent, compose("mult", sub_emb, rel_emb), label_index, subj, rel, label_smooth, col_chunk, _what="distmult_bce_all")
+
+
+def transe_bce_all(all_ent, sub_emb, rel_emb, gamma, label_index, subj, rel, label_smooth=0.0, col_chunk=None):
+    """The fixed-genotype driver's training loss with sf_TransE_op: the mean over [B, N] of BCELoss(sigmoid(gamma - ||sub_emb + rel_emb -
+    all_ent||_1), label_index.labels(subj, rel, label_smooth)) as a float32 scalar with no [B, N] tensor (csrc/transe_1n.hip).  The
+    backward holds one [B, col_chunk] slice (default: bce_default_col_chunk(B)) and no transpose; the gradient of obj = sub_emb + rel_emb
+    goes to both.  No host synchronisation."""
+    if sub_emb.dim() != 2 or sub_emb.shape != rel_emb.shape or all_ent.dim() != 2 or sub_emb.shape[1] != all_ent.shape[1]:
+        raise ValueError("transe_bce_all: all_ent [num_ent, D] and sub_emb / rel_emb [B, D] expected")
+    _require_cuda("transe_bce_all", (all_ent, sub_emb, rel_emb, subj, rel))
+    if int(sub_emb.shape[0]) == 0:
+        raise ValueError("transe_bce_all: all_ent [num_ent, D], query rows [B, D], subj / rel [B] with B > 0 expected")
+    return rows_bce_all("l1", gamma, all_ent, compose("add", sub_emb, rel_emb), label_index, subj, rel, label_smooth, col_chunk,
+                        _what="transe_bce_all")
 
 
 class _TransE(torch.autograd.Function):
@@ -241,86 +311,3 @@ class _TransE(torch.autograd.Function):
 def transe_scores_all(all_ent, sub_emb, rel_emb, gamma):
     """sf_TransE_op (reference models/operations_lp.py:101-112): sigmoid(gamma - ||sub + rel - ent||_1) for all entities."""
     return _TransE.apply(all_ent, sub_emb, rel_emb, gamma)
-
-
-def _l1_ws(name, B, cols, D, like):
-    nbytes = _ws_bytes(name, B, cols, D)
-    if nbytes < 0:
-        check(int(nbytes), name)
-    return _ws(nbytes, like), int(nbytes)
-
-
-def transe_bce_mean(obj, ent, gamma, label_index, qkey, v_zero, v_one):
-    """mrg_transe_bce_fwd, no autograd: mean over [B, N] of BCE(sigmoid(gamma - ||obj - ent||_1), labels) as a float32 device scalar."""
-    li = label_index
-    (B, D), N = obj.shape, ent.shape[0]
-    loss = torch.empty((), dtype=torch.float32, device=obj.device)
-    ws, nbytes = _l1_ws("mrg_transe_bce_workspace_bytes", B, N, D, obj)
-    call("mrg_transe_bce_fwd", (ptr(obj), ptr(ent), ptr(qkey), ptr(li.keys), ptr(li.rowptr), ptr(li.objs), int(li.keys.numel()),
-                                float(gamma), v_zero, v_one, B, N, D, ptr(loss), ptr(ws), nbytes, stream_of(obj)),
-         nbytes=4 * (B + N) * D, flops=2 * B * N * D)
-    return loss
-
-
-def transe_bce_dlogit(obj, ent, gamma, label_index, qkey, v_zero, v_one, c0, c1, gscale, out=None):
-    """mrg_transe_bce_dlogit, no autograd: the loss gradient with respect to x = gamma - dist of the entities [c0, c1) as [B, c1 - c0],
-    written into the first B * (c1 - c0) floats of `out` when given.  gscale: float32 [1] on the device (upstream gradient / (B N))."""
-    li = label_index
-    (B, D), N, nc = obj.shape, ent.shape[0], c1 - c0
-    if out is None:
-        out = torch.empty(B * nc, dtype=torch.float32, device=obj.device)
-    ws, nbytes = _l1_ws("mrg_transe_bce_workspace_bytes", B, nc, D, obj)
-    call("mrg_transe_bce_dlogit", (ptr(obj), ptr(ent), ptr(qkey), ptr(li.keys), ptr(li.rowptr), ptr(li.objs), int(li.keys.numel()),
-                                   float(gamma), v_zero, v_one, B, N, D, c0, c1, ptr(gscale), ptr(out), ptr(ws), nbytes, stream_of(obj)),
-         nbytes=4 * (B + nc) * D + 4 * B * nc, flops=2 * B * nc * D)
-    return out[:B * nc].view(B, nc)
-
-
-class _TransEBCE(torch.autograd.Function):
-    """loss(obj, ent) of transe_bce_all, shaped like _DistMultBCE.  Forward: one sweep that stores nothing per element.  Backward: per
-    column chunk the slice dl [B, chunk] of the gradient with respect to gamma - dist (mrg_transe_bce_dlogit, the tile recomputed) and
-    mrg_transe_dist_bwd on it: g_ent[c0:c1] written, g_obj accumulated in chunk order.  One dl slice, no transpose."""
-
-    @staticmethod
-    def forward(ctx, obj, ent, gamma, label_index, qkey, v_zero, v_one, col_chunk):
-        obj, ent = f32c(obj), f32c(ent)
-        li = label_index
-        require_hip(obj, ent, qkey, li.keys, li.rowptr, li.objs)
-        ctx.li, ctx.v, ctx.col_chunk, ctx.gamma = li, (v_zero, v_one), col_chunk, float(gamma)
-        ctx.save_for_backward(obj, ent, qkey)
-        return transe_bce_mean(obj, ent, gamma, li, qkey, v_zero, v_one)
-
-    @staticmethod
-    def backward(ctx, g):
-        obj, ent, qkey = ctx.saved_tensors
-        li, (v_zero, v_one), step = ctx.li, ctx.v, ctx.col_chunk
-        (B, D), N, st = obj.shape, ent.shape[0], stream_of(obj)
-        step = min(step, N)
-        need_obj, need_ent = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
-        gscale = (g.detach().float().reshape(1) / float(B * N)).contiguous()          # stays on the device: no host synchronisation
-        dl = torch.empty(B * step, dtype=torch.float32, device=obj.device)             # ONE slice, reused by every chunk
-        g_obj = torch.empty_like(obj) if need_obj else None
-        g_ent = torch.empty_like(ent) if need_ent else None
-        esz = ent.element_size()
-        for c0 in range(0, N, step):
-            c1 = min(N, c0 + step)
-            nc = c1 - c0
-            transe_bce_dlogit(obj, ent, ctx.gamma, li, qkey, v_zero, v_one, c0, c1, gscale, out=dl)
-            call("mrg_transe_dist_bwd", (ctypes.c_void_p(ent.data_ptr() + c0 * D * esz), ptr(obj), ptr(dl), nc,
-                                         ctypes.c_void_p(g_ent.data_ptr() + c0 * D * esz) if need_ent else None, ptr(g_obj),
-                                         1 if c0 > 0 else 0, B, nc, D, st),
-                 nbytes=4 * (B * nc + (B + nc) * D), flops=(int(need_obj) + int(need_ent)) * 2 * B * nc * D)
-        return g_obj, g_ent, None, None, None, None, None, None
-
-
-def transe_bce_all(all_ent, sub_emb, rel_emb, gamma, label_index, subj, rel, label_smooth=0.0, col_chunk=None):
-    """The fixed-genotype driver's training loss with sf_TransE_op: the mean over [B, N] of BCELoss(sigmoid(gamma - ||sub_emb + rel_emb -
-    all_ent||_1), label_index.labels(subj, rel, label_smooth)) as a float32 scalar with no [B, N] tensor (csrc/transe_1n.hip).  The
-    backward holds one [B, col_chunk] slice (default: bce_default_col_chunk(B)) and no transpose; the gradient of obj = sub_emb + rel_emb
-    goes to both.  No host synchronisation."""
-    if sub_emb.dim() != 2 or sub_emb.shape != rel_emb.shape or all_ent.dim() != 2 or sub_emb.shape[1] != all_ent.shape[1]:
-        raise ValueError("transe_bce_all: all_ent [num_ent, D] and sub_emb / rel_emb [B, D] expected")
-    B, N = int(sub_emb.shape[0]), int(all_ent.shape[0])
-    qkey, v_zero, v_one, col_chunk = _bce_all_args("transe_bce_all", (all_ent, sub_emb, rel_emb, subj, rel), B, N, label_index, subj, rel,
-                                                   label_smooth, col_chunk)
-    return _TransEBCE.apply(compose("add", sub_emb, rel_emb), all_ent, gamma, label_index, qkey, v_zero, v_one, col_chunk)

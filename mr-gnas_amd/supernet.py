@@ -452,14 +452,12 @@ class FixedNetwork(nn.Module):
             raise MrgnasError(f"loss_fused covers the DistMult scorer only; this network scores with {type(self.score_func).__name__}")
         if not self.embedding_h.weight.is_cuda:
             raise MrgnasError("loss_fused runs on a HIP device (no CPU fallback); the network is on " + str(self.embedding_h.weight.device))
-        if not self.embedding_h.weight.is_cuda:
-            raise MrgnasError("loss_fused runs on a HIP device (no CPU fallback); the network is on " + str(self.embedding_h.weight.device))
         return self.loss_1n(g, subj, rel, label_index, label_smooth)
 
     def loss_1n(self, g, subj, rel, label_index, label_smooth=0.0, col_chunk=None):
         """loss_fused for every scorer that follows the scorer protocol (operations_lp: ``query`` and ``score_kind``): one embed(g), the
-        query rows q = score_func.query(ent[subj], rel_emb[rel]), then functional.dot_bce_all (DistMult, ConvE) or
-        functional.transe_bce_all on them.  No [B, N] tensor; HIP only."""
+        query rows q = score_func.query(ent[subj], rel_emb[rel]), then functional.rows_bce_all on them by the scorer's kind ("dot":
+        DistMult, ConvE; "l1": TransE with its gamma).  No [B, N] tensor; HIP only."""
         sf = self.score_func
         if not hasattr(sf, "query") or getattr(sf, "score_kind", None) not in ("dot", "l1"):
             raise MrgnasError(f"loss_1n needs a scorer with query() and a score_kind of 'dot' or 'l1'; this network scores with {type(sf).__name__}")
@@ -467,6 +465,5 @@ class FixedNetwork(nn.Module):
             raise MrgnasError("loss_1n runs on a HIP device (no CPU fallback); the network is on " + str(self.embedding_h.weight.device))
         with K.deferred_counters():
             ent, rel_emb = self.embed(g)
-            if sf.score_kind == "l1":
-                return K.transe_bce_all(ent, ent[subj], rel_emb[rel], sf.gamma, label_index, subj, rel, label_smooth, col_chunk)
-            return K.dot_bce_all(ent, sf.query(ent[subj], rel_emb[rel]), label_index, subj, rel, label_smooth, col_chunk)
+            q = sf.query(ent[subj], rel_emb[rel])
+            return K.rows_bce_all(sf.score_kind, getattr(sf, "gamma", None), ent, q, label_index, subj, rel, label_smooth, col_chunk)

@@ -103,9 +103,10 @@ def check_against_f64(got, ref, what):
 
 
 # every B of {1, 127, 129, 257} and every N of {1, 33, 224, 225, 449} with the split core (D = 52, 64, 200) and with the exact core
-# (D = 4: vectorised loads, D = 50: plain loads)
+# (D = 4: vectorised loads, D = 50: plain loads); N = 28 672 + 33 sweeps a second column block (csrc/sweep_host.hpp: BCE_COLS) on each
+# core, so the partials of two launches are added
 SHAPES = [(1, 449, 52), (127, 33, 64), (129, 224, 200), (257, 225, 52), (129, 1, 64), (127, 449, 200),
-          (1, 225, 4), (127, 449, 50), (129, 33, 4), (257, 224, 50), (127, 1, 4)]
+          (1, 225, 4), (127, 449, 50), (129, 33, 4), (257, 224, 50), (127, 1, 4), (5, 28672 + 33, 4), (5, 28672 + 33, 52)]
 
 
 # label smoothing 0.1 leaves labels in [0, 1] from N = 10 on (0.9 y + 1 / N: at N = 1 the labels are 1.0 and 1.9, which

@@ -98,8 +98,10 @@ def check_against_f64(got, ref, what):
 
 
 # ---- TransE: loss and gradients ------------------------------------------------------------------------------------------------------
-# every B of {1, 63, 65, 129}, every N of {1, 63, 64, 65, 449}, every D of {1, 31, 33, 64, 200} (D = 64, 200: float4 staging)
-SHAPES = [(1, 449, 33), (63, 63, 64), (65, 64, 200), (129, 65, 31), (129, 1, 1), (63, 449, 200), (65, 65, 1), (1, 64, 31)]
+# every B of {1, 63, 65, 129}, every N of {1, 63, 64, 65, 449}, every D of {1, 31, 33, 64, 200} (D = 64, 200: float4 staging);
+# N = 28 672 + 65 sweeps a second column block (csrc/sweep_host.hpp: BCE_COLS) with both kinds of staging
+SHAPES = [(1, 449, 33), (63, 63, 64), (65, 64, 200), (129, 65, 31), (129, 1, 1), (63, 449, 200), (65, 65, 1), (1, 64, 31),
+          (5, 28672 + 65, 4), (5, 28672 + 65, 33)]
 # label smoothing 0.1 for N >= 10 only: below, the smoothed labels leave [0, 1] and torch's binary_cross_entropy, the dense path's
 # loss, rejects them (tests/test_fused_bce_gpu.py)
 CASES = [(B, N, D, ls) for B, N, D in SHAPES for ls in (0.0, 0.1) if ls == 0.0 or N >= 10]
@@ -292,8 +294,8 @@ def l1_ranks(c, filtered=True):
     return EV.query_ranks(c["obj"], c["ent"], c["t"], kind="l1").cpu()
 
 
-@pytest.mark.parametrize("D", [1, 33, 200])
-@pytest.mark.parametrize("N", [1, 63, 64, 65, 449])
+# (N = 28 672 + 65: the L1 rank sweep goes through a second column block)
+@pytest.mark.parametrize("N,D", [(N, D) for N in (1, 63, 64, 65, 449) for D in (1, 33, 200)] + [(28672 + 65, 1), (28672 + 65, 33)])
 def test_transe_dyadic_ranks_are_exact(N, D):
     for Q in (1, 63, 65, 300):
         c = _dyadic_case(Q, N, D)
