@@ -34,7 +34,7 @@
 extern "C" {
 #endif
 
-#define MRG_ABI_VERSION 23   /* 23 (addition, no bump): mrg_rows_rank, mrg_transe_bce_fwd / _dlogit / _workspace_bytes, mrg_transe_dist_bwd, mrg_transe_rank / _workspace_bytes (1-N loss and ranks of ConvE and TransE without [B, N] tensors); 23 (addition, no bump: nothing existing changed, and tests pin the number): mrg_distmult_rank, mrg_distmult_rank_workspace_bytes (raw / filtered DistMult ranks as a row GEMM with a counting epilogue); 23: mrg_gemm_set_epilogue removed (the row-order and transposed-accumulator store orders of the split-core row GEMM, measured slower, left the library; accumulator-order stores remain), mrg_gemm_set_wide8 and mrg_gemm_set_small take 0 or 1 only; 22: mrg_cand_linear_fwd, mrg_cand_linear_bwd_input, mrg_cand_linear_colsum_blocks, mrg_cand_linear_workspace_bytes (the candidate Linears of one node-classification MixedOp in one launch, BatchNorm sums included); 21: mrg_adam_step (multi-tensor Adam over the pointer tables of mrg_clip_sgd_step, two launches; per-tensor step counts and lr in device memory); 20: BatchNorm sums formed by a candidate's producer: mrg_gated_branch.given / given_n / given_stride (mrg_mix_stats_coef skips the sweep over such a candidate), mrg_dense_filter3_colsum_blocks, mrg_dense_filter_fwd3_colsum, mrg_gate_row_colsum_blocks, mrg_gate_row_fwd_colsum; 19: mrg_seg_std_workspace_bytes, mrg_seg_std_fwd, mrg_seg_std_bwd (a_std, the standard-deviation aggregator of the node-classification task); 18: mrg_conve_* (the ConvE feature path: BN0 statistics, conv, BN1, split-K fc and their gradients, stacked or interleaved image layout); 17: mrg_ccorr_rows, mrg_ccorr_matrix, mrg_ccorr_matrix_grad (standalone circular correlation: per-row kernel, and the circulant of a shared row with its gradient fold for the row GEMM); 16: mrg_set_stream_blocks, mrg_gate_collapse and mrg_gate_param_grad removed (the streaming grid bound is fixed; the three-segment forms remain); 15: mrg_gated_branch.valid_rows and the valid_rows argument of mrg_mix_finalize_bwd / mrg_zero_* except colstats (the device row count of a static step graph, passed per call instead of the process-wide registry of 13), mrg_linear_bwd_weight_share (the weight gradient of one range of a grouped launch, instead of the process-wide setter of 14); 14: mrg_clip_sgd_step, mrg_optim_chunk (clip_grad_norm_ + SGD with momentum over every parameter tensor in three launches), mrg_gated_branch.act (tanh behind the BatchNorm: CompGraphConv's tail on the epilogue kernels), mrg_gemm_set_small (few-row products on two-tile column blocks), a weight-gradient share setter, mrg_segmax_bwd_input (a_max's input gradient without a dense product); 13: a registry of device-side row counts (the sampled search step as one replayable HIP graph), mrg_seg_reduce_bwd_ordered (aggregator backward walked in destination order), mrg_gemm_set_q (the 16 x 16 x 32 row GEMM at three workgroups per CU for 129..224 output columns); 12: mrg_act_grad_transpose (the [B, N] scorer's output gradient, activation folded in, as [N, B] rows); 11: mrg_gemm_set_wide8 (eight-tile column block for D = 256); 10: mrg_gemm_set_epilogue(2) (transposed accumulators: a tested comparison point); 9: mrg_gated_branch (the MixedOp epilogue recomputes f_dense_comp's output from its gate and f_sparse_comp's from its row factor), mrg_gate_row_fwd / _bwd, mrg_sum_rows_gather, mrg_wgrad_set_variant, mrg_dense_filter_fwd3 out == NULL; 8: mrg_zero_* (cell-zero MixedOp recomputed from the tables), mrg_linear_bwd_input3_pair, mrg_sample_edge_neighborhood; 7: mrg_gemm_set_epilogue (row-order stores of the split-core row GEMM), mrg_set_stream_blocks, mrg_gemm_set_mode(2); 6: fused a_mean (run-sum epilogue, heads reducer, bit-mask backward), mrg_mix_stats_coef; 5: three-segment dense filter entry points; 4: mrg_linear_relu_segmax_fwd (fused a_max); 3: device graph / plan builders, samplers, [B, N] scorers, ranking; 2: GEMM workspaces, span_gcs ext_scal */
+#define MRG_ABI_VERSION 23   /* 23 (addition, no bump): mrg_linear_bwd_input_acc2, mrg_linear_bwd_input3_acc2, mrg_linear_bwd_input3_pair_acc2, mrg_segmax_bwd_input_chain, mrg_gate_row_bwd_acc (the gradient fan-in chain: a reader adds the running sum of the other readers' gradients in its own last store); 23 (addition, no bump): mrg_rows_rank, mrg_transe_bce_fwd / _dlogit / _workspace_bytes, mrg_transe_dist_bwd, mrg_transe_rank / _workspace_bytes (1-N loss and ranks of ConvE and TransE without [B, N] tensors); 23 (addition, no bump: nothing existing changed, and tests pin the number): mrg_distmult_rank, mrg_distmult_rank_workspace_bytes (raw / filtered DistMult ranks as a row GEMM with a counting epilogue); 23: mrg_gemm_set_epilogue removed (the row-order and transposed-accumulator store orders of the split-core row GEMM, measured slower, left the library; accumulator-order stores remain), mrg_gemm_set_wide8 and mrg_gemm_set_small take 0 or 1 only; 22: mrg_cand_linear_fwd, mrg_cand_linear_bwd_input, mrg_cand_linear_colsum_blocks, mrg_cand_linear_workspace_bytes (the candidate Linears of one node-classification MixedOp in one launch, BatchNorm sums included); 21: mrg_adam_step (multi-tensor Adam over the pointer tables of mrg_clip_sgd_step, two launches; per-tensor step counts and lr in device memory); 20: BatchNorm sums formed by a candidate's producer: mrg_gated_branch.given / given_n / given_stride (mrg_mix_stats_coef skips the sweep over such a candidate), mrg_dense_filter3_colsum_blocks, mrg_dense_filter_fwd3_colsum, mrg_gate_row_colsum_blocks, mrg_gate_row_fwd_colsum; 19: mrg_seg_std_workspace_bytes, mrg_seg_std_fwd, mrg_seg_std_bwd (a_std, the standard-deviation aggregator of the node-classification task); 18: mrg_conve_* (the ConvE feature path: BN0 statistics, conv, BN1, split-K fc and their gradients, stacked or interleaved image layout); 17: mrg_ccorr_rows, mrg_ccorr_matrix, mrg_ccorr_matrix_grad (standalone circular correlation: per-row kernel, and the circulant of a shared row with its gradient fold for the row GEMM); 16: mrg_set_stream_blocks, mrg_gate_collapse and mrg_gate_param_grad removed (the streaming grid bound is fixed; the three-segment forms remain); 15: mrg_gated_branch.valid_rows and the valid_rows argument of mrg_mix_finalize_bwd / mrg_zero_* except colstats (the device row count of a static step graph, passed per call instead of the process-wide registry of 13), mrg_linear_bwd_weight_share (the weight gradient of one range of a grouped launch, instead of the process-wide setter of 14); 14: mrg_clip_sgd_step, mrg_optim_chunk (clip_grad_norm_ + SGD with momentum over every parameter tensor in three launches), mrg_gated_branch.act (tanh behind the BatchNorm: CompGraphConv's tail on the epilogue kernels), mrg_gemm_set_small (few-row products on two-tile column blocks), a weight-gradient share setter, mrg_segmax_bwd_input (a_max's input gradient without a dense product); 13: a registry of device-side row counts (the sampled search step as one replayable HIP graph), mrg_seg_reduce_bwd_ordered (aggregator backward walked in destination order), mrg_gemm_set_q (the 16 x 16 x 32 row GEMM at three workgroups per CU for 129..224 output columns); 12: mrg_act_grad_transpose (the [B, N] scorer's output gradient, activation folded in, as [N, B] rows); 11: mrg_gemm_set_wide8 (eight-tile column block for D = 256); 10: mrg_gemm_set_epilogue(2) (transposed accumulators: a tested comparison point); 9: mrg_gated_branch (the MixedOp epilogue recomputes f_dense_comp's output from its gate and f_sparse_comp's from its row factor), mrg_gate_row_fwd / _bwd, mrg_sum_rows_gather, mrg_wgrad_set_variant, mrg_dense_filter_fwd3 out == NULL; 8: mrg_zero_* (cell-zero MixedOp recomputed from the tables), mrg_linear_bwd_input3_pair, mrg_sample_edge_neighborhood; 7: mrg_gemm_set_epilogue (row-order stores of the split-core row GEMM), mrg_set_stream_blocks, mrg_gemm_set_mode(2); 6: fused a_mean (run-sum epilogue, heads reducer, bit-mask backward), mrg_mix_stats_coef; 5: three-segment dense filter entry points; 4: mrg_linear_relu_segmax_fwd (fused a_max); 3: device graph / plan builders, samplers, [B, N] scorers, ranking; 2: GEMM workspaces, span_gcs ext_scal */
 
 #define MRG_OK            0
 #define MRG_E_NULLPTR    -1   /* a required pointer is NULL */
@@ -147,6 +147,10 @@ int mrg_gate_row_fwd_colsum(const float *s, const float *s_in, const float *norm
  * ws: mrg_gate_bwd_workspace_bytes(M, D). */
 int mrg_gate_row_bwd(const float *q, const float *hvec, const float *s, const float *s_in, const float *uvc, float *gs_in, float *d_uvc,
                      void *ws, int64_t b0, int64_t b1, int64_t M, int D, void *stream);
+/* The same as a member of a running gradient fan-in sum (see "gradient fan-in chain" below): gs_in = total + dz_r * v instead of
+ * dz_r * v.  s_in and total [M, D] must be given; total may be gs_in itself (in place). */
+int mrg_gate_row_bwd_acc(const float *q, const float *hvec, const float *s, const float *s_in, const float *uvc, float *gs_in, float *d_uvc,
+                         void *ws, int64_t b0, int64_t b1, int64_t M, int D, void *stream, const float *total);
 
 /* ---- a4 / a5 / a6: destination-segmented reducers --------------------------
  * block.update_all(fn.copy_edge('msg_e','m'), fn.max|sum|mean('m','h')) + residual
@@ -195,6 +199,16 @@ int mrg_seg_reduce_bwd_ordered(int mode, const float *gout, const int32_t *dst, 
 int mrg_segmax_bwd_input_ok(int D, int Kin);
 int mrg_segmax_bwd_input(const float *gout, const float *mx, const int32_t *dst, const int32_t *arg, const float *W, float *gmsg,
                          float *gx, const int32_t *order, int64_t E, int64_t N, int D, int Kin, void *stream);
+/* The same as the member of a gradient fan-in chain that closes it: gx has E + N rows (D == Kin) and leaves as
+ *   gx[e]     = (gh[dst[e]] + total[e]) + sum_c gmsg[e][c] * W[c][k]      e < E
+ *   gx[E + n] = (gself[n] + total[E + n]) + gout[n]                       n < N   (the aggregator's residual self rows)
+ * total [E + N, Kin]: the running sum of the other readers' gradients; gh / gself [N, Kin]: a_sum's gradient left as a gather (what
+ * mrg_sum_rows_gather reads; gself needs gh).  Each may be NULL: the term is left out.  The additions run in mrg_sum_rows_gather's
+ * order (gather, then the buffers), so the result equals that launch over {total, this kernel's plain output} element for element
+ * (up to the sign of a zero).  total may be gx itself. */
+int mrg_segmax_bwd_input_chain(const float *gout, const float *mx, const int32_t *dst, const int32_t *arg, const float *W, float *gmsg,
+                               float *gx, const int32_t *order, int64_t E, int64_t N, int D, int Kin, void *stream,
+                               const float *total, const float *gh, const float *gself);
 
 /* ---- a_std: destination-segmented standard deviation (ABI 19) ------------------------------------------------------------
  * The node-classification aggregator of reference models/operations.py:168-190, update_all(copy_edge, reduce_std) on a block:
@@ -526,6 +540,14 @@ int mrg_seg_reduce_bwd_bits(int mode, const float *gout, const int32_t *dst, con
 int64_t mrg_linear_bwd_input_workspace_bytes(int K, int Nout);
 int mrg_linear_bwd_input(const float *gY, const float *W, float *gX, void *ws,
                          int64_t rows, int K, int Nout, int ldw, int accumulate, void *stream);
+/* Gradient fan-in chain.  A tensor with several readers receives the sum of their gradients; instead of one [rows, K] tensor per
+ * reader and a K-way pass (mrg_sum_buffers), every reader but the first adds the running sum `total` [rows, K] in the store of
+ * its own last kernel.  For the input-gradient GEMMs (this one, mrg_linear_bwd_input3 and mrg_linear_bwd_input3_pair):
+ *   accumulate != 0:  gX = (gY W[:, 0:K] + gX) + total     (an epilogue kind of its own; total must not be gX)
+ *   accumulate == 0:  gX = gY W[:, 0:K] + total            (total may be gX: in place)
+ * i.e. what the plain call followed by mrg_sum_buffers({its output, total}) leaves, element for element (up to the sign of a zero). */
+int mrg_linear_bwd_input_acc2(const float *gY, const float *W, float *gX, void *ws,
+                              int64_t rows, int K, int Nout, int ldw, int accumulate, void *stream, const float *total);
 /* gW[Nout, K1+K2] = gY^T [X1 | X2]  (X2 NULL / K2 = 0: single source; the reference's
  * torch.cat([s, s_in], 1) is never materialised),  gbias[Nout] = column sums of gY (NULL ok). */
 int64_t mrg_linear_bwd_weight_workspace_bytes(int64_t rows, int K, int Nout);
@@ -589,6 +611,12 @@ int64_t mrg_linear_bwd_input3_pair_workspace_bytes(int K, int Nout);
 int mrg_linear_bwd_input3_pair(const float *gY1, const float *gY2, const float *const *W1, const float *const *W2, float *gX,
                                void *ws, int64_t b0, int64_t b1, int64_t M, int K, int Nout, int ldw, int accumulate,
                                void *stream);
+/* The two grouped input gradients joined to a running gradient fan-in sum (see mrg_linear_bwd_input_acc2); same workspaces. */
+int mrg_linear_bwd_input3_acc2(const float *gY, const float *const *W, float *gX, void *ws, int64_t b0, int64_t b1, int64_t M,
+                               int K, int Nout, int ldw, int accumulate, void *stream, const float *total);
+int mrg_linear_bwd_input3_pair_acc2(const float *gY1, const float *gY2, const float *const *W1, const float *const *W2, float *gX,
+                                    void *ws, int64_t b0, int64_t b1, int64_t M, int K, int Nout, int ldw, int accumulate,
+                                    void *stream, const float *total);
 int64_t mrg_linear_bwd_weight3_workspace_bytes(int64_t b0, int64_t b1, int64_t M, int K1, int K2, int Nout);
 int mrg_linear_bwd_weight3(const float *gY, const float *X1, const float *X2, float *const *gW, float *const *gbias, void *ws,
                            int64_t b0, int64_t b1, int64_t M, int K1, int K2, int Nout, void *stream);

@@ -54,6 +54,7 @@ SIGNATURES = {
     "mrg_gate_row_colsum_blocks": (_L, [_L, _L, _L, _I, _I]),
     "mrg_gate_row_fwd_colsum": (_I, [_P, _P, _P, _P, _P, _P, _L, _L, _L, _I, _F, _P, _P, _L]),
     "mrg_gate_row_bwd": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _L, _L, _L, _I, _P]),
+    "mrg_gate_row_bwd_acc": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _L, _L, _L, _I, _P, _P]),
     "mrg_mix_workspace_bytes": (_L, [_I, _I]),
     "mrg_mix_colstats": (_I, [_P, _I, _L, _I, _P, _P, _P, _P]),
     "mrg_mix_finalize_fwd": (_I, [_P, _P, _P, _P, _P, _I, ctypes.c_double, _I, _F, _F, _P, _P]),
@@ -77,6 +78,7 @@ SIGNATURES = {
     "mrg_gemm_set_small": (_I, [_I]),
     "mrg_segmax_bwd_input_ok": (_I, [_I, _I]),
     "mrg_segmax_bwd_input": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _L, _L, _I, _I, _P]),
+    "mrg_segmax_bwd_input_chain": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _L, _L, _I, _I, _P, _P, _P, _P]),
     "mrg_seg_std_workspace_bytes": (_L, [_L, _I]),
     "mrg_seg_std_fwd": (_I, [_P, _P, _P, _P, _P, _P, _L, _P, _P, _P, _L, _L, _P, _P, _P, _P, _P, _L, _I, _P]),
     "mrg_seg_std_bwd": (_I, [_P, _P, _P, _P, _P, _P, _P, _L, _L, _I, _P]),
@@ -93,8 +95,10 @@ SIGNATURES = {
     "mrg_dense_filter_dz3": (_I, [_I, _P, _P, _P, _P, _F, _F, _P, _P, _L, _L, _I, _P]),
     "mrg_linear_bwd_input3_workspace_bytes": (_L, [_I, _I]),
     "mrg_linear_bwd_input3": (_I, [_P, _P, _P, _P, _L, _L, _L, _I, _I, _I, _I, _P]),
+    "mrg_linear_bwd_input3_acc2": (_I, [_P, _P, _P, _P, _L, _L, _L, _I, _I, _I, _I, _P, _P]),
     "mrg_linear_bwd_input3_pair_workspace_bytes": (_L, [_I, _I]),
     "mrg_linear_bwd_input3_pair": (_I, [_P, _P, _P, _P, _P, _P, _L, _L, _L, _I, _I, _I, _I, _P]),
+    "mrg_linear_bwd_input3_pair_acc2": (_I, [_P, _P, _P, _P, _P, _P, _L, _L, _L, _I, _I, _I, _I, _P, _P]),
     "mrg_linear_bwd_weight3_workspace_bytes": (_L, [_L, _L, _L, _I, _I, _I]),
     "mrg_linear_bwd_weight3": (_I, [_P, _P, _P, _P, _P, _P, _L, _L, _L, _I, _I, _I, _P]),
     "mrg_linear_relu_segsum_fwd": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _L, _I, _I, _P]),
@@ -105,6 +109,7 @@ SIGNATURES = {
     "mrg_linear_relu_segmax_fwd": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _L, _L, _I, _I, _P]),
     "mrg_linear_bwd_input_workspace_bytes": (_L, [_I, _I]),
     "mrg_linear_bwd_input": (_I, [_P, _P, _P, _P, _L, _I, _I, _I, _I, _P]),
+    "mrg_linear_bwd_input_acc2": (_I, [_P, _P, _P, _P, _L, _I, _I, _I, _I, _P, _P]),
     "mrg_linear_bwd_weight_workspace_bytes": (_L, [_L, _I, _I]),
     "mrg_linear_bwd_weight": (_I, [_P, _P, _P, _P, _P, _P, _L, _I, _I, _I, _P]),
     "mrg_linear_bwd_weight_share": (_I, [_P, _P, _P, _P, _P, _P, _L, _I, _I, _I, _I, _P]),
@@ -234,11 +239,20 @@ def _trace(name, args):
     print(f"[mrg] {name} {shown}", file=sys.stderr, flush=True)
 
 
+# The forms of an entry point as a member of a gradient fan-in chain (functional/fanin.py) take the running sum -- and, a_max, the
+# gathered term -- as trailing arguments: call() recognises them by the number of arguments, so a call site only appends them.
+_CHAIN_FORMS = {(name, len(SIGNATURES[sym][1])): sym for name, sym in (
+    ("mrg_linear_bwd_input", "mrg_linear_bwd_input_acc2"), ("mrg_linear_bwd_input3", "mrg_linear_bwd_input3_acc2"),
+    ("mrg_linear_bwd_input3_pair", "mrg_linear_bwd_input3_pair_acc2"), ("mrg_segmax_bwd_input", "mrg_segmax_bwd_input_chain"),
+    ("mrg_gate_row_bwd", "mrg_gate_row_bwd_acc"))}
+_CHAIN_NAMES = frozenset(name for name, _ in _CHAIN_FORMS)
+
+
 def call(name, args, nbytes=0, flops=0, symbol=None):
     """Invoke C-ABI function `name`; raise on a non-zero return code.  symbol: the C function to call when it is a variant of `name`
-    with trailing arguments (mrg_dense_filter_fwd3_colsum, mrg_gate_row_fwd_colsum): traces, the meter and bench.py's tables
-    keep one logical name per entry point."""
-    sym = symbol or name
+    with trailing arguments (mrg_dense_filter_fwd3_colsum, mrg_gate_row_fwd_colsum; the chain forms above need not be named): traces,
+    the meter and bench.py's tables keep one logical name per entry point."""
+    sym = symbol or (_CHAIN_FORMS.get((name, len(args)), name) if name in _CHAIN_NAMES else name)
     fn = _FN.get(sym)
     if fn is None:
         fn = _FN[sym] = getattr(load(), sym)

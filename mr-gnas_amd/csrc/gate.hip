@@ -355,10 +355,22 @@ __global__ __launch_bounds__(MRG_BLOCK) void gate_row_fwd_colsum_k(const float* 
 // q[r] (the gradient w.r.t. fvec[r], from the epilogue's backward), dz_r = q_r * hvec[r] -> gs_in = dz_r * v (HAS_IN), per-block
 // partials of du = sum_r dz_r s_r, dv = sum_r dz_r s_in_r, dc = sum_r dz_r  (the block reduction and its order are gate_bwd_k's).
 // The gradient w.r.t. s (gy * f_r + dz_r * u) was added to the epilogue's gs_out.
-template <int VEC, int LPR, int KMAX, bool HAS_IN>
+// a + b where b is a product formed by the caller: the product is rounded first, as the plain kernel stores it (inside the caller's
+// loop hipcc contracts the two into a fused multiply-add, whose sum differs from the K-way pass over the stored product)
+template <int VEC>
+__device__ __forceinline__ Vec<VEC> add_rounded(Vec<VEC> a, Vec<VEC> b) {
+#pragma clang fp contract(off)
+#pragma unroll
+  for (int j = 0; j < VEC; ++j) a[j] = a[j] + b[j];
+  return a;
+}
+
+// ACC (with HAS_IN): gs_in = tot + dz_r * v, the rank-1 term added onto the running gradient fan-in sum tot [M, D] (functional/fanin.py);
+// tot may be gsin itself (a lane reads its elements before it stores them; gsin carries no __restrict__ for that).
+template <int VEC, int LPR, int KMAX, bool HAS_IN, bool ACC = false>
 __global__ __launch_bounds__(MRG_BLOCK) void gate_row_bwd_k(const float* __restrict__ qv, const float* __restrict__ hv, const float* __restrict__ s,
                                                             const float* __restrict__ sin_, const float* __restrict__ uvc,
-                                                            float* __restrict__ gsin, float* __restrict__ ws, SegPlan p, int D) {
+                                                            float* gsin, float* __restrict__ ws, SegPlan p, int D, const float* tot = nullptr) {
   constexpr int RPB = MRG_BLOCK / LPR;
   constexpr int WIDTH = LPR * KMAX * VEC;                 // >= D
   __shared__ float red[RPB * (2 * WIDTH + 1)];
@@ -398,6 +410,7 @@ __global__ __launch_bounds__(MRG_BLOCK) void gate_row_bwd_k(const float* __restr
             o2[j] = dz * vk[k][j];
             dvv[k][j] += dz * xk[j];
           }
+          if (ACC) o2 = add_rounded(Vec<VEC>::load(tot + r * D + c * VEC), o2);
           o2.store(gsin + r * D + c * VEC);
         }
       }
@@ -688,16 +701,17 @@ extern "C" int mrg_gate_row_fwd_colsum(const float* s, const float* s_in, const 
 
 // q [M] (written by mrg_mix_bwd_apply, mrg_gated_branch.row_dq), hvec [M] (mrg_gate_row_fwd) -> gs_in [M, D] (s_in != NULL) and
 // d_uvc [3][MRG_GATE_LD(D)] (then mrg_gate_param_grad3).  ws: mrg_gate_bwd_workspace_bytes(M, D).
-extern "C" int mrg_gate_row_bwd(const float* q, const float* hvec, const float* s, const float* s_in, const float* uvc, float* gs_in, float* d_uvc,
-                                void* ws, int64_t b0, int64_t b1, int64_t M, int D, void* stream) {
+static int gate_row_bwd(const float* q, const float* hvec, const float* s, const float* s_in, const float* uvc, float* gs_in, float* d_uvc,
+                        void* ws, int64_t b0, int64_t b1, int64_t M, int D, void* stream, const float* total) {
   if (D <= 0 || M < 0 || b0 < 0 || b1 < b0 || M < b1) return MRG_E_SHAPE;
   if (!uvc || !d_uvc) return MRG_E_NULLPTR;
   if (M > 0 && (!q || !hvec || !s)) return MRG_E_NULLPTR;
   if (s_in && !gs_in) return MRG_E_NULLPTR;
+  if (total && !s_in) return MRG_E_NULLPTR;
   if (!ws) return MRG_E_WORKSPACE;
   hipStream_t st = (hipStream_t)stream;
   const int ld = MRG_GATE_LD(D);
-  RowGeom g = row_geom(D, aligned16(s) && aligned16(s_in) && aligned16(gs_in) && aligned16(uvc));
+  RowGeom g = row_geom(D, aligned16(s) && aligned16(s_in) && aligned16(gs_in) && aligned16(uvc) && aligned16(total));
   if (!g.ok) return MRG_E_SHAPE;
   SegPlan p{};
 #define CALL(V, L, K)                                                                                                   \
@@ -706,8 +720,9 @@ extern "C" int mrg_gate_row_bwd(const float* q, const float* hvec, const float* 
     if (grid < 3) grid = 3;                                                                                             \
     p = make_plan(b0, b1, M, grid);                                                                                     \
     if (M > 0) {                                                                                                        \
-      if (s_in) hipLaunchKernelGGL((gate_row_bwd_k<V, L, K, true>), dim3(p.blk[3]), dim3(MRG_BLOCK), 0, st, q, hvec, s, s_in, uvc, gs_in, (float*)ws, p, D); \
-      else hipLaunchKernelGGL((gate_row_bwd_k<V, L, K, false>), dim3(p.blk[3]), dim3(MRG_BLOCK), 0, st, q, hvec, s, s_in, uvc, gs_in, (float*)ws, p, D); \
+      if (total) hipLaunchKernelGGL((gate_row_bwd_k<V, L, K, true, true>), dim3(p.blk[3]), dim3(MRG_BLOCK), 0, st, q, hvec, s, s_in, uvc, gs_in, (float*)ws, p, D, total); \
+      else if (s_in) hipLaunchKernelGGL((gate_row_bwd_k<V, L, K, true>), dim3(p.blk[3]), dim3(MRG_BLOCK), 0, st, q, hvec, s, s_in, uvc, gs_in, (float*)ws, p, D, nullptr); \
+      else hipLaunchKernelGGL((gate_row_bwd_k<V, L, K, false>), dim3(p.blk[3]), dim3(MRG_BLOCK), 0, st, q, hvec, s, s_in, uvc, gs_in, (float*)ws, p, D, nullptr); \
     }                                                                                                                   \
   } while (0)
   MRG_DISPATCH_GEOM(g, CALL);
@@ -716,4 +731,16 @@ extern "C" int mrg_gate_row_bwd(const float* q, const float* hvec, const float* 
   launch_ordered_reduce_ranges<float>((const float*)ws, d_uvc, p.blk, 3, ld, ld, ld, st);
   MRG_LAUNCH_CHECK();
   return MRG_OK;
+}
+
+extern "C" int mrg_gate_row_bwd(const float* q, const float* hvec, const float* s, const float* s_in, const float* uvc, float* gs_in, float* d_uvc,
+                                void* ws, int64_t b0, int64_t b1, int64_t M, int D, void* stream) {
+  return gate_row_bwd(q, hvec, s, s_in, uvc, gs_in, d_uvc, ws, b0, b1, M, D, stream, nullptr);
+}
+
+// the same with the rank-1 term added onto the running gradient fan-in sum: gs_in = total + dz_r * v (s_in != NULL; total may be gs_in)
+extern "C" int mrg_gate_row_bwd_acc(const float* q, const float* hvec, const float* s, const float* s_in, const float* uvc, float* gs_in, float* d_uvc,
+                                    void* ws, int64_t b0, int64_t b1, int64_t M, int D, void* stream, const float* total) {
+  if (!total) return MRG_E_NULLPTR;
+  return gate_row_bwd(q, hvec, s, s_in, uvc, gs_in, d_uvc, ws, b0, b1, M, D, stream, total);
 }

@@ -46,6 +46,10 @@ constexpr bool epi_diag(int epi) { return epi == EPI_RANK_DIAG; }
 // are queries, columns are entities, the label of an element is looked up in the query's object list.  EPI_BCE stores nothing per
 // element (one float64 partial per workgroup), EPI_BCE_GRAD stores the gradient with respect to the logits.  Kernel instances of their own.
 enum { EPI_BCE = 10, EPI_BCE_GRAD = 11 };
+// EPI_ACCUM with a second addend: C = (acc + Cin) + Cin2 -- the input-gradient GEMM of a reader that joins a running gradient fan-in
+// sum (functional/fanin.py): its own term first, then the sum so far.  Cin2 may be C itself.  Kernel instances of their own.
+enum { EPI_ACCUM2 = 12 };
+constexpr bool epi_accum(int epi) { return epi == EPI_ACCUM || epi == EPI_ACCUM2; }
 
 // Up to three row ranges of ONE launch of the split-core row GEMM that share every tensor but differ in the weight matrix
 // (the in / out / self direction segments of a dense filter: one launch instead of three).  Workgroup blocks
@@ -98,6 +102,8 @@ struct GemmArgs {
 // EPI_GATE_SUMS / EPI_SCALE_SUMS: colsum[workgroup along x][2][N] float64, the workgroup's column sums and column sums of squares of
 // its output values.  The pointer shares the slot of seg_part (EPI_SEGSUM only), so the argument block -- and with it the code of
 // every other kernel instance -- stays what it was.
+// EPI_ACCUM2: the second addend [rows][ld] travels in the slots of the gate's multiplicand (S, ld_s), which EPI_ACCUM does not use.
+inline void gemm_set_cin2(GemmArgs& a, const float* cin2, int ld) { a.S = cin2; a.ld_s = ld; }
 inline void gemm_set_colsum(GemmArgs& a, double* colsum) { a.seg_part = reinterpret_cast<float*>(colsum); }
 __host__ __device__ __forceinline__ double* gemm_colsum(const GemmArgs& a) { return reinterpret_cast<double*>(a.seg_part); }
 
@@ -549,6 +555,7 @@ __device__ __forceinline__ void gemm_epilogue(const GemmArgs& a, f32x16 (&acc)[N
   const int colw = col0 + li < a.N ? col0 + li : a.N - 1;   // this lane's column in tile 0 (clamped: only lanes of a partial tile)
   float* crow[16];
   const float* srow[16];
+  const float* trow[16];                                   // EPI_ACCUM2: the second addend
   float* xrow[16];
   float cs[16];
   bool rok[16];
@@ -562,7 +569,8 @@ __device__ __forceinline__ void gemm_epilogue(const GemmArgs& a, f32x16 (&acc)[N
     rok[r] = row <= last;
     crow[r] = a.C + (rowbase + rc) * a.ldc + colw;
     if (EPI == EPI_GATE) srow[r] = a.S + (rowbase + rc) * a.ld_s + colw;
-    if (EPI == EPI_ACCUM) srow[r] = a.Cin + (rowbase + rc) * a.ld_cin + colw;
+    if (epi_accum(EPI)) srow[r] = a.Cin + (rowbase + rc) * a.ld_cin + colw;
+    if (EPI == EPI_ACCUM2) trow[r] = a.S + (rowbase + rc) * a.ld_s + colw;
     if (EPI == EPI_GATE) xrow[r] = a.aux ? a.aux + (rowbase + rc) * a.N + colw : nullptr;
     cs[r] = 1.0f;
     if (EPI == EPI_GATE || EPI == EPI_SCALE) cs[r] = a.scale * (a.rowscale ? a.rowscale[rowbase + rc] : 1.0f);
@@ -574,12 +582,16 @@ __device__ __forceinline__ void gemm_epilogue(const GemmArgs& a, f32x16 (&acc)[N
     const bool cok = col < a.N;
     const int off = cok ? n * 32 : 0;
     const float bv = a.bias ? a.bias[cok ? col : colw] : 0.f;
-    float in[16], v[16], g[16];
+    float in[16], in2[16], v[16], g[16];
 #pragma unroll
     for (int r = 0; r < 16; ++r) in[r] = 0.f;
-    if ((EPI == EPI_GATE && (cstore || SUMS)) || EPI == EPI_ACCUM) {     // (gate only, no sums: the multiplicand is not read at all)
+    if ((EPI == EPI_GATE && (cstore || SUMS)) || epi_accum(EPI)) {       // (gate only, no sums: the multiplicand is not read at all)
 #pragma unroll
       for (int r = 0; r < 16; ++r) in[r] = srow[r][off];
+    }
+    if (EPI == EPI_ACCUM2) {
+#pragma unroll
+      for (int r = 0; r < 16; ++r) in2[r] = trow[r][off];
     }
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
@@ -591,6 +603,8 @@ __device__ __forceinline__ void gemm_epilogue(const GemmArgs& a, f32x16 (&acc)[N
         v[r] = g[r] * in[r] * cs[r];
       } else if (EPI == EPI_SCALE) {
         v[r] = x * cs[r];
+      } else if (EPI == EPI_ACCUM2) {
+        v[r] = (x + in[r]) + in2[r];
       } else {
         v[r] = x + in[r];
       }

@@ -61,6 +61,7 @@ __device__ __forceinline__ void gemm_epilogue_q(const GemmArgs& a, f32x4v (&acc)
   const int colw = li < a.N ? li : a.N - 1;
   float* crow[8];
   const float* srow[8];
+  const float* trow[8];                                    // EPI_ACCUM2: the second addend
   float* xrow[8];
   float cs[8];
   bool rok[8];
@@ -72,7 +73,8 @@ __device__ __forceinline__ void gemm_epilogue_q(const GemmArgs& a, f32x4v (&acc)
     rok[i] = row <= last;
     crow[i] = a.C + (rowbase + rc) * a.ldc + colw;
     if (EPI == EPI_GATE) srow[i] = a.S + (rowbase + rc) * a.ld_s + colw;
-    if (EPI == EPI_ACCUM) srow[i] = a.Cin + (rowbase + rc) * a.ld_cin + colw;
+    if (epi_accum(EPI)) srow[i] = a.Cin + (rowbase + rc) * a.ld_cin + colw;
+    if (EPI == EPI_ACCUM2) trow[i] = a.S + (rowbase + rc) * a.ld_s + colw;
     if (EPI == EPI_GATE) xrow[i] = a.aux ? a.aux + (rowbase + rc) * a.N + colw : nullptr;
     cs[i] = 1.0f;
     if (EPI == EPI_GATE || EPI == EPI_SCALE) cs[i] = a.scale * (a.rowscale ? a.rowscale[rowbase + rc] : 1.0f);
@@ -98,12 +100,16 @@ __device__ __forceinline__ void gemm_epilogue_q(const GemmArgs& a, f32x4v (&acc)
     const int col = j * 32 + li;
     const bool cok = col < a.N;                             // columns of this pair that exist; a lane beyond them re-reads its column of pair 0 (never stored)
     const int off = cok ? j * 32 : 0;
-    float in[8], v[8], g[8];
+    float in[8], in2[8], v[8], g[8];
 #pragma unroll
     for (int i = 0; i < 8; ++i) in[i] = 0.f;
-    if ((EPI == EPI_GATE && (cstore || SUMS)) || EPI == EPI_ACCUM) {
+    if ((EPI == EPI_GATE && (cstore || SUMS)) || epi_accum(EPI)) {
 #pragma unroll
       for (int i = 0; i < 8; ++i) in[i] = srow[i][off];
+    }
+    if (EPI == EPI_ACCUM2) {
+#pragma unroll
+      for (int i = 0; i < 8; ++i) in2[i] = trow[i][off];
     }
 #pragma unroll
     for (int i = 0; i < 8; ++i) {
@@ -113,6 +119,8 @@ __device__ __forceinline__ void gemm_epilogue_q(const GemmArgs& a, f32x4v (&acc)
       } else if (EPI == EPI_GATE) {
         g[i] = sigmoidf_fast(x);
         v[i] = g[i] * in[i] * cs[i];
+      } else if (EPI == EPI_ACCUM2) {
+        v[i] = (x + in[i]) + in2[i];
       } else if (EPI == EPI_SCALE) {
         v[i] = x * cs[i];
       } else {

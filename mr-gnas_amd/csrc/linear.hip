@@ -149,6 +149,27 @@ extern "C" int mrg_linear_bwd_input(const float* gY, const float* W, float* gX, 
   return launch_gemm<EPI_BIAS_ACT>(a, 1, ldw, ws, st);
 }
 
+// The same joined to a running gradient fan-in sum `total` [rows, K] (functional/fanin.py): gX = (gY W[:, 0:K] + gX) + total with
+// accumulate != 0, gX = gY W[:, 0:K] + total without.  total may be gX itself where gX is not also the first addend.
+extern "C" int mrg_linear_bwd_input_acc2(const float* gY, const float* W, float* gX, void* ws, int64_t rows, int K, int Nout,
+                                         int ldw, int accumulate, void* stream, const float* total) {
+  if (rows < 0 || K <= 0 || Nout <= 0 || ldw < K) return MRG_E_SHAPE;
+  if (rows == 0) return MRG_OK;
+  if (!gY || !W || !gX || !total) return MRG_E_NULLPTR;
+  if (accumulate && total == gX) return MRG_E_SHAPE;
+  if (!ws) return MRG_E_WORKSPACE;
+  hipStream_t st = (hipStream_t)stream;
+  GemmArgs a{};
+  a.A1 = gY; a.K1 = Nout; a.B = W; a.C = gX; a.ldc = K; a.N = K; a.rows = rows; a.act = MRG_ACT_NONE;
+  if (accumulate) {
+    a.Cin = gX; a.ld_cin = K;
+    gemm_set_cin2(a, total, K);
+    return launch_gemm<EPI_ACCUM2>(a, 1, ldw, ws, st);
+  }
+  a.Cin = total; a.ld_cin = K;
+  return launch_gemm<EPI_ACCUM>(a, 1, ldw, ws, st);
+}
+
 // ---- the three direction segments of a dense filter in one launch each (split core only) -----------------------------------
 // gX rows [0, b0) (+)= gY W[0][:, 0:K], rows [b0, b1) with W[1], rows [b1, M) with W[2]; W: HOST array of three device
 // pointers to [Nout][ldw] weights (a column block when offset by the caller).
@@ -159,14 +180,24 @@ extern "C" int mrg_linear_bwd_input(const float* gY, const float* W, float* gX, 
 static size_t bwd_input3_each(int K, int Nred) { return (size_t)(((int64_t)bsplit_bytes_any(K, Nred) + 255) / 256 * 256); }
 
 // the arguments as checked by the two entry points below; gY2 / W2_host NULL: the single form
+// total (NULL: none): the running fan-in sum this product is joined to, gX = (product [+ gX]) + total (mrg_linear_bwd_input_acc2)
 static int bwd_input3(const float* gY1, const float* gY2, const float* const* W1_host, const float* const* W2_host, float* gX, void* ws,
-                      int64_t b0, int64_t b1, int64_t M, int K, int Nout, int ldw, int accumulate, hipStream_t st) {
+                      int64_t b0, int64_t b1, int64_t M, int K, int Nout, int ldw, int accumulate, hipStream_t st,
+                      const float* total = nullptr) {
   const bool pair = gY2 != nullptr;
   const int Nred = pair ? 2 * Nout : Nout;       // the reduction dimension
   GemmArgs a{};
   a.A1 = gY1; a.K1 = Nout; a.C = gX; a.ldc = K; a.N = K; a.rows = M; a.act = MRG_ACT_NONE;
   if (pair) { a.A2 = gY2; a.K2 = Nout; }
   if (accumulate) { a.Cin = gX; a.ld_cin = K; }
+  if (total && accumulate) {
+    if (total == gX) return MRG_E_SHAPE;
+    gemm_set_cin2(a, total, K);
+  } else if (total) {
+    a.Cin = total; a.ld_cin = K;
+  }
+  // the epilogue kind: the weight split and the launch must name the same one (x3q_shape / x3n_shape are functions of it)
+  const int epi = total && accumulate ? EPI_ACCUM2 : (total || accumulate ? EPI_ACCUM : EPI_BIAS_ACT);
   if (!x3_eligible(a)) return MRG_E_SHAPE;
   const int64_t lo[3] = {0, b0, b1}, hi[3] = {b0, b1, M};
   const size_t each = bwd_input3_each(K, Nred);
@@ -183,9 +214,10 @@ static int bwd_input3(const float* gY1, const float* gY2, const float* const* W1
     a.grp.scale[i] = 1.0f;
   }
   // B(n = k_in, k) = k < Nout ? W1[k * ldw + k_in] : W2[(k - Nout) * ldw + k_in]
-  launch_bsplit3_any(accumulate ? EPI_ACCUM : EPI_BIAS_ACT, M, Bs, 1, ldw, K, Nred, outs, st, pair ? Bs2 : nullptr, pair ? Nout : 0);
+  launch_bsplit3_any(epi, M, Bs, 1, ldw, K, Nred, outs, st, pair ? Bs2 : nullptr, pair ? Nout : 0);
   MRG_LAUNCH_CHECK();
-  if (accumulate) return launch_rowgemm_x3_mode<EPI_ACCUM>(a, outs[0], st);
+  if (epi == EPI_ACCUM2) return launch_rowgemm_x3_mode<EPI_ACCUM2>(a, outs[0], st);
+  if (epi == EPI_ACCUM) return launch_rowgemm_x3_mode<EPI_ACCUM>(a, outs[0], st);
   return launch_rowgemm_x3_mode<EPI_BIAS_ACT>(a, outs[0], st);
 }
 
@@ -204,6 +236,16 @@ extern "C" int mrg_linear_bwd_input3(const float* gY, const float* const* W_host
   return bwd_input3(gY, nullptr, W_host, nullptr, gX, ws, b0, b1, M, K, Nout, ldw, accumulate, (hipStream_t)stream);
 }
 
+extern "C" int mrg_linear_bwd_input3_acc2(const float* gY, const float* const* W_host, float* gX, void* ws, int64_t b0, int64_t b1, int64_t M,
+                                          int K, int Nout, int ldw, int accumulate, void* stream, const float* total) {
+  if (K <= 0 || Nout <= 0 || ldw < K || M < 0 || b0 < 0 || b1 < b0 || M < b1) return MRG_E_SHAPE;
+  if (K <= 0 || Nout <= 48 || Nout % 4 != 0) return MRG_E_SHAPE;
+  if (M == 0) return MRG_OK;
+  if (!gY || !W_host || !gX || !total) return MRG_E_NULLPTR;
+  if (!ws) return MRG_E_WORKSPACE;
+  return bwd_input3(gY, nullptr, W_host, nullptr, gX, ws, b0, b1, M, K, Nout, ldw, accumulate, (hipStream_t)stream, total);
+}
+
 extern "C" int64_t mrg_linear_bwd_input3_pair_workspace_bytes(int K, int Nout) {
   if (K <= 0 || Nout <= 24 || Nout % 4 != 0 || gemm_mode() == 1) return 0;
   return 3 * (int64_t)bwd_input3_each(K, 2 * Nout);
@@ -216,4 +258,14 @@ extern "C" int mrg_linear_bwd_input3_pair(const float* gY1, const float* gY2, co
   if (!gY1 || !gY2 || !W1_host || !W2_host || !gX) return MRG_E_NULLPTR;
   if (!ws) return MRG_E_WORKSPACE;
   return bwd_input3(gY1, gY2, W1_host, W2_host, gX, ws, b0, b1, M, K, Nout, ldw, accumulate, (hipStream_t)stream);
+}
+
+extern "C" int mrg_linear_bwd_input3_pair_acc2(const float* gY1, const float* gY2, const float* const* W1_host, const float* const* W2_host, float* gX,
+                                               void* ws, int64_t b0, int64_t b1, int64_t M, int K, int Nout, int ldw, int accumulate, void* stream,
+                                               const float* total) {
+  if (K <= 0 || Nout <= 24 || Nout % 4 != 0 || ldw < K || M < 0 || b0 < 0 || b1 < b0 || M < b1) return MRG_E_SHAPE;
+  if (M == 0) return MRG_OK;
+  if (!gY1 || !gY2 || !W1_host || !W2_host || !gX || !total) return MRG_E_NULLPTR;
+  if (!ws) return MRG_E_WORKSPACE;
+  return bwd_input3(gY1, gY2, W1_host, W2_host, gX, ws, b0, b1, M, K, Nout, ldw, accumulate, (hipStream_t)stream, total);
 }

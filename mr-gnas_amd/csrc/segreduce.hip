@@ -147,10 +147,19 @@ __global__ __launch_bounds__(MRG_BLOCK) void seg_bwd_k(const float* __restrict__
 // N * D / E of them (5.3) -- from a copy of W in LDS (D * K * 4 bytes <= 160 KB: D = K = 200 fills the CU's LDS exactly; one
 // 1024-thread workgroup per CU).  Order of the sum per output element: the won columns c ascending within j = c % 4, j = 0..3 --
 // deterministic; exact f32 FMAs (the dense product ran on the split core at f32-equivalent accuracy).
+// CHAIN (the kernel as the last-but-one or last producer of a gradient fan-in, functional/fanin.py): gx has E + N rows and leaves as
+//   gx[e]     = (gh[dst[e]] + total[e]) + own[e]          e < E      own: the product above
+//   gx[E + n] = (gself[n] + total[E + n]) + gout[n]       n < N      (the residual self rows; needs D == Kin)
+// gh [N, Kin] / gself [N, Kin] (a_sum's gradient left as a gather: what sum_rows_gather_k reads) and total [E + N, Kin] (the running
+// sum) may each be NULL: that term is left out.  The order of the additions is sum_rows_gather_k's.  total may be gx itself: a
+// lane reads its own elements of a row before it stores them (gx carries no __restrict__ for that).
+template <bool CHAIN>
 __global__ __launch_bounds__(1024) void segmax_bwd_gx_k(const float* __restrict__ gout, const float* __restrict__ mx,
                                                       const int32_t* __restrict__ dst, const int32_t* __restrict__ arg,
-                                                      const float* __restrict__ W, float* __restrict__ gmsg, float* __restrict__ gx,
-                                                      const int32_t* __restrict__ order, int64_t E, int D, int Kin) {
+                                                      const float* __restrict__ W, float* __restrict__ gmsg, float* gx,
+                                                      const int32_t* __restrict__ order, int64_t E, int D, int Kin,
+                                                      const float* total, const float* __restrict__ gh, const float* __restrict__ gself,
+                                                      int64_t N) {
   extern __shared__ __align__(16) float wl[];
   constexpr int THREADS = 1024, WAVES = THREADS / 64;
   const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -174,18 +183,45 @@ __global__ __launch_bounds__(1024) void segmax_bwd_gx_k(const float* __restrict_
     }
   };
   const int64_t first = (int64_t)blockIdx.x * WAVES + wave;
-  if (first >= E) return;                                   // (after the only barrier)
+  // CHAIN: the self rows, one wave per row
+  auto self_rows = [&]() {
+    for (int64_t n = first; n < N; n += stride) {
+      if (lane < kv) {
+        const int64_t o = (E + n) * Kin + lane * 4;
+        float4 a = *reinterpret_cast<const float4*>(gout + n * D + lane * 4);
+        float4 t = make_float4(0.f, 0.f, 0.f, 0.f), h = t;
+        if (total) t = *reinterpret_cast<const float4*>(total + o);
+        if (gself) h = *reinterpret_cast<const float4*>(gself + n * Kin + lane * 4);
+        if (gself && total) { a.x = (h.x + t.x) + a.x; a.y = (h.y + t.y) + a.y; a.z = (h.z + t.z) + a.z; a.w = (h.w + t.w) + a.w; }
+        else if (gself) { a.x += h.x; a.y += h.y; a.z += h.z; a.w += h.w; }
+        else if (total) { a.x += t.x; a.y += t.y; a.z += t.z; a.w += t.w; }
+        *reinterpret_cast<float4*>(gx + o) = a;
+      }
+    }
+  };
+  if (first >= E) {                                         // (after the only barrier)
+    if constexpr (CHAIN) self_rows();
+    return;
+  }
   int r0 = __builtin_amdgcn_readfirstlane(edge_at(first));
   int r1 = __builtin_amdgcn_readfirstlane(edge_at(first + stride));
   int64_t v1 = __builtin_amdgcn_readfirstlane(dst[r1]);
+  int64_t v0 = __builtin_amdgcn_readfirstlane(dst[r0]);
   float4 g4, x4; int4 a4;
-  load_row((int64_t)__builtin_amdgcn_readfirstlane(dst[r0]), g4, a4, x4);
+  load_row(v0, g4, a4, x4);
   for (int64_t pos = first; pos < E; pos += stride) {
     const int r2 = __builtin_amdgcn_readfirstlane(edge_at(pos + 2 * stride));
     const int v2 = dst[r2];                                 // in flight until the bottom of the trip
     float4 gn, xn; int4 an;
     load_row(v1, gn, an, xn);                               // edge i + 1's rows: in flight during edge i's work
     const int r = r0;
+    float4 t4 = make_float4(0.f, 0.f, 0.f, 0.f), h4 = t4;   // CHAIN: this row of the running sum and of the gather, in flight during the product
+    if constexpr (CHAIN) {
+      if (lane < kv) {
+        if (total) t4 = *reinterpret_cast<const float4*>(total + (int64_t)r * Kin + lane * 4);
+        if (gh) h4 = *reinterpret_cast<const float4*>(gh + v0 * Kin + lane * 4);
+      }
+    }
     float m[4];
     m[0] = (a4.x == r && x4.x > 0.f) ? g4.x : 0.f;
     m[1] = (a4.y == r && x4.y > 0.f) ? g4.y : 0.f;
@@ -207,11 +243,18 @@ __global__ __launch_bounds__(1024) void segmax_bwd_gx_k(const float* __restrict_
         }
       }
     }
+    if constexpr (CHAIN) {
+      if (gh && total) { acc.x = (h4.x + t4.x) + acc.x; acc.y = (h4.y + t4.y) + acc.y; acc.z = (h4.z + t4.z) + acc.z; acc.w = (h4.w + t4.w) + acc.w; }
+      else if (gh) { acc.x += h4.x; acc.y += h4.y; acc.z += h4.z; acc.w += h4.w; }
+      else if (total) { acc.x += t4.x; acc.y += t4.y; acc.z += t4.z; acc.w += t4.w; }
+    }
     if (lane < kv) *reinterpret_cast<float4*>(gx + (int64_t)r * Kin + lane * 4) = acc;
     g4 = gn; a4 = an; x4 = xn;
     r0 = r1; r1 = r2;
+    v0 = v1;
     v1 = __builtin_amdgcn_readfirstlane(v2);
   }
+  if constexpr (CHAIN) self_rows();
 }
 
 }  // namespace mrg
@@ -225,20 +268,45 @@ extern "C" int mrg_segmax_bwd_input_ok(int D, int Kin) {
 
 // gmsg [E, D] (may be NULL) and gx [E, Kin] = gmsg W of a_max's backward in one pass (see segmax_bwd_gx_k).  gout / mx / arg: [N, D]
 // (mx NULL: no ReLU mask); W [D, Kin] row-major (nn.Linear.weight of the aggregator); order: NULL or the edge ids by destination.
-extern "C" int mrg_segmax_bwd_input(const float* gout, const float* mx, const int32_t* dst, const int32_t* arg, const float* W, float* gmsg,
-                                    float* gx, const int32_t* order, int64_t E, int64_t N, int D, int Kin, void* stream) {
+// chain: gx has E + N rows and also receives the running fan-in sum `total` [E + N, Kin], a_sum's gather gh / gself [N, Kin] and, on
+// the self rows, gout itself (segmax_bwd_gx_k<true>; D == Kin).
+static int segmax_bwd_input(const float* gout, const float* mx, const int32_t* dst, const int32_t* arg, const float* W, float* gmsg,
+                            float* gx, const int32_t* order, int64_t E, int64_t N, int D, int Kin, void* stream, bool chain,
+                            const float* total, const float* gh, const float* gself) {
   if (E < 0 || N < 0 || E >= ((int64_t)1 << 31)) return MRG_E_SHAPE;
   if (!mrg_segmax_bwd_input_ok(D, Kin)) return MRG_E_SHAPE;
-  if (E == 0) return MRG_OK;
-  if (!gout || !dst || !arg || !W || !gx) return MRG_E_NULLPTR;
+  if (chain && D != Kin) return MRG_E_SHAPE;
+  const int64_t work = chain && N > E ? N : E;
+  if (work == 0) return MRG_OK;
+  if (!gout || !arg || !W || !gx || (E > 0 && !dst)) return MRG_E_NULLPTR;
+  if (gself && !gh) return MRG_E_NULLPTR;
   if (!aligned16(gout) || !aligned16(arg) || !aligned16(W) || !aligned16(gx) || !aligned16(gmsg) || !aligned16(mx)) return MRG_E_SHAPE;
+  if (!aligned16(total) || !aligned16(gh) || !aligned16(gself)) return MRG_E_SHAPE;
   const size_t lds = (size_t)D * Kin * sizeof(float);
-  (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&segmax_bwd_gx_k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  int64_t grid = (E + 15) / 16;
+  int64_t grid = (work + 15) / 16;
   if (grid > 256) grid = 256;                              // one 1024-thread workgroup (the whole LDS) per CU
-  hipLaunchKernelGGL(segmax_bwd_gx_k, dim3((unsigned)grid), dim3(1024), lds, (hipStream_t)stream, gout, mx, dst, arg, W, gmsg, gx, order, E, D, Kin);
+  if (chain) {
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&segmax_bwd_gx_k<true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    hipLaunchKernelGGL(segmax_bwd_gx_k<true>, dim3((unsigned)grid), dim3(1024), lds, (hipStream_t)stream, gout, mx, dst, arg, W, gmsg, gx, order, E, D,
+                       Kin, total, gh, gself, N);
+  } else {
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&segmax_bwd_gx_k<false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    hipLaunchKernelGGL(segmax_bwd_gx_k<false>, dim3((unsigned)grid), dim3(1024), lds, (hipStream_t)stream, gout, mx, dst, arg, W, gmsg, gx, order, E, D,
+                       Kin, nullptr, nullptr, nullptr, N);
+  }
   MRG_LAUNCH_CHECK();
   return MRG_OK;
+}
+
+extern "C" int mrg_segmax_bwd_input(const float* gout, const float* mx, const int32_t* dst, const int32_t* arg, const float* W, float* gmsg,
+                                    float* gx, const int32_t* order, int64_t E, int64_t N, int D, int Kin, void* stream) {
+  return segmax_bwd_input(gout, mx, dst, arg, W, gmsg, gx, order, E, N, D, Kin, stream, false, nullptr, nullptr, nullptr);
+}
+
+extern "C" int mrg_segmax_bwd_input_chain(const float* gout, const float* mx, const int32_t* dst, const int32_t* arg, const float* W, float* gmsg,
+                                          float* gx, const int32_t* order, int64_t E, int64_t N, int D, int Kin, void* stream,
+                                          const float* total, const float* gh, const float* gself) {
+  return segmax_bwd_input(gout, mx, dst, arg, W, gmsg, gx, order, E, N, D, Kin, stream, true, total, gh, gself);
 }
 
 extern "C" int64_t mrg_seg_reduce_workspace_bytes(int64_t n_slots, int D) {

@@ -11,6 +11,28 @@ from .._lib import ptr_array, call, f32c, ptr, require_hip, stream_of
 from . import switches as SW
 from ._base import Fork, _ws, _ws_bytes, same_rows
 from .candidates import Candidate, Link, RowScale, wants_stats
+from .fanin import Fan, join
+
+
+def _bwd_input3(name, head, tail, gX, accumulate, jn, **work):
+    """One grouped input-gradient GEMM (`name`: mrg_linear_bwd_input3 / _pair; arguments head + (gX, ...) + tail + (accumulate, stream))
+    as a member of a gradient fan-in chain (fanin.join): jn None -> the plain launch into gX, which is returned to autograd;
+    jn without a running sum -> the plain launch, gX becomes the running sum; else the *_acc2 form adds the running sum in the
+    GEMM's store -- into gX where gX holds the direct term already (accumulate), into the running sum's own buffer otherwise.
+    Returns what the node hands autograd for this gradient (None once it is deposited)."""
+    st = stream_of(gX if gX is not None else jn.total)
+    if jn is None or jn.total is None:
+        call(name, (*head, ptr(gX), *tail, accumulate, st), **work)
+        if jn is None:
+            return gX
+        jn.deposit(gX)
+        return None
+    tot = jn.total
+    out = gX if accumulate else tot
+    work["nbytes"] = work.get("nbytes", 0) + 4 * tot.numel()
+    call(name, (*head, ptr(out), *tail, accumulate, st, ptr(tot)), **work)         # (the trailing argument: the *_acc2 form)
+    jn.deposit(out)
+    return None
 
 
 class _DenseFilter(torch.autograd.Function):
@@ -20,6 +42,7 @@ class _DenseFilter(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, link, kind, s, s_in, norm, b0, b1, scale_edge, scale_self, *params):
+        ctx.fan = (Fan.node_of(s), Fan.node_of(s_in))  # the operands as Fan aliases: their gradients may join the fan-in chain
         s, s_in, norm = f32c(s), f32c(s_in), f32c(norm)
         params = tuple(f32c(p) for p in params)
         require_hip(s, s_in, norm, *params)
@@ -71,8 +94,7 @@ class _DenseFilter(torch.autograd.Function):
             gs = ctx.link.gs_direct
             gs.record_stream(torch.cuda.current_stream())   # allocated by the epilogue's backward on ITS stream
         else:
-            gs = torch.empty_like(s)
-        gs_in = torch.empty_like(s) if s_in is not None else None
+            gs = torch.empty_like(s) if kind == 0 else None
         K_ = 2 * D if s_in is not None else D
         lib = _lib.load()
         if SW.GROUPED_SEGMENTS and all(params[2 * i] is not None for i in range(3)):
@@ -88,14 +110,25 @@ class _DenseFilter(torch.autograd.Function):
                     call("mrg_dense_filter_dz3", (kind, ptr(g), ptr(s), ptr(gate), ptr(norm), scale_edge, scale_self, ptr(dz), ptr(gs), b1, M, D, st),
                          nbytes=4 * M * D * (5 if kind == 0 else 2))
                 gwork = dict(nbytes=4 * M * 2 * D + 12 * D * D, flops=2 * M * D * D)
-                call("mrg_linear_bwd_input3", (ptr(dz), ptr_array(Ws), ptr(gs), ptr(_ws(wsi, s)), b0, b1, M, D, D, K_, int(kind == 0), st), **gwork)
+                jn = join(ctx.fan[0], s)
+                if kind != 0 and (jn is None or jn.total is None):
+                    gs = torch.empty_like(s)
+                gs = _bwd_input3("mrg_linear_bwd_input3", (ptr(dz), ptr_array(Ws)), (ptr(_ws(wsi, s)), b0, b1, M, D, D, K_), gs, int(kind == 0), jn,
+                                 **gwork)
+                gs_in = None
                 if s_in is not None:
-                    call("mrg_linear_bwd_input3", (ptr(dz), ptr_array([W[:, D:] for W in Ws]), ptr(gs_in), ptr(_ws(wsi, s)), b0, b1, M, D, D, K_, 0, st),
-                         **gwork)
+                    jn = join(ctx.fan[1], s)
+                    gs_in = torch.empty_like(s) if (jn is None or jn.total is None) else None
+                    gs_in = _bwd_input3("mrg_linear_bwd_input3", (ptr(dz), ptr_array([W[:, D:] for W in Ws])), (ptr(_ws(wsi, s)), b0, b1, M, D, D, K_),
+                                        gs_in, 0, jn, **gwork)
                 call("mrg_linear_bwd_weight3", (ptr(dz), ptr(s), ptr(s_in), ptr_array(gWs), ptr_array(gbs), ptr(_ws(wsw, s)), b0, b1, M, D, K_ - D, D, st),
                      nbytes=4 * M * (D + K_), flops=2 * M * K_ * D)
                 grads = [t for pair in zip(gWs, gbs) for t in pair]
                 return (None, None, gs, gs_in, None, None, None, None, None, *grads)
+        # (one launch per direction segment -- an absent segment, the lab switch: the gradients go back through autograd)
+        if gs is None:
+            gs = torch.empty_like(s)
+        gs_in = torch.empty_like(s) if s_in is not None else None
         grads = []
         segs = ((0, b0, scale_edge, True), (b0, b1, scale_edge, True), (b1, M, scale_self, False))
         work = []
@@ -201,6 +234,7 @@ class _DensePair(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, link, sums, s, s_in, norm, b0, b1, gate_only, *params):
+        ctx.fan = (Fan.node_of(s), Fan.node_of(s_in))  # the operands as Fan aliases: their gradients may join the fan-in chain
         s, s_in, norm = f32c(s), f32c(s_in), f32c(norm)
         params = tuple(f32c(p) for p in params)
         require_hip(s, s_in, norm, *params)
@@ -270,13 +304,15 @@ class _DensePair(torch.autograd.Function):
         lib = _lib.load()
         wsp = int(lib.mrg_linear_bwd_input3_pair_workspace_bytes(D, D))
         gwork = dict(nbytes=4 * M * 3 * D + 24 * D * D, flops=4 * M * D * D)
-        call("mrg_linear_bwd_input3_pair", (ptr(dz_d), ptr(dz_c), ptr_array(dW), ptr_array(cW), ptr(gs), ptr(_ws(wsp, s)), b0, b1, M, D, D, K_, 1, st),
-             nbytes=4 * M * 4 * D + 24 * D * D, flops=4 * M * D * D)
+        # (both products as members of the operands' gradient fan-in chains where the operands are Fan aliases: fanin.join)
+        gs = _bwd_input3("mrg_linear_bwd_input3_pair", (ptr(dz_d), ptr(dz_c), ptr_array(dW), ptr_array(cW)), (ptr(_ws(wsp, s)), b0, b1, M, D, D, K_),
+                         gs, 1, join(ctx.fan[0], s), nbytes=4 * M * 4 * D + 24 * D * D, flops=4 * M * D * D)
         gs_in = None
         if s_in is not None:
-            gs_in = torch.empty_like(s)
-            call("mrg_linear_bwd_input3_pair", (ptr(dz_d), ptr(dz_c), ptr_array([W[:, D:] for W in dW]), ptr_array([W[:, D:] for W in cW]), ptr(gs_in),
-                                                ptr(_ws(wsp, s)), b0, b1, M, D, D, K_, 0, st), **gwork)
+            jn = join(ctx.fan[1], s)
+            gs_in = torch.empty_like(s) if (jn is None or jn.total is None) else None
+            gs_in = _bwd_input3("mrg_linear_bwd_input3_pair", (ptr(dz_d), ptr(dz_c), ptr_array([W[:, D:] for W in dW]), ptr_array([W[:, D:] for W in cW])),
+                                (ptr(_ws(wsp, s)), b0, b1, M, D, D, K_), gs_in, 0, jn, **gwork)
         # 3. the weight gradients of the two candidates
         wsw = int(lib.mrg_linear_bwd_weight3_workspace_bytes(b0, b1, M, D, K_ - D, D))
         g_dW = [torch.empty_like(W) for W in dW]

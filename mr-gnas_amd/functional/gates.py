@@ -8,6 +8,7 @@ from .. import _lib
 from .._lib import ptr_array, call, f32c, ptr, require_hip, stream_of
 from ._base import _ws, _ws_bytes, gate_ld, same_rows
 from .candidates import Candidate, Link, wants_stats
+from .fanin import Fan, join
 
 
 class _Gate(torch.autograd.Function):
@@ -81,6 +82,7 @@ class _GateRow(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, link, sums, s, s_in, norm, b0, b1, scale, *params):
+        ctx.fan_in = Fan.node_of(s_in)                  # s_in as a Fan alias: its gradient may join the fan-in chain
         tied = s_in is not None and same_rows(s, s_in)
         s, s_in, norm = f32c(s), (None if tied else f32c(s_in)), f32c(norm)
         params = tuple(f32c(p) for p in params)
@@ -120,11 +122,21 @@ class _GateRow(torch.autograd.Function):
         gq = f32c(gq)
         M, D = s.shape
         st = stream_of(s)
-        gs_in = torch.empty_like(s) if s_in is not None else None
+        # the rank-1 term dz_r * v as a member of s_in's gradient fan-in chain (fanin.join): onto the running sum in place
+        jn = join(ctx.fan_in, s) if s_in is not None else None
+        tot = jn.total if jn is not None else None
+        gs_in = tot if tot is not None else (torch.empty_like(s) if s_in is not None else None)
         d_uvc = torch.empty(3, gate_ld(D), dtype=torch.float32, device=s.device)
         ws = _ws(_ws_bytes("mrg_gate_bwd_workspace_bytes", M, D), s)
         nb = 4 * D * M * (3 if s_in is not None else 1) + 8 * M
-        call("mrg_gate_row_bwd", (ptr(gq), ptr(hvec), ptr(s), ptr(s_in), ptr(uvc), ptr(gs_in), ptr(d_uvc), ptr(ws), b0, b1, M, D, st), nbytes=nb)
+        args = (ptr(gq), ptr(hvec), ptr(s), ptr(s_in), ptr(uvc), ptr(gs_in), ptr(d_uvc), ptr(ws), b0, b1, M, D, st)
+        if tot is not None:
+            call("mrg_gate_row_bwd", args + (ptr(tot),), nbytes=nb + 4 * D * M)       # (the trailing argument: mrg_gate_row_bwd_acc)
+        else:
+            call("mrg_gate_row_bwd", args, nbytes=nb)
+        if jn is not None:
+            jn.deposit(gs_in)
+            gs_in = None
         Ws, bs, as_ = params[0::3], params[1::3], params[2::3]
         gWs = [None if W is None else torch.empty_like(W) for W in Ws]
         gbs = [None if b is None else torch.empty_like(b) for b in bs]

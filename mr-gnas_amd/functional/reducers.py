@@ -54,18 +54,31 @@ def _seg_bwd(mode, g, graph, arg, gmsg, gself, relu_src=None, relu_bits=None):
 
 
 
-def _amax_bwd_sparse(g, mx, arg, W, graph, gy, gx):
+def _amax_bwd_ok(g, W):
+    """Does mrg_segmax_bwd_input take the shape (W within the LDS of a CU: not D = 256)?"""
+    return bool(SW.SPARSE_AMAX_BWD and g.is_cuda and _lib.load().mrg_segmax_bwd_input_ok(g.shape[1], W.shape[1]))
+
+
+def _amax_bwd_sparse(g, mx, arg, W, graph, gy, gx, chain=None):
     """a_max's backward for the fused forward: gy = the gradient w.r.t. the messages (one non-zero per (node, column): the arg-max
     edge where the maximum is positive) AND gx[:E] = gy W in one pass per edge row, without the dense input-gradient product
-    (mrg_segmax_bwd_input).  Returns False when the shape is not taken (W beyond the LDS of a CU: D = 256)."""
+    (mrg_segmax_bwd_input).  Returns False when the shape is not taken (_amax_bwd_ok).
+    chain = (total, gh, gself), each a tensor or None: the node closes a gradient fan-in chain (fanin.join) -- the kernel adds the
+    running sum and a_sum's gathered gradient in its store and writes the self rows gx[E:] = (gself + total[E:]) + g as well."""
     E, N, D = graph.num_edges(), graph.number_of_nodes(), g.shape[1]
-    if not (SW.SPARSE_AMAX_BWD and g.is_cuda and _lib.load().mrg_segmax_bwd_input_ok(D, W.shape[1])):
+    if not _amax_bwd_ok(g, W):
         return False
     p = graph.plan()
     big = 4 * D * N * 3 > ORDERED_BWD_MIN_BYTES            # the three gathered [N, D] tables beyond the caches: walk by destination
     order = p["eid"] if (ORDERED_BWD and big) else None
-    call("mrg_segmax_bwd_input", (ptr(g), ptr(mx), ptr(graph.i32("dst")), ptr(arg), ptr(W), ptr(gy), ptr(gx), ptr(order), E, N, D, W.shape[1],
-                                  stream_of(g)), nbytes=4 * E * (D + W.shape[1]) + 4 * E + 12 * N * D)
+    args = (ptr(g), ptr(mx), ptr(graph.i32("dst")), ptr(arg), ptr(W), ptr(gy), ptr(gx), ptr(order), E, N, D, W.shape[1], stream_of(g))
+    nb = 4 * E * (D + W.shape[1]) + 4 * E + 12 * N * D
+    if chain is None:
+        call("mrg_segmax_bwd_input", args, nbytes=nb)
+    else:
+        total, gh, gself = chain
+        nb += 8 * N * D + (4 * (E + N) * D if total is not None else 0) + 4 * N * D * ((gh is not None) + (gself is not None))
+        call("mrg_segmax_bwd_input", args + (ptr(total), ptr(gh), ptr(gself)), nbytes=nb)      # (trailing arguments: mrg_segmax_bwd_input_chain)
     return True
 
 class _SegReduce(torch.autograd.Function):
@@ -133,6 +146,7 @@ class _AggRows(torch.autograd.Function):
         # sum can read itself (mrg_sum_rows_gather) instead of receiving an [M, D] copy
         from .fanin import Fan                     # (fanin imports this module: resolved at call time)
         ctx.fan_node = Fan.node_of(x) if (SW.LAZY_ASUM and mode == 0 and x.is_cuda) else None
+        ctx.box = Fan.node_of(x) if x.is_cuda else None   # ... and a materialised gradient may join the fan-in chain (fanin.join)
         return out
 
     @staticmethod
@@ -159,6 +173,16 @@ class _AggRows(torch.autograd.Function):
         else:
             gx[E:].zero_()
         _seg_bwd(ctx.mode, gh, graph, arg, gx, None)
+        # the materialised gradient as a member of the fan-in chain: added onto the running sum by the K-way kernel itself (this form
+        # is the lab setting and the gradient of every further a_sum / a_mean reader of one state: it keeps the chain in reader order)
+        from .fanin import join
+        jn = join(ctx.box, gx)
+        if jn is not None:
+            if jn.total is not None:
+                call("mrg_sum_buffers", (_lib.ptr_array([gx]), 1, ptr(jn.total), gx.numel(), 1, stream_of(gx)), nbytes=12 * gx.numel())
+                gx = jn.total
+            jn.deposit(gx)
+            gx = None
         return None, gx, None, None, None
 
 
@@ -177,6 +201,8 @@ def _lin_relu_forward(ctx, mode, x, W, b, graph, partial):
     the self rows added by the reducer.  partial: returns (h, x[E:].clone()), the reducers see no self rows, and "mean" is the sum.
     Whenever the split matrix core takes the shape, the maximum runs as ONE GEMM whose epilogue is the ReLU and the segmented max, and
     the sum / mean as a GEMM whose epilogue leaves ordered run sums for the heads reducer: m is never written."""
+    from .fanin import Fan                                # (fanin imports this module: resolved at call time)
+    ctx.fan_node = Fan.node_of(x) if x.is_cuda else None  # x as a Fan alias: its gradient may join the fan-in chain
     x, W, b = f32c(x), f32c(W), f32c(b)
     require_hip(x, W, b)
     E, N, D = graph.num_edges(), graph.number_of_nodes(), x.shape[1]
@@ -240,36 +266,66 @@ def _lin_relu_backward(ctx, g, gself, partial):
     E, N, D = graph.num_edges(), graph.number_of_nodes(), x.shape[1]
     g = f32c(g) if g is not None else torch.zeros(N, D, dtype=torch.float32, device=x.device)
     st = stream_of(x)
-    gx = torch.empty_like(x)
+    # x as a Fan alias (whole graph): the gradient joins the fan-in chain (fanin.join) -- tot: the running sum so far, which this
+    # node adds in the store of its last kernel, in place
+    from .fanin import join                               # (fanin imports this module: resolved at call time)
+    sparse = fused is True and _amax_bwd_ok(g, W)        # a_max's one-pass kernel: it adds a_sum's gathered gradient as well
+    jn = join(ctx.fan_node, x, absorbs_gather=sparse) if not partial else None
+    tot = jn.total if jn is not None else None
+    gx = tot if tot is not None else torch.empty_like(x)
     gy = torch.empty(E, D, dtype=torch.float32, device=x.device)
-    own = None                                            # gx[E:], where the reducer's backward is the one to write it (a copy of g)
-    if partial and gself is not None:
-        gx[E:] = gself
-    elif partial:
-        gx[E:].zero_()
-    elif fused is True:
-        gx[E:] = g
-    else:
-        own = gx[E:]
     have_gx = False
-    if fused is True:
+    if jn is not None and sparse:
+        # a_max closes the chain in ONE pass: the running sum, a_sum's gather (if that reader left one) and the self rows too
+        gat = ctx.fan_node.gathered
+        gh = gs_ = None
+        if gat is not None and gat[2] is graph and gat[0].shape == (N, D):
+            gh, gs_, _, ev = gat
+            ctx.fan_node.gathered = None
+            cur = torch.cuda.current_stream(x.device)
+            cur.wait_event(ev)                                # the producer's stream may not be this one
+            for t in (gh, gs_):
+                if t is not None:
+                    t.record_stream(cur)
         arg, mx = saved
-        have_gx = _amax_bwd_sparse(g, mx, arg, W, graph, gy, gx)       # gy and gx[:E] in one pass, no dense product
-        if not have_gx:
-            _seg_bwd(mode, g * (mx > 0), graph, arg, gy, None)         # the winning message is ReLU-dead iff the maximum is 0
-    elif fused:
-        _seg_bwd(REDUCE[fused], g, graph, None, gy, own, relu_bits=saved[0])
+        have_gx = _amax_bwd_sparse(g, mx, arg, W, graph, gy, gx, chain=(tot, f32c(gh), f32c(gs_)))
     else:
-        y, *arg = saved                                                # arg: a_max only
-        _seg_bwd(mode, g, graph, arg[0] if arg else None, gy, own, relu_src=y)      # gy masked by ReLU
+        own = None                                            # gx[E:], where the reducer's backward is the one to write it (a copy of g)
+        if tot is not None:
+            gx[E:] += g                                       # (N node rows)
+        elif partial and gself is not None:
+            gx[E:] = gself
+        elif partial:
+            gx[E:].zero_()
+        elif fused is True:
+            gx[E:] = g
+        else:
+            own = gx[E:]
+        if fused is True:
+            arg, mx = saved
+            have_gx = tot is None and _amax_bwd_sparse(g, mx, arg, W, graph, gy, gx)      # gy and gx[:E] in one pass, no dense product
+            if not have_gx:
+                _seg_bwd(mode, g * (mx > 0), graph, arg, gy, None)         # the winning message is ReLU-dead iff the maximum is 0
+        elif fused:
+            _seg_bwd(REDUCE[fused], g, graph, None, gy, own, relu_bits=saved[0])
+        else:
+            y, *arg = saved                                                # arg: a_max only
+            _seg_bwd(mode, g, graph, arg[0] if arg else None, gy, own, relu_src=y)      # gy masked by ReLU
     work = dict(nbytes=4 * E * 2 * D + 4 * D * D, flops=2 * E * D * D)
     if not have_gx:
         wt = _ws(_ws_bytes("mrg_linear_bwd_input_workspace_bytes", D, D), x)
-        call("mrg_linear_bwd_input", (ptr(gy), ptr(W), ptr(gx), ptr(wt), E, D, D, D, 0, st), **work)
+        if tot is not None:                                   # gx[:E] = gy W + tot[:E], in place
+            call("mrg_linear_bwd_input", (ptr(gy), ptr(W), ptr(gx), ptr(wt), E, D, D, D, 0, st, ptr(gx)),      # (trailing argument: the _acc2 form)
+                 nbytes=work["nbytes"] + 4 * E * D, flops=work["flops"])
+        else:
+            call("mrg_linear_bwd_input", (ptr(gy), ptr(W), ptr(gx), ptr(wt), E, D, D, D, 0, st), **work)
     gW = torch.empty_like(W)
     gb = torch.empty(D, dtype=torch.float32, device=x.device)
     ws = _ws(_ws_bytes("mrg_linear_bwd_weight_workspace_bytes", E, D, D), x)
     call("mrg_linear_bwd_weight", (ptr(gy), ptr(x), None, ptr(gW), ptr(gb), ptr(ws), E, D, 0, D, st), **work)
+    if jn is not None:
+        jn.deposit(gx)
+        gx = None
     return None, gx, gW, gb, None
 
 

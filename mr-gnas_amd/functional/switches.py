@@ -4,6 +4,9 @@ import os
 
 ROW_FACTOR = os.environ.get("MRG_ROW_FACTOR", "1") == "1"     # lab switch: 0 = f_sparse_comp's output is stored for the epilogue
 LAZY_ASUM = os.environ.get("MRG_LAZY_ASUM", "1") == "1"     # lab switch: 0 = a_sum's [M, D] input gradient is materialised for the fan-in sum
+# lab switch: 0 = every reader of a state returns its own [rows, D] gradient and the fan-in sum adds them in a K-way pass; 1 = the readers
+# that know how (fanin.py: the dense filters, the row-factor gate, a_max / a_mean, a_sum's gather) add the running sum in their own store
+FANIN_CHAIN = os.environ.get("MRG_FANIN_CHAIN", "1") == "1"
 FUSED_AMAX = os.environ.get("MRG_FUSED_AMAX", "1") == "1"      # lab switch: 0 = linear + segmented max as separate launches
 # below this many edges the step is launch-bound and the fused form's extra launches (key memset, unpack pass, mask product)
 # cost more than the [E, D] round trip they save: 30 000-edge sampled step 18.4 vs 17.7 ms
