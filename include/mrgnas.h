@@ -823,6 +823,27 @@ int64_t mrg_transe_rank_workspace_bytes(int64_t Q, int64_t N, int D);
 int mrg_transe_rank(const float *obj, const float *ent, const int32_t *t_idx, const int64_t *qkey, const int32_t *when,
                     const int64_t *keys, const int32_t *rowptr, const int32_t *members, const int32_t *gone_at, int64_t U, int64_t Q,
                     int64_t N, int D, int64_t *ranks, void *ws, int64_t ws_bytes, void *stream);
+/* Top-k link prediction without a [Q, N] tensor (csrc/topk.hip, csrc/transe_1n.hip, csrc/topk_parts.hpp).  Additive: ABI 23.
+ *   mrg_rows_topk:   the k unfiltered entities with the largest x_e = sum_c q[i, c] * ent[e, c], largest first (mrg_rows_rank's score).
+ *   mrg_transe_topk: the k unfiltered entities with the smallest dist_e = sum_c |obj[i, c] - ent[e, c]|, smallest first
+ *                    (mrg_transe_rank's distance; the distance itself is compared).
+ * Equal values: the lower entity id first, the rule of mrg_rank_filtered.  Filter: the index and rule of the rank entry points (a member
+ * of the list of qkey[i] is excluded iff gone_at > when[i]; an unknown key, qkey[i] = -1 or U = 0 excludes nothing); there is no target, so
+ * nothing is exempt.  ids [Q][k] int32, vals [Q][k] float32: the float32 accumulator the sweep compared, bit-identical with what
+ * mrg_rows_rank / mrg_transe_rank compare for the same (query, entity) -- same cores, same tile routines -- so the rank of ids[i][j]
+ * under the same filter is j + 1.  Where fewer than k candidates remain the tail is id -1 with value -inf (rows) / +inf (transe).
+ * 1 <= k <= 64, else MRG_E_SHAPE; shapes, N and the other errors as for the rank entry points; Q == 0 returns MRG_OK with nothing
+ * launched.  No atomics: bitwise repeatable.  Workspace: mrg_*_topk_workspace_bytes(Q, N, D, k) = the split table of one block of at
+ * most 28 672 entities (rows, split core) + 16 bytes per query + the (row, tile) lists of one launch, at most 16 MiB: it does not
+ * grow with N beyond 28 672. */
+int64_t mrg_rows_topk_workspace_bytes(int64_t Q, int64_t N, int D, int k);
+int mrg_rows_topk(const float *q, const float *ent, const int64_t *qkey, const int32_t *when, const int64_t *keys, const int32_t *rowptr,
+                  const int32_t *members, const int32_t *gone_at, int64_t U, int64_t Q, int64_t N, int D, int k, int32_t *ids,
+                  float *vals, void *ws, int64_t ws_bytes, void *stream);
+int64_t mrg_transe_topk_workspace_bytes(int64_t Q, int64_t N, int D, int k);
+int mrg_transe_topk(const float *obj, const float *ent, const int64_t *qkey, const int32_t *when, const int64_t *keys,
+                    const int32_t *rowptr, const int32_t *members, const int32_t *gone_at, int64_t U, int64_t Q, int64_t N, int D, int k,
+                    int32_t *ids, float *vals, void *ws, int64_t ws_bytes, void *stream);
 /* sf_TransE_op.forward, reference models/operations_lp.py:101-112:
  *   score[b, n] = sigmoid(gamma - sum_c |sub[b, c] + rel[b, c] - ent[n, c]|)
  * backward: gobj [B][D] (the gradient of both sub and rel) and gent [N][D]; either may be NULL.

@@ -139,6 +139,10 @@ SIGNATURES = {
     "mrg_transe_dist_bwd": (_I, [_P, _P, _P, _L, _P, _P, _I, _L, _L, _I, _P]),
     "mrg_transe_rank_workspace_bytes": (_L, [_L, _L, _I]),
     "mrg_transe_rank": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _L, _L, _L, _I, _P, _P, _L, _P]),
+    "mrg_rows_topk_workspace_bytes": (_L, [_L, _L, _I, _I]),
+    "mrg_rows_topk": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _L, _L, _L, _I, _I, _P, _P, _P, _L, _P]),
+    "mrg_transe_topk_workspace_bytes": (_L, [_L, _L, _I, _I]),
+    "mrg_transe_topk": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _L, _L, _L, _I, _I, _P, _P, _P, _L, _P]),
     "mrg_transe_score_fwd": (_I, [_P, _P, _P, _F, _P, _L, _L, _I, _P]),
     "mrg_transe_score_bwd": (_I, [_P, _P, _P, _P, _P, _P, _P, _L, _L, _I, _P]),
     "mrg_ccorr_rows": (_I, [_I, _P, _P, _P, _L, _I, _P]),

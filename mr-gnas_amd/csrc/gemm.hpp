@@ -50,6 +50,12 @@ enum { EPI_BCE = 10, EPI_BCE_GRAD = 11 };
 // sum (functional/fanin.py): its own term first, then the sum so far.  Cin2 may be C itself.  Kernel instances of their own.
 enum { EPI_ACCUM2 = 12 };
 constexpr bool epi_accum(int epi) { return epi == EPI_ACCUM || epi == EPI_ACCUM2; }
+// The selecting epilogue of mrg_rows_topk (topk.hip defines gemm_epilogue_topk and what it reads): rows are queries, columns are
+// entities, every (row, workgroup) leaves its k best unfiltered (value, id) pairs.  Kernel instances of their own.
+enum { EPI_TOPK = 13 };
+struct GemmArgs;
+template <int NT>
+__device__ __forceinline__ void gemm_epilogue_topk(const GemmArgs& a, f32x16 (&acc)[NT], int64_t rowbase, int col0, int li, int lh);
 
 // Up to three row ranges of ONE launch of the split-core row GEMM that share every tensor but differ in the weight matrix
 // (the in / out / self direction segments of a dense filter: one launch instead of three).  Workgroup blocks
@@ -779,6 +785,7 @@ __global__ __launch_bounds__(MRG_BLOCK, (MT == 1 ? 2 : 1)) void rowgemm_k(GemmAr
     if constexpr (EPI == EPI_BCE_GRAD) gemm_epilogue_bce_grad<NT>(a, acc[m], row0 + wave * 32 * MT + m * 32, col0, li, lh, row0 + GBM <= a.rows);
     else if constexpr (EPI == EPI_RANK) gemm_epilogue_rank<NT>(a, acc[m], row0 + wave * 32 * MT + m * 32, col0, li, lh);
     else if constexpr (EPI == EPI_RANK_DIAG) gemm_epilogue_rank_diag<NT>(a, acc[m], row0 + wave * 32 * MT + m * 32, wave, li, lh);
+    else if constexpr (EPI == EPI_TOPK) gemm_epilogue_topk<NT>(a, acc[m], row0 + wave * 32 * MT + m * 32, col0, li, lh);
     else gemm_epilogue<NT, EPI>(a, acc[m], row0 + wave * 32 * MT + m * 32, col0, li, lh, row0 + GBM <= a.rows);
   }
 }

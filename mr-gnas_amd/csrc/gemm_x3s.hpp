@@ -164,6 +164,7 @@ __global__ __launch_bounds__(256, 2) void rowgemm_x3s_k(GemmArgs a, const char* 
   else if constexpr (EPI == EPI_SEGSUM) gemm_epilogue_segsum<NT>(a, acc, roww, col0, li, lh);
   else if constexpr (EPI == EPI_RANK) gemm_epilogue_rank<NT>(a, acc, roww, col0, li, lh);
   else if constexpr (EPI == EPI_RANK_DIAG) gemm_epilogue_rank_diag<NT>(a, acc, roww, wave, li, lh);
+  else if constexpr (EPI == EPI_TOPK) gemm_epilogue_topk<NT>(a, acc, roww, col0, li, lh);
   else if constexpr (EPI == EPI_BCE) gemm_bce_flush(a, gemm_epilogue_bce<NT>(a, acc, roww, col0, li, lh), reinterpret_cast<double*>(smem_b));
   else if constexpr (EPI == EPI_BCE_GRAD) gemm_epilogue_bce_grad<NT>(a, acc, roww, col0, li, lh, row0 + GBM <= a.rows);
   else gemm_epilogue<NT, EPI>(a, acc, roww, col0, li, lh, row0 + GBM <= a.rows);

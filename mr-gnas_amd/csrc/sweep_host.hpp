@@ -27,11 +27,12 @@ template <class... P>
 inline bool sweep_labels_ok(int64_t U, const P*... p) { return U <= 0 || (... && (p != nullptr)); }
 
 // The launch grid of a blocked sweep over the columns [c0, c1) of rows_all rows in workgroup tiles of tile_rows x tile_cols: column blocks
-// of BCE_COLS outermost (the row GEMM splits the entity rows once per block), row chunks of RANK_CHUNK inside.  The ONE definition of
+// of BCE_COLS outermost (the row GEMM splits the entity rows once per block), row chunks of row_chunk inside.  The ONE definition of
 // it: a sweep launches through each(), a plan sizes the per-workgroup partials with workgroups(), which walks the same loop.
 struct SweepGrid {
   int64_t rows_all, c0, c1;
   int tile_rows, tile_cols;
+  int64_t row_chunk = RANK_CHUNK;     // rows per launch; a sweep that keeps per-(row, tile) partials sets less (topk_parts.hpp)
   unsigned row_tiles(int64_t rows) const { return (unsigned)((rows + tile_rows - 1) / tile_rows); }
   unsigned col_tiles(int64_t nc) const { return (unsigned)((nc + tile_cols - 1) / tile_cols); }
   // launch(q0, rows, c, nc, wg0): rows [q0, q0 + rows) x columns [c, c + nc) on a grid of row_tiles(rows) x col_tiles(nc) workgroups;
@@ -41,8 +42,8 @@ struct SweepGrid {
     int64_t wg = 0;
     for (int64_t c = c0; c < c1; c += BCE_COLS) {
       const int64_t nc = c1 - c < BCE_COLS ? c1 - c : BCE_COLS;
-      for (int64_t q0 = 0; q0 < rows_all; q0 += RANK_CHUNK) {
-        const int64_t rows = rows_all - q0 < RANK_CHUNK ? rows_all - q0 : RANK_CHUNK;
+      for (int64_t q0 = 0; q0 < rows_all; q0 += row_chunk) {
+        const int64_t rows = rows_all - q0 < row_chunk ? rows_all - q0 : row_chunk;
         const int rc = launch(q0, rows, c, nc, wg);
         if (rc != MRG_OK) return rc;
         wg += (int64_t)row_tiles(rows) * col_tiles(nc);

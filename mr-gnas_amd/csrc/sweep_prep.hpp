@@ -39,12 +39,9 @@ static __global__ __launch_bounds__(256) void bce_finish_k(const double* __restr
   if (threadIdx.x == 0) loss[0] = (float)(s[0] * scale);
 }
 
-// qinfo[i] = {target, begin, end of the list of qkey[i] (empty when the key is -1 or unknown), when}; counts[i] = 0
-static __global__ void rank_prep_k(const int32_t* __restrict__ t_idx, const int64_t* __restrict__ qkey, const int32_t* __restrict__ when,
-                                   const int64_t* __restrict__ keys, const int32_t* __restrict__ rowptr, int64_t U, int64_t Q,
-                                   int32_t* __restrict__ qinfo, unsigned* __restrict__ counts) {
-  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= Q) return;
+// {begin, end} of the filter list of query i's key (empty when there is no index, or the key is -1 or unknown)
+__device__ __forceinline__ int2 sweep_filter_list(const int64_t* __restrict__ qkey, const int64_t* __restrict__ keys,
+                                                  const int32_t* __restrict__ rowptr, int64_t U, int64_t i) {
   int lo = 0, hi = 0;
   const int64_t key = (qkey && U > 0) ? qkey[i] : -1;
   if (key >= 0) {
@@ -55,8 +52,30 @@ static __global__ void rank_prep_k(const int32_t* __restrict__ t_idx, const int6
     }
     if (b < U && keys[b] == key) { lo = rowptr[b]; hi = rowptr[b + 1]; }
   }
-  *reinterpret_cast<int4*>(qinfo + i * 4) = make_int4(t_idx[i], lo, hi, when ? when[i] : -1);
+  return make_int2(lo, hi);
+}
+
+// qinfo[i] = {target, begin, end of the list of qkey[i] (empty when the key is -1 or unknown), when}; counts[i] = 0
+static __global__ void rank_prep_k(const int32_t* __restrict__ t_idx, const int64_t* __restrict__ qkey, const int32_t* __restrict__ when,
+                                   const int64_t* __restrict__ keys, const int32_t* __restrict__ rowptr, int64_t U, int64_t Q,
+                                   int32_t* __restrict__ qinfo, unsigned* __restrict__ counts) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= Q) return;
+  const int2 l = sweep_filter_list(qkey, keys, rowptr, U, i);
+  *reinterpret_cast<int4*>(qinfo + i * 4) = make_int4(t_idx[i], l.x, l.y, when ? when[i] : -1);
   counts[i] = 0;
+}
+
+// The top-k sweeps' form of rank_prep_k: there is no target (qinfo[i].x = -1, an id no candidate has), and instead of a count the
+// query's running list ids / vals [Q][k] starts empty: id -1, value `pad`.
+static __global__ void topk_prep_k(const int64_t* __restrict__ qkey, const int32_t* __restrict__ when, const int64_t* __restrict__ keys,
+                                   const int32_t* __restrict__ rowptr, int64_t U, int64_t Q, int k, float pad, int32_t* __restrict__ qinfo,
+                                   int32_t* __restrict__ ids, float* __restrict__ vals) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= Q) return;
+  const int2 l = sweep_filter_list(qkey, keys, rowptr, U, i);
+  *reinterpret_cast<int4*>(qinfo + i * 4) = make_int4(-1, l.x, l.y, when ? when[i] : -1);
+  for (int t = 0; t < k; ++t) { ids[i * k + t] = -1; vals[i * k + t] = pad; }
 }
 
 static __global__ void rank_finish_k(const unsigned* __restrict__ counts, int64_t* __restrict__ ranks, int64_t Q) {

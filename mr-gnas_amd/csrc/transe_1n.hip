@@ -19,12 +19,14 @@
 // Labels / filters of a tile: thread r < 64 walks the slice of tile row r's ascending list that falls into the tile's 64 entities
 // (binary search for its start, as gemm_bce_label_words does) and leaves a 64-bit mask in LDS.
 #include "sweep_host.hpp"      // the launch bounds, SweepGrid, the workspace's rounding and base, the checks; the prep / finish kernels
+#include "topk_parts.hpp"      // L1_TOPK: the order, the per-tile selection, the merge
 
 namespace mrg {
 
 constexpr int L1_T = 64;            // tile: 64 queries x 64 entities
 constexpr int L1_C = 32;            // columns per LDS slice
-enum { L1_LOSS = 0, L1_DLOGIT = 1, L1_RANK = 2 };
+enum { L1_LOSS = 0, L1_DLOGIT = 1, L1_RANK = 2, L1_TOPK = 3 };
+constexpr bool l1_filters(int epi) { return epi == L1_RANK || epi == L1_TOPK; }      // the tile's mask: filtered members, read through qinfo
 
 struct L1Args {
   const float* obj;           // [rows][D]: the launch's query rows
@@ -34,9 +36,9 @@ struct L1Args {
   int e0;                     // entity id of the launch's column 0
   float gamma;
   const int32_t* qlist;       // L1_LOSS / L1_DLOGIT: [rows][2] begin and end of the query's object list in `list`
-  const int32_t* qinfo;       // L1_RANK: [rows][4] target, begin and end of the filter list in `list` / gone_at, `when`
+  const int32_t* qinfo;       // L1_RANK / L1_TOPK: [rows][4] target (L1_TOPK: -1), begin and end of the filter list in `list` / gone_at, `when`
   const int32_t* list;        // entity ids, ascending inside a list
-  const int32_t* gone_at;     // L1_RANK: per member, filtered iff gone_at > when
+  const int32_t* gone_at;     // L1_RANK / L1_TOPK: per member, filtered iff gone_at > when
   float v_zero, v_one;
   double* partial;            // L1_LOSS: [gridDim.y][gridDim.x]
   const float* gscale;        // L1_DLOGIT: [1] on the device
@@ -44,6 +46,10 @@ struct L1Args {
   int64_t ld;
   const float* tdist;         // L1_RANK: [rows] the target's distance (l1_target_k)
   unsigned* counts;           // L1_RANK: [rows], zeroed
+  TopkEnt* part;              // L1_TOPK: [rows][gridDim.x][k] the (row, tile) lists
+  int k;
+  const float* run_vals;      // L1_TOPK: [rows][k] the rows' running lists after the column blocks swept so far: their k-th entry prunes
+  const int32_t* run_ids;
 };
 
 // tdist[i] = sum_c |obj[i, c] - ent[target_i, c]|, the sweep's chain
@@ -75,7 +81,7 @@ __global__ __launch_bounds__(256) void l1_sweep_k(const L1Args a) {
     const int64_t row = row0 + tid;
     if (row < a.rows) {
       int lo, hi, when = 0;
-      if constexpr (EPI == L1_RANK) {
+      if constexpr (l1_filters(EPI)) {
         const int4 qi = *reinterpret_cast<const int4*>(a.qinfo + row * 4);
         lo = qi.y; hi = qi.z; when = qi.w;
       } else {
@@ -92,7 +98,7 @@ __global__ __launch_bounds__(256) void l1_sweep_k(const L1Args a) {
         for (; b < hi; ++b) {
           const int id = a.list[b];
           if (id >= cend) break;
-          if constexpr (EPI == L1_RANK) { if (a.gone_at[b] > when) m |= 1ull << (id - cbeg); }
+          if constexpr (l1_filters(EPI)) { if (a.gone_at[b] > when) m |= 1ull << (id - cbeg); }
           else m |= 1ull << (id - cbeg);
         }
       }
@@ -203,6 +209,22 @@ __global__ __launch_bounds__(256) void l1_sweep_k(const L1Args a) {
         if (cok[j]) out[j] = gs * (p - y) * (pq1 / fmaxf(pq1, 1e-12f));
       }
     }
+  } else if constexpr (EPI == L1_TOPK) {
+    // a row's 64 columns sit in the 16 consecutive lanes tx of micro-tile row ty, four per lane: topk_select's layout
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      float v[4];
+      int id[4];
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const bool ok = cok[j] && !((mrow[i] >> j) & 1ull);
+        v[j] = ok ? acc[i][j] : topk_pad<false>();
+        id[j] = ok ? a.e0 + col0 + tx * 4 + j : TOPK_NONE;
+      }
+      const int64_t row = row0 + ty * 4 + i;
+      const int64_t kth = (rok[i] ? row : a.rows - 1) * a.k + a.k - 1;
+      topk_select<false, 16, 4>(v, id, a.run_vals[kth], a.run_ids[kth], a.k, a.part + (row * gridDim.x + blockIdx.x) * a.k, rok[i]);
+    }
   } else {
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
@@ -227,7 +249,9 @@ __global__ __launch_bounds__(256) void l1_sweep_k(const L1Args a) {
   }
 }
 
-inline SweepGrid l1_grid(int64_t rows_all, int64_t c0, int64_t c1) { return SweepGrid{rows_all, c0, c1, L1_T, L1_T}; }
+inline SweepGrid l1_grid(int64_t rows_all, int64_t c0, int64_t c1, int64_t row_chunk = RANK_CHUNK) {
+  return SweepGrid{rows_all, c0, c1, L1_T, L1_T, row_chunk};
+}
 
 struct L1Plan { size_t qlist, partial, total; int64_t nparts; };
 // ncols: the columns a call sweeps (N for the forward, c1 - c0 for the logit gradient)
@@ -253,15 +277,18 @@ inline L1RankPlan l1_rank_plan(int64_t Q) {
 }
 
 // The sweep over the columns [c0, c1) of all rows on l1_grid: column blocks of BCE_COLS outermost, row chunks of RANK_CHUNK inside.  `all`
-// carries what does not change from launch to launch; L1_LOSS appends its launches' partials at all.partial.
-template <int EPI>
-static int l1_sweep(const L1Args& all, const float* obj, const float* ent, int64_t rows_all, int64_t c0, int64_t c1, hipStream_t st) {
+// carries what does not change from launch to launch; L1_LOSS appends its launches' partials at all.partial.  L1_TOPK: every launch fills
+// all.part, and after(q0, rows, column tiles) follows it (the merge into the running lists).
+template <int EPI, class AFTER>
+static int l1_sweep(const L1Args& all, const float* obj, const float* ent, int64_t rows_all, int64_t c0, int64_t c1, hipStream_t st,
+                    int64_t row_chunk, AFTER&& after) {
   const bool vec = all.D % 4 == 0 && aligned16(obj) && aligned16(ent);
-  const SweepGrid sg = l1_grid(rows_all, c0, c1);
+  const SweepGrid sg = l1_grid(rows_all, c0, c1, row_chunk);
   return sg.each([&](int64_t q0, int64_t rows, int64_t c, int64_t nc, int64_t wg0) {
     L1Args a = all;
     a.obj = obj + q0 * a.D; a.ent = ent + c * a.D; a.rows = rows; a.ncols = (int)nc; a.e0 = (int)c;
     if (EPI == L1_RANK) { a.qinfo = all.qinfo + q0 * 4; a.tdist = all.tdist + q0; a.counts = all.counts + q0; }
+    else if (EPI == L1_TOPK) { a.qinfo = all.qinfo + q0 * 4; a.run_vals = all.run_vals + q0 * a.k; a.run_ids = all.run_ids + q0 * a.k; }
     else a.qlist = all.qlist + q0 * 2;
     if (EPI == L1_DLOGIT) a.dl = all.dl + q0 * a.ld + (c - c0);
     if (EPI == L1_LOSS) a.partial = all.partial + wg0;
@@ -269,8 +296,12 @@ static int l1_sweep(const L1Args& all, const float* obj, const float* ent, int64
     if (vec) hipLaunchKernelGGL((l1_sweep_k<EPI, true>), grid, dim3(256), 0, st, a);
     else hipLaunchKernelGGL((l1_sweep_k<EPI, false>), grid, dim3(256), 0, st, a);
     MRG_LAUNCH_CHECK();
-    return (int)MRG_OK;
+    return (int)after(q0, rows, (int)grid.x);
   });
+}
+template <int EPI>
+static int l1_sweep(const L1Args& all, const float* obj, const float* ent, int64_t rows_all, int64_t c0, int64_t c1, hipStream_t st) {
+  return l1_sweep<EPI>(all, obj, ent, rows_all, c0, c1, st, RANK_CHUNK, [](int64_t, int64_t, int) { return (int)MRG_OK; });
 }
 
 }  // namespace mrg
@@ -354,4 +385,35 @@ extern "C" int mrg_transe_rank(const float* obj, const float* ent, const int32_t
   rc = l1_sweep<L1_RANK>(a, obj, ent, Q, 0, N, st);
   if (rc != MRG_OK) return rc;
   return sweep_launch_rows(rank_finish_k, Q, st, counts, ranks, Q);
+}
+
+// mrg_rows_topk on the L1 distance: the k unfiltered entities nearest to every query row, nearest first (topk_parts.hpp).  The
+// distances are l1_sweep_k's accumulators, the ones mrg_transe_rank compares.
+static_assert(TopkTileCheck<L1_T, L1_T>::ok, "");
+
+extern "C" int64_t mrg_transe_topk_workspace_bytes(int64_t Q, int64_t N, int D, int k) {
+  if (!sweep_shape_ok(Q, N, D, false) || !topk_k_ok(k)) return MRG_E_SHAPE;
+  return (int64_t)topk_plan(Q, N, k, L1_T, L1_T, 0).total;
+}
+
+extern "C" int mrg_transe_topk(const float* obj, const float* ent, const int64_t* qkey, const int32_t* when, const int64_t* keys,
+                               const int32_t* rowptr, const int32_t* members, const int32_t* gone_at, int64_t U, int64_t Q, int64_t N, int D,
+                               int k, int32_t* ids, float* vals, void* ws, int64_t ws_bytes, void* stream) {
+  if (U < 0 || !sweep_shape_ok(Q, N, D, false) || !topk_k_ok(k)) return MRG_E_SHAPE;
+  if (Q == 0) return MRG_OK;
+  if (!obj || !ent || !ids || !vals) return MRG_E_NULLPTR;
+  if (!sweep_labels_ok(U, qkey, when, keys, rowptr, members, gone_at)) return MRG_E_NULLPTR;
+  const TopkPlan p = topk_plan(Q, N, k, L1_T, L1_T, 0);
+  if (!ws || ws_bytes < (int64_t)p.total) return MRG_E_WORKSPACE;
+  hipStream_t st = (hipStream_t)stream;
+  char* w = sweep_ws_base(ws);
+  int32_t* qinfo = (int32_t*)(w + p.qinfo);
+  TopkEnt* part = (TopkEnt*)(w + p.part);
+  int rc = sweep_launch_rows(topk_prep_k, Q, st, qkey, when, keys, rowptr, U, Q, k, topk_pad<false>(), qinfo, ids, vals);
+  if (rc != MRG_OK) return rc;
+  L1Args a{};
+  a.D = D; a.qinfo = qinfo; a.list = members; a.gone_at = gone_at; a.part = part; a.k = k; a.run_vals = vals; a.run_ids = ids;
+  return l1_sweep<L1_TOPK>(a, obj, ent, Q, 0, N, st, p.chunk, [&](int64_t q0, int64_t rows, int ntile) {
+    return topk_merge_launch<false>(part, ntile, k, rows, ids + q0 * k, vals + q0 * k, st);
+  });
 }

@@ -14,6 +14,9 @@ module: ``calc_mrr`` / ``calc_raw_mrr`` / ``calc_filtered_mrr`` / ``infer_graph`
 without a [B, N] tensor, over ``query_ranks`` (``mrg_rows_rank`` / ``mrg_transe_rank``).  ``distmult_ranks`` and ``query_ranks`` share
 their filter side and their call (``_filter_side``, ``_rank_call``); the three ``predict`` passes share their per-batch statistics
 vector and their one device -> host copy (``_stats_begin``, ``_batch_stats``, ``_stats_end``).
+
+``query_topk`` / ``predict_topk`` answer (s, r, ?): the k best unfiltered entities per query from the same sweeps
+(``mrg_rows_topk`` / ``mrg_transe_topk``), again without a [B, N] tensor.
 """
 import torch
 import torch.nn.functional as F
@@ -272,6 +275,76 @@ def query_ranks(q, ent, target, known_side=None, when=None, qkey=None, kind="dot
     side = _filter_side("query_ranks: a filtered call needs when [Q] and qkey [Q]", known_side, when, qkey, Q)
     name, ws_name = ("mrg_rows_rank", "mrg_distmult_rank_workspace_bytes") if kind == "dot" else ("mrg_transe_rank", "mrg_transe_rank_workspace_bytes")
     return _rank_call(name, ws_name, name, (q, ent, target), side, Q, N, D, q)
+
+
+_TOPK_MAX = 64
+
+
+def query_topk(q, ent, k, known_side=None, when=None, qkey=None, kind="dot"):
+    """(ids [Q, k] int64, values [Q, k] float32): per query row of q [Q, D] the k best unfiltered entities, best first, without a
+    [Q, N] tensor -- the twin of query_ranks.  kind "dot": the largest logits q . ent[e] (mrg_rows_topk); kind "l1": the smallest
+    distances ||q - ent[e]||_1 (mrg_transe_topk).  Equal values: the lower entity id first.  known_side / when / qkey as in
+    query_ranks; there is no target, so every member with gone_at > when is excluded.  values are the float32 accumulators the rank
+    sweeps compare, so query_ranks(q, ent, ids[:, j], ...) == j + 1.  Where fewer than k candidates remain the tail is id -1 with
+    value -inf ("dot") / +inf ("l1")."""
+    if kind not in ("dot", "l1"):
+        raise ValueError("query_topk: kind is 'dot' or 'l1'")
+    k = int(k)
+    if not 1 <= k <= _TOPK_MAX:
+        raise ValueError(f"query_topk: 1 <= k <= {_TOPK_MAX} (got {k}); for a longer list run the dense forward, model(g, subj, rel), "
+                         "and torch.topk")
+    if not (q.is_cuda and ent.is_cuda):
+        raise MrgnasError("query_topk runs on a HIP device (no CPU fallback)")
+    q, ent = f32c(q), f32c(ent)
+    require_hip(q, ent)
+    if q.dim() != 2 or ent.dim() != 2 or ent.shape[1] != q.shape[1]:
+        raise ValueError("query_topk: q [Q, D] and ent [N, D] expected")
+    (Q, D), N = q.shape, ent.shape[0]
+    side = _filter_side("query_topk: a filtered call needs when [Q] and qkey [Q]", known_side, when, qkey, Q)
+    name = "mrg_rows_topk" if kind == "dot" else "mrg_transe_topk"
+    ids = torch.empty(Q, k, dtype=torch.int32, device=q.device)
+    vals = torch.empty(Q, k, dtype=torch.float32, device=q.device)
+    nbytes = getattr(load(), name + "_workspace_bytes")(Q, N, D, k)
+    if nbytes < 0:
+        check(int(nbytes), name)
+    ws = torch.empty(max(int(nbytes), 1), dtype=torch.uint8, device=q.device)
+    call(name, (ptr(q), ptr(ent), *(ptr(t) for t in side[:6]), side[6], Q, N, D, k, ptr(ids), ptr(vals), ptr(ws), int(nbytes), stream_of(q)),
+         nbytes=4 * (Q + N) * D, flops=2 * Q * N * D)
+    return ids.long(), vals
+
+
+def predict_topk(model, g, subj, rel, k, label_index=None):
+    """(objects [B, k] int64, probabilities [B, k] float32): the k most probable objects of every query (subj[b], rel[b], ?) of a
+    network whose scorer follows the scorer protocol (operations_lp: ``query`` and ``score_kind``), most probable first, without the
+    [B, N] matrix of model(g, subj, rel).  rel follows the loaders' convention (r + num_rel asks for heads).  Eval mode, no autograd,
+    one model.embed(g) and one score_func.query.  label_index: a sampler.LabelIndex whose known objects of (subj[b], rel[b]) are
+    excluded (the filter of predict_1n with no target); None for raw results.  Probabilities are sigmoid(logit), or
+    sigmoid(gamma - distance) for TransE; where fewer than k objects remain the tail is object -1 with probability 0."""
+    from . import functional as K
+    sf = model.score_func
+    kind = getattr(sf, "score_kind", None)
+    if not hasattr(sf, "query") or kind not in ("dot", "l1"):
+        raise MrgnasError(f"predict_topk needs a scorer with query() and a score_kind of 'dot' or 'l1'; this network scores with {type(sf).__name__}")
+    if not (next(model.parameters()).is_cuda and subj.is_cuda and rel.is_cuda):
+        raise MrgnasError("predict_topk runs on a HIP device (no CPU fallback)")
+    if not 1 <= int(k) <= _TOPK_MAX:
+        raise ValueError(f"predict_topk: 1 <= k <= {_TOPK_MAX} (got {k}); for a longer list run the dense forward, model(g, subj, rel), "
+                         "and torch.topk")
+    with torch.no_grad():
+        model.eval()
+        s, r = subj.int().contiguous(), rel.int().contiguous()
+        ent, rel_emb = model.embed(g)
+        ent = f32c(ent)
+        q = f32c(sf.query(K.gather_rows(ent, s), K.gather_rows(f32c(rel_emb), r)))
+        if label_index is None:
+            ids, vals = query_topk(q, ent, k, kind=kind)
+        else:
+            side = _LabelSide(label_index)
+            when = torch.full((s.numel(),), -1, dtype=torch.int32, device=q.device)
+            qkey = (s.long() * side.num_rels + r.long()).contiguous()
+            ids, vals = query_topk(q, ent, k, side, when, qkey, kind)
+        prob = torch.sigmoid(sf.gamma - vals) if kind == "l1" else torch.sigmoid(vals)
+        return ids, torch.where(ids >= 0, prob, torch.zeros_like(prob))
 
 
 def _both_passes(embedding, w, test, eval_bz, known, protocol):

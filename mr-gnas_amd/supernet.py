@@ -454,6 +454,12 @@ class FixedNetwork(nn.Module):
             raise MrgnasError("loss_fused runs on a HIP device (no CPU fallback); the network is on " + str(self.embedding_h.weight.device))
         return self.loss_1n(g, subj, rel, label_index, label_smooth)
 
+    def predict_topk(self, g, subj, rel, k, label_index=None):
+        """(objects [B, k] int64, probabilities [B, k] float32) of the queries (subj[b], rel[b], ?), most probable first, without the
+        [B, N] matrix of forward(): evaluation.predict_topk."""
+        from .evaluation import predict_topk
+        return predict_topk(self, g, subj, rel, k, label_index)
+
     def loss_1n(self, g, subj, rel, label_index, label_smooth=0.0, col_chunk=None):
         """loss_fused for every scorer that follows the scorer protocol (operations_lp: ``query`` and ``score_kind``): one embed(g), the
         query rows q = score_func.query(ent[subj], rel_emb[rel]), then functional.rows_bce_all on them by the scorer's kind ("dot":
