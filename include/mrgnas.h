@@ -844,6 +844,44 @@ int64_t mrg_transe_topk_workspace_bytes(int64_t Q, int64_t N, int D, int k);
 int mrg_transe_topk(const float *obj, const float *ent, const int64_t *qkey, const int32_t *when, const int64_t *keys,
                     const int32_t *rowptr, const int32_t *members, const int32_t *gone_at, int64_t U, int64_t Q, int64_t N, int D, int k,
                     int32_t *ids, float *vals, void *ws, int64_t ws_bytes, void *stream);
+/* The score-function search leg without a [B, N] tensor (csrc/sf_mix_1n.hip): the 1-N loss, its gradients and the filtered ranks under
+ * the mixed score of MixedOp_SF over SF_OPS = [sf_TransE, sf_DisMult] (reference models/cell_lp.py:36-50, 71-86, 191-200; the
+ * supernet's score_f, models/model_search_lp.py:160-161).  Additive: ABI 23.
+ *   dist[b, e] = sum_c |obj[b, c] - ent[e, c]|  (obj [B][D] = sub + rel),  dot[b, e] = sum_c qd[b, c] * ent[e, c]  (qd [B][D] = sub * rel),
+ *   both operands float32 and formed by the caller;  p0 = sigmoid(gamma - dist), p1 = sigmoid(dot), p = w[0] * p0 + w[1] * p1 in float32
+ *   with every product and the sum rounded on its own.  w: [2] float32 ON THE DEVICE, TransE's weight first (no host synchronisation).
+ *   dist is one float32 accumulator over c ascending (bit-identical with mrg_transe_score_fwd's), dot one float32 fused multiply-add
+ *   chain over c ascending.
+ * mrg_sfmix_bce_fwd:  loss[0] = mean over b, e of (y - 1) * max(log1p(-p), -100) - y * max(log p, -100), labels as for
+ *   mrg_distmult_bce_fwd (index keys / rowptr / objs, key qkey[b], v_zero / v_one), summed in float64 -- lane, wave, workgroup, then one
+ *   partial per workgroup added in a fixed order: no float atomics, bitwise repeatable.
+ * mrg_sfmix_bce_grad: for the entities [c0, c1), with G = gscale[0] * (p - y) / max((1 - p) p, 1e-12) (torch's
+ *   binary_cross_entropy_backward; gscale: one float on the device, the upstream gradient divided by B * N):
+ *     dl0 [B][c1 - c0] = (G w[0]) ((1 - p0) p0)   the gradient with respect to x0 = gamma - dist   (feeds mrg_transe_dist_bwd)
+ *     dl1 [B][c1 - c0] = (G w[1]) ((1 - p1) p1)   the gradient with respect to x1 = dot            (feeds the row GEMM's gradients)
+ *   each exactly 0 where its component saturates, and dw[k] = sum over b and the entities [c0, c1) of G p_k: two float64 partials per
+ *   workgroup added in a fixed order, WRITTEN to dw [2] (float32) when c0 == 0 and ADDED to it otherwise -- a caller sweeps its column
+ *   chunks in ascending order.  G p_k is not clamped where p itself saturates (neither is the dense formulation's).
+ * mrg_sfmix_rank: ranks[i] = 1 + #(p_e > p_t) + #(p_e == p_t, e < t) over candidates e != t = t_idx[i] that are not filtered:
+ *   mrg_transe_rank's rule and filter (index, gone_at > when) on the float32 p itself; the target's p is formed by the same two chains and
+ *   the same expression, so a duplicate of the target's row ties exactly.  Integer atomics only.
+ * Workspace: mrg_sfmix_bce_workspace_bytes(B, N, D) for the forward and (B, c1 - c0, D) for the gradient: two integers per query and two
+ * float64 per tile of 64 x 64 elements; mrg_sfmix_rank_workspace_bytes(Q, N, D), O(Q) bytes.  1 <= D <= 1024, N bounded as for
+ * mrg_distmult_rank; indices are trusted.  Argument errors are returned before any HIP call; B == 0 / Q == 0 returns MRG_OK with nothing
+ * launched. */
+int64_t mrg_sfmix_bce_workspace_bytes(int64_t B, int64_t ncols, int D);
+int mrg_sfmix_bce_fwd(const float *obj, const float *qd, const float *ent, const float *w, const int64_t *qkey, const int64_t *keys,
+                      const int32_t *rowptr, const int32_t *objs, int64_t U, float gamma, float v_zero, float v_one, int64_t B, int64_t N,
+                      int D, float *loss, void *ws, int64_t ws_bytes, void *stream);
+int mrg_sfmix_bce_grad(const float *obj, const float *qd, const float *ent, const float *w, const int64_t *qkey, const int64_t *keys,
+                       const int32_t *rowptr, const int32_t *objs, int64_t U, float gamma, float v_zero, float v_one, int64_t B, int64_t N,
+                       int D, int64_t c0, int64_t c1, const float *gscale, float *dl0, float *dl1, float *dw, void *ws, int64_t ws_bytes,
+                       void *stream);
+int64_t mrg_sfmix_rank_workspace_bytes(int64_t Q, int64_t N, int D);
+int mrg_sfmix_rank(const float *obj, const float *qd, const float *ent, const float *w, float gamma, const int32_t *t_idx,
+                   const int64_t *qkey, const int32_t *when, const int64_t *keys, const int32_t *rowptr, const int32_t *members,
+                   const int32_t *gone_at, int64_t U, int64_t Q, int64_t N, int D, int64_t *ranks, void *ws, int64_t ws_bytes,
+                   void *stream);
 /* sf_TransE_op.forward, reference models/operations_lp.py:101-112:
  *   score[b, n] = sigmoid(gamma - sum_c |sub[b, c] + rel[b, c] - ent[n, c]|)
  * backward: gobj [B][D] (the gradient of both sub and rel) and gent [N][D]; either may be NULL.

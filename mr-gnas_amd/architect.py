@@ -11,6 +11,8 @@ Two things the reference does, which a restatement from the DARTS paper would mi
   gradients only at the end of ``train()``, and so the weight step that follows is taken on the sum of the validation and the training
   gradients;
 * the score-function alpha (the fifth architecture parameter) never receives a gradient: Adam skips it, its step count stays 0.
+  That describes ``supernet.SearchNetwork``; ``supernet.ScoreSearchNetwork``, whose loss ends in the score-function cell, is the
+  exception: there the fifth alpha is stepped like the other four.
 
 ``unrolled=True`` (the second-order step) cannot run in the reference -- it calls ``model.new()``, which models/model_search_lp.py has
 commented out -- and raises here.

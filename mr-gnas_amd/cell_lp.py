@@ -4,9 +4,12 @@ registry and -- when handed CUDA tensors -- on the fused HIP MixedOp path.
 
     reference                                              here
     MixedOp(feature_dim, drop_aggr, operations)            same      (models/cell_lp.py:12-33)
-    MixedOp_SF(gamma, operations)                          same      (:36-50)
+    MixedOp_SF(gamma, operations)                          same      (:36-50)    + registry=None: the scorer registry (MIXED_OPS_sf)
     Cell_Zero(nodes, feature_dim, drop_aggr)               same      (:53-68)    forward(g, h, hr, weights)
-    Cell_Final(gamma) / Cell_SF(gamma)                     same      (:71-86, :191-200)
+    Cell_Final(gamma) / Cell_SF(gamma)                     same      (:71-86, :191-200)   + registry=None, handed to MixedOp_SF (CPU
+                                                                                          tests pass scorers that compute there);
+                                                                                          + loss_1n(...): BCELoss of the mixed score
+                                                                                          without [B, N] tensors (csrc/sf_mix_1n.hip)
     Cell_First(nodes, feature_dim, drop_aggr)              same      (:89-109)   forward(g, states, h_in, weights)
     Cell_Middle(nodes, feature_dim, drop_aggr)             same      (:112-127)
     Cell_Last(in_nodes, nodes, feature_dim, drop_aggr)     same      (:130-152)
@@ -28,6 +31,7 @@ import os
 
 import torch
 import torch.nn as nn
+import torch.nn.functional as F
 
 from . import functional as K
 from . import lazy as LZ
@@ -233,6 +237,24 @@ class MixedOp_SF(nn.Module):
     def forward(self, weights, g, h, h_in):
         return sum(w * self.op_forward(op, g, h, h_in) for w, op in zip(weights, self._ops))
 
+    def _fused_1n(self, weights, all_ent, sub_emb, rel_emb):
+        """True when loss_1n runs functional.sf_mix_bce_all: the operations are exactly SF_OPS' TransE and DistMult (in that order, this
+        package's own scorers), the tensors float32 on a HIP device, and CALLER is not 'reference'.  The scorer types are compared
+        exactly: a registry may hand in other modules under the same names, and a subclass may score differently, so both run
+        the literal lines, which call them."""
+        tensors = (weights, all_ent, sub_emb, rel_emb)
+        return (CALLER != "reference" and list(self._operations) == ['sf_TransE', 'sf_DisMult']
+                and type(self._ops[0][0]) is OPS.sf_TransE_op and type(self._ops[1][0]) is OPS.sf_DisMult_op
+                and all(t.is_cuda and t.dtype == torch.float32 for t in tensors))
+
+    def loss_1n(self, weights, all_ent, sub_emb, rel_emb, label_index, subj, rel, label_smooth=0.0, col_chunk=None):
+        """BCELoss(forward(weights, all_ent, sub_emb, rel_emb), label_index.labels(subj, rel, label_smooth)) as a float32 scalar.  On the
+        fused path (_fused_1n) neither the [B, N] scores, nor their weighted sum, nor the labels exist (functional.sf_mix_bce_all,
+        csrc/sf_mix_1n.hip), and `weights` [2] receives its gradient from the same sweep; otherwise the literal lines run."""
+        if self._fused_1n(weights, all_ent, sub_emb, rel_emb):
+            return K.sf_mix_bce_all(all_ent, sub_emb, rel_emb, weights, self._ops[0][0].gamma, label_index, subj, rel, label_smooth, col_chunk)
+        return F.binary_cross_entropy(self.forward(weights, all_ent, sub_emb, rel_emb), label_index.labels(subj, rel, label_smooth))
+
 
 def _dense_stage(mixed_ops, states, h_in, weights, g, steps, fan):
     """The MixedOps feeding one new state each add onto the previous one's output inside the combine kernel (`addend`);
@@ -262,12 +284,15 @@ class Cell_Zero(nn.Module):
 
 
 class Cell_Final(nn.Module):
-    def __init__(self, gamma):
+    def __init__(self, gamma, registry=None):
         super().__init__()
-        self._ops = nn.ModuleList([MixedOp_SF(gamma, SF_OPS)])
+        self._ops = nn.ModuleList([MixedOp_SF(gamma, SF_OPS, registry)])
 
     def forward(self, all_ent, sub_emb, rel_emb, weights):
         return self._ops[0](weights[0], all_ent, sub_emb, rel_emb)
+
+    def loss_1n(self, all_ent, sub_emb, rel_emb, weights, label_index, subj, rel, label_smooth=0.0, col_chunk=None):
+        return self._ops[0].loss_1n(weights[0], all_ent, sub_emb, rel_emb, label_index, subj, rel, label_smooth, col_chunk)
 
 
 class Cell_First(nn.Module):
@@ -333,9 +358,13 @@ class Cell(nn.Module):
 
 
 class Cell_SF(nn.Module):
-    def __init__(self, gamma):
+    def __init__(self, gamma, registry=None):
         super().__init__()
-        self.cell_score = Cell_Final(gamma)
+        self.cell_score = Cell_Final(gamma, registry)
 
     def forward(self, all_ent_emb, sub_emb, rel_emb, weights_sf):
         return self.cell_score(all_ent_emb, sub_emb, rel_emb, weights_sf)
+
+    def loss_1n(self, all_ent_emb, sub_emb, rel_emb, weights_sf, label_index, subj, rel, label_smooth=0.0, col_chunk=None):
+        """BCELoss(forward(...), label_index.labels(subj, rel, label_smooth)) without the [B, N] tensors where MixedOp_SF.loss_1n can."""
+        return self.cell_score.loss_1n(all_ent_emb, sub_emb, rel_emb, weights_sf, label_index, subj, rel, label_smooth, col_chunk)

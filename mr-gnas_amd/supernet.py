@@ -302,6 +302,47 @@ class SearchNetwork(nn.Module):
         return [self.show_genotype(l) for l in range(self._layers)]
 
 
+class ScoreSearchNetwork(SearchNetwork):
+    """SearchNetwork whose loss ends in the score-function search cell, as the reference's supernet forward was written to
+    (models/model_search_lp.py:160-161: ``score_f = self.score_func(all_ent_emb, all_ent_emb[subj], rel_embed[rel], W_final)``): the
+    1-N BCE loss of the mixed probability W_final[0] * sf_TransE + W_final[1] * sf_DisMult over the step graph's nodes, so that the
+    fifth architecture parameter receives a gradient and the derived genotype names a score function.  ``architect.Architect`` and
+    ``architect.search_epoch`` drive it unchanged: they only pass ``data`` and ``labels`` through.
+
+    data: int tensor [B, >= 2] of (subj, rel) in the step graph's node ids.  labels: a ``sampler.LabelIndex`` over the step graph's
+    nodes -- no [B, N] tensor is formed (cell_lp.MixedOp_SF.loss_1n, csrc/sf_mix_1n.hip) -- or a dense float [B, N] tensor, which runs
+    the literal Cell_SF forward and BCELoss (also the path of CPU tensors, with a scorer registry that computes on the CPU).
+    ``score_func`` has neither parameters nor buffers: the state_dict keys are SearchNetwork's."""
+
+    def __init__(self, *args, sf_registry=None, **kwargs):
+        super().__init__(*args, **kwargs)
+        self.score_func = _cell_lp.Cell_SF(self.gamma, sf_registry)
+        self.label_smooth = 0.0
+
+    def score_weights(self):
+        """W_final of the reference (models/model_search_lp.py:158): softmax of the score-function alpha, [1, len(SF_OPS)]."""
+        return F.softmax(self._arch_parameters[4], dim=1)
+
+    def get_loss(self, g_train, ent, rel, data, labels):
+        subj, r = data[:, 0].long(), data[:, 1].long()
+        w = self.score_weights()
+        if torch.is_tensor(labels):
+            return F.binary_cross_entropy(self.score_func(ent, ent[subj], rel[r], w), labels)
+        return self.score_func.loss_1n(ent, ent[subj], rel[r], w, labels, subj, r, self.label_smooth)
+
+    def _loss(self, g_train, node_id, src_in, edge_type, data, labels):
+        ent, rel = self.forward(g_train, node_id, src_in, edge_type)
+        return self.get_loss(g_train, ent, rel, data, labels)
+
+    def show_genotype(self, l):
+        """The parent's genotype; the last layer's names the score function, SF_OPS[argmax of score_weights()] (what the reference's
+        commented block at models/model_search_lp.py:296-306 intends); the other layers' stays None."""
+        gt = super().show_genotype(l)
+        if l != self._layers - 1:
+            return gt
+        return gt._replace(score_func=OPS.SF_OPS[int(self.score_weights().detach()[0].argmax())])
+
+
 # ---------------------------------------------------------------------------
 # fixed genotype
 # ---------------------------------------------------------------------------
