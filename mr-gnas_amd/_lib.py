@@ -210,15 +210,21 @@ class KernelMeter:
     pair of events recorded on torch's current stream (the stream the kernels are
     enqueued on); ``meter.stop()`` synchronises and returns, per name, the number
     of launches, the summed device time and the summed algorithmic bytes / flops
-    the call sites declared.  Used by bench.py for the roofline figures."""
+    the call sites declared.  A call that returned an error code is counted
+    apart, in ``meter.refused`` ({name: calls}, kept until the next start()):
+    it is no completed launch of the entry point -- which does not say that
+    nothing was enqueued, an entry point may return an error after its first
+    kernel.  Used by bench.py for the roofline figures."""
 
     def __init__(self):
         self.names = None
         self.records = {}
+        self.refused = {}
 
     def start(self, names=None):
         self.names = set(names) if names is not None else True
         self.records = {}
+        self.refused = {}
 
     def active(self, name):
         return self.names is not None and (self.names is True or name in self.names)
@@ -277,7 +283,10 @@ def call(name, args, nbytes=0, flops=0, symbol=None):
         a.record()
         code = fn(*args)
         b.record()
-        meter.records.setdefault(name, []).append((a, b, nbytes, flops))
+        if code == 0:
+            meter.records.setdefault(name, []).append((a, b, nbytes, flops))
+        else:                                           # an error return is no launch of the entry point: counted apart
+            meter.refused[name] = meter.refused.get(name, 0) + 1
     else:
         code = fn(*args)
     if code != 0:

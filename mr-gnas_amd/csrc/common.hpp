@@ -4,6 +4,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "../../include/mrgnas.h"
+#include "row_geom.hpp"
 
 #define MRG_WAVE 64
 #define MRG_BLOCK 256            // 4 waves per workgroup, one per SIMD
@@ -97,28 +98,6 @@ __device__ __forceinline__ float group_sum(float x) {
 }
 
 __device__ __forceinline__ float sigmoidf_fast(float z) { return 1.0f / (1.0f + __expf(-z)); }
-
-// ---- row-tile geometry ---------------------------------------------------------
-// A row of D floats is covered by LPR lanes x KMAX steps x VEC floats.
-struct RowGeom {
-  int vec;    // 4 (D % 4 == 0 and 16-B aligned pointers) or 1
-  int lpr;    // lanes per row: 16 / 32 / 64
-  int kmax;   // 1 / 2 / 4
-  bool ok;
-};
-
-inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
-
-inline RowGeom row_geom(int D, bool all_aligned) {
-  RowGeom g{};
-  g.vec = (D % 4 == 0 && all_aligned) ? 4 : 1;
-  int dv = D / g.vec;
-  g.lpr = dv <= 16 ? 16 : (dv <= 32 ? 32 : 64);
-  int k = (dv + g.lpr - 1) / g.lpr;
-  g.kmax = k <= 1 ? 1 : (k <= 2 ? 2 : 4);
-  g.ok = D > 0 && k <= 4;
-  return g;
-}
 
 // Dispatch a kernel template<VEC, LPR, KMAX> on a RowGeom.
 #define MRG_DISPATCH_GEOM(G, CALL)                                             \
