@@ -882,6 +882,29 @@ int mrg_sfmix_rank(const float *obj, const float *qd, const float *ent, const fl
                    const int64_t *qkey, const int32_t *when, const int64_t *keys, const int32_t *rowptr, const int32_t *members,
                    const int32_t *gone_at, int64_t U, int64_t Q, int64_t N, int D, int64_t *ranks, void *ws, int64_t ws_bytes,
                    void *stream);
+/* The same leg over THREE scorers, [sf_TransE, sf_DisMult, sf_ConvE] (csrc/sf_mix3_1n.hip; reference models/operations_lp.py:26-30).
+ * Additive: ABI 23.  The two-way entry points argument for argument, with
+ *   qh [B][D]: ConvE's hidden rows after BN2 + ReLU (float32, formed by the caller) after qd,  dot2[b, e] = sum_c qh[b, c] * ent[e, c]
+ *   (one float32 fused multiply-add chain over c ascending),  p2 = sigmoid(dot2),
+ *   w: [3] float32 ON THE DEVICE, and p = (w[0] * p0 + w[1] * p1) + w[2] * p2 in float32 with every product and every sum rounded on
+ *   its own (the order in which sum(w * op(...)) evaluates).  With w[2] == 0 the loss, dl0, dl1 and dw[0..1] equal the two-way entry
+ *   points' bit for bit.
+ * mrg_sfmix3_bce_grad: dl2 [B][c1 - c0] = (G w[2]) ((1 - p2) p2), the gradient with respect to dot2, after dl1; dw [3], three float64
+ *   partials per workgroup.  mrg_sfmix3_rank: the target's p is formed by the same three chains and the same expression.
+ * Workspace: as above with three float64 per tile.  The same shape checks, error codes and B == 0 / Q == 0 / U == 0 handling. */
+int64_t mrg_sfmix3_bce_workspace_bytes(int64_t B, int64_t ncols, int D);
+int mrg_sfmix3_bce_fwd(const float *obj, const float *qd, const float *qh, const float *ent, const float *w, const int64_t *qkey,
+                       const int64_t *keys, const int32_t *rowptr, const int32_t *objs, int64_t U, float gamma, float v_zero, float v_one,
+                       int64_t B, int64_t N, int D, float *loss, void *ws, int64_t ws_bytes, void *stream);
+int mrg_sfmix3_bce_grad(const float *obj, const float *qd, const float *qh, const float *ent, const float *w, const int64_t *qkey,
+                        const int64_t *keys, const int32_t *rowptr, const int32_t *objs, int64_t U, float gamma, float v_zero, float v_one,
+                        int64_t B, int64_t N, int D, int64_t c0, int64_t c1, const float *gscale, float *dl0, float *dl1, float *dl2,
+                        float *dw, void *ws, int64_t ws_bytes, void *stream);
+int64_t mrg_sfmix3_rank_workspace_bytes(int64_t Q, int64_t N, int D);
+int mrg_sfmix3_rank(const float *obj, const float *qd, const float *qh, const float *ent, const float *w, float gamma, const int32_t *t_idx,
+                    const int64_t *qkey, const int32_t *when, const int64_t *keys, const int32_t *rowptr, const int32_t *members,
+                    const int32_t *gone_at, int64_t U, int64_t Q, int64_t N, int D, int64_t *ranks, void *ws, int64_t ws_bytes,
+                    void *stream);
 /* sf_TransE_op.forward, reference models/operations_lp.py:101-112:
  *   score[b, n] = sigmoid(gamma - sum_c |sub[b, c] + rel[b, c] - ent[n, c]|)
  * backward: gobj [B][D] (the gradient of both sub and rel) and gent [N][D]; either may be NULL.

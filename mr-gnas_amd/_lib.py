@@ -148,6 +148,11 @@ SIGNATURES = {
     "mrg_sfmix_bce_grad": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _L, _F, _F, _F, _L, _L, _I, _L, _L, _P, _P, _P, _P, _P, _L, _P]),
     "mrg_sfmix_rank_workspace_bytes": (_L, [_L, _L, _I]),
     "mrg_sfmix_rank": (_I, [_P, _P, _P, _P, _F, _P, _P, _P, _P, _P, _P, _P, _L, _L, _L, _I, _P, _P, _L, _P]),
+    "mrg_sfmix3_bce_workspace_bytes": (_L, [_L, _L, _I]),
+    "mrg_sfmix3_bce_fwd": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _L, _F, _F, _F, _L, _L, _I, _P, _P, _L, _P]),
+    "mrg_sfmix3_bce_grad": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _L, _F, _F, _F, _L, _L, _I, _L, _L, _P, _P, _P, _P, _P, _P, _L, _P]),
+    "mrg_sfmix3_rank_workspace_bytes": (_L, [_L, _L, _I]),
+    "mrg_sfmix3_rank": (_I, [_P, _P, _P, _P, _P, _F, _P, _P, _P, _P, _P, _P, _P, _L, _L, _L, _I, _P, _P, _L, _P]),
     "mrg_transe_score_fwd": (_I, [_P, _P, _P, _F, _P, _L, _L, _I, _P]),
     "mrg_transe_score_bwd": (_I, [_P, _P, _P, _P, _P, _P, _P, _L, _L, _I, _P]),
     "mrg_ccorr_rows": (_I, [_I, _P, _P, _P, _L, _I, _P]),

@@ -9,7 +9,9 @@ registry and -- when handed CUDA tensors -- on the fused HIP MixedOp path.
     Cell_Final(gamma) / Cell_SF(gamma)                     same      (:71-86, :191-200)   + registry=None, handed to MixedOp_SF (CPU
                                                                                           tests pass scorers that compute there);
                                                                                           + loss_1n(...): BCELoss of the mixed score
-                                                                                          without [B, N] tensors (csrc/sf_mix_1n.hip)
+                                                                                          without [B, N] tensors (csrc/sf_mix_1n.hip);
+                                                                                          + operations=None (SF_OPS), sf_args=None
+                                                                                          (MixedOp_SF's: sf_ConvE's sizes and dropouts)
     Cell_First(nodes, feature_dim, drop_aggr)              same      (:89-109)   forward(g, states, h_in, weights)
     Cell_Middle(nodes, feature_dim, drop_aggr)             same      (:112-127)
     Cell_Last(in_nodes, nodes, feature_dim, drop_aggr)     same      (:130-152)
@@ -224,11 +226,15 @@ class MixedOp(nn.Module):
 class MixedOp_SF(nn.Module):
     """sum_k w_k * score_k(all_ent, sub_emb, rel_emb)   (reference models/cell_lp.py:36-50)."""
 
-    def __init__(self, gamma, operations, registry=None):
+    def __init__(self, gamma, operations, registry=None, sf_args=None):
+        """sf_args: merged into the args dict handed to the scorers -- sf_ConvE's embed_dim, k_h, k_w, num_filt, ker_sz, conve_hid_drop
+        and feat_drop (the reference hands {'gamma'} alone, so its sf_ConvE is bound to D = 200 = 20 x 10)."""
         super().__init__()
         registry = MIXED_OPS_sf if registry is None else registry
         self._operations, self.gamma = operations, gamma
         self._args = {'gamma': gamma}
+        if sf_args:
+            self._args.update(sf_args)
         self._ops = nn.ModuleList(nn.ModuleList([registry[name](self._args)]) for name in operations)
 
     def op_forward(self, op, g, h, h_in):
@@ -238,21 +244,42 @@ class MixedOp_SF(nn.Module):
         return sum(w * self.op_forward(op, g, h, h_in) for w, op in zip(weights, self._ops))
 
     def _fused_1n(self, weights, all_ent, sub_emb, rel_emb):
-        """True when loss_1n runs functional.sf_mix_bce_all: the operations are exactly SF_OPS' TransE and DistMult (in that order, this
-        package's own scorers), the tensors float32 on a HIP device, and CALLER is not 'reference'.  The scorer types are compared
+        """True when loss_1n runs functional.sf_mix_bce_all / sf_mix3_bce_all: the operations are exactly SF_OPS' TransE and DistMult, or
+        those two and ConvE (in that order, this package's own scorers), the tensors float32 on a HIP device, and CALLER is not
+        'reference'.  The scorer types are compared
         exactly: a registry may hand in other modules under the same names, and a subclass may score differently, so both run
         the literal lines, which call them."""
+        return self._fused_width(weights, all_ent, sub_emb, rel_emb) > 0
+
+    def _fused_width(self, weights, all_ent, sub_emb, rel_emb):
+        """2 or 3, the number of scorers of the fused sweep loss_1n runs, or 0 for the literal lines.  3: exactly ['sf_TransE',
+        'sf_DisMult', 'sf_ConvE'] in that order, this package's own scorers, where the ConvE scorer's own HIP path holds (its
+        _hip_ok: float32 HIP operands, no autocast, no hooks, BatchNorms with running statistics).  Any other list -- other orders of
+        the three included -- runs the literal lines."""
         tensors = (weights, all_ent, sub_emb, rel_emb)
-        return (CALLER != "reference" and list(self._operations) == ['sf_TransE', 'sf_DisMult']
-                and type(self._ops[0][0]) is OPS.sf_TransE_op and type(self._ops[1][0]) is OPS.sf_DisMult_op
-                and all(t.is_cuda and t.dtype == torch.float32 for t in tensors))
+        if CALLER == "reference" or not all(t.is_cuda and t.dtype == torch.float32 for t in tensors):
+            return 0
+        names, ops = list(self._operations), [op[0] for op in self._ops]
+        if names == ['sf_TransE', 'sf_DisMult']:
+            return 2 if type(ops[0]) is OPS.sf_TransE_op and type(ops[1]) is OPS.sf_DisMult_op else 0
+        if names == ['sf_TransE', 'sf_DisMult', 'sf_ConvE']:
+            mine = type(ops[0]) is OPS.sf_TransE_op and type(ops[1]) is OPS.sf_DisMult_op and type(ops[2]) is OPS.sf_ConvE_op
+            return 3 if mine and ops[2]._hip_ok((all_ent, sub_emb, rel_emb)) else 0
+        return 0
 
     def loss_1n(self, weights, all_ent, sub_emb, rel_emb, label_index, subj, rel, label_smooth=0.0, col_chunk=None):
         """BCELoss(forward(weights, all_ent, sub_emb, rel_emb), label_index.labels(subj, rel, label_smooth)) as a float32 scalar.  On the
         fused path (_fused_1n) neither the [B, N] scores, nor their weighted sum, nor the labels exist (functional.sf_mix_bce_all,
-        csrc/sf_mix_1n.hip), and `weights` [2] receives its gradient from the same sweep; otherwise the literal lines run."""
-        if self._fused_1n(weights, all_ent, sub_emb, rel_emb):
-            return K.sf_mix_bce_all(all_ent, sub_emb, rel_emb, weights, self._ops[0][0].gamma, label_index, subj, rel, label_smooth, col_chunk)
+        csrc/sf_mix_1n.hip; with sf_ConvE as the third scorer functional.sf_mix3_bce_all, csrc/sf_mix3_1n.hip, on ONE call of the ConvE
+        scorer's query: one BatchNorm update and one dropout draw per step, as forward has), and `weights` receives its gradient from
+        the same sweep; otherwise the literal lines run."""
+        width = self._fused_width(weights, all_ent, sub_emb, rel_emb)
+        gamma = self._ops[0][0].gamma if width else None
+        if width == 2:
+            return K.sf_mix_bce_all(all_ent, sub_emb, rel_emb, weights, gamma, label_index, subj, rel, label_smooth, col_chunk)
+        if width == 3:
+            hidden = self._ops[2][0].query(sub_emb, rel_emb)
+            return K.sf_mix3_bce_all(all_ent, sub_emb, rel_emb, hidden, weights, gamma, label_index, subj, rel, label_smooth, col_chunk)
         return F.binary_cross_entropy(self.forward(weights, all_ent, sub_emb, rel_emb), label_index.labels(subj, rel, label_smooth))
 
 
@@ -284,9 +311,9 @@ class Cell_Zero(nn.Module):
 
 
 class Cell_Final(nn.Module):
-    def __init__(self, gamma, registry=None):
+    def __init__(self, gamma, registry=None, operations=None, sf_args=None):
         super().__init__()
-        self._ops = nn.ModuleList([MixedOp_SF(gamma, SF_OPS, registry)])
+        self._ops = nn.ModuleList([MixedOp_SF(gamma, SF_OPS if operations is None else operations, registry, sf_args)])
 
     def forward(self, all_ent, sub_emb, rel_emb, weights):
         return self._ops[0](weights[0], all_ent, sub_emb, rel_emb)
@@ -358,9 +385,9 @@ class Cell(nn.Module):
 
 
 class Cell_SF(nn.Module):
-    def __init__(self, gamma, registry=None):
+    def __init__(self, gamma, registry=None, operations=None, sf_args=None):
         super().__init__()
-        self.cell_score = Cell_Final(gamma, registry)
+        self.cell_score = Cell_Final(gamma, registry, operations, sf_args)
 
     def forward(self, all_ent_emb, sub_emb, rel_emb, weights_sf):
         return self.cell_score(all_ent_emb, sub_emb, rel_emb, weights_sf)

@@ -280,17 +280,22 @@ def query_ranks(q, ent, target, known_side=None, when=None, qkey=None, kind="dot
     return _rank_call(name, ws_name, name, (q, ent, target), side, Q, N, D, q)
 
 
-def mix_ranks(sub_emb, rel_emb, ent, weights, gamma, target, known_side=None, when=None, qkey=None):
+def mix_ranks(sub_emb, rel_emb, ent, weights, gamma, target, known_side=None, when=None, qkey=None, hidden=None):
     """ranks [Q] int64 (1-based) of `target` among all entities under the mixed score of the score-function search cell,
     p_e = w0 sigmoid(gamma - ||sub + rel - ent[e]||_1) + w1 sigmoid((sub * rel) . ent[e]), compared on the float32 p itself
     (mrg_sfmix_rank; equal p: the lower entity id first).  sub_emb / rel_emb [Q, D]; weights [2] float32 on the device, TransE's first.
-    known_side / when / qkey as in query_ranks; None for raw ranks."""
+    With weights [3] and hidden [Q, D] (sf_ConvE_op.query's rows) the score has the third term + w2 sigmoid(hidden . ent[e])
+    (mrg_sfmix3_rank).  known_side / when / qkey as in query_ranks; None for raw ranks."""
     from . import functional as K
     if not (sub_emb.is_cuda and rel_emb.is_cuda and ent.is_cuda and weights.is_cuda and target.is_cuda):
         raise MrgnasError("mix_ranks runs on a HIP device (no CPU fallback)")
-    if sub_emb.dim() != 2 or sub_emb.shape != rel_emb.shape or ent.dim() != 2 or ent.shape[1] != sub_emb.shape[1] or weights.numel() != 2:
-        raise ValueError("mix_ranks: sub_emb / rel_emb [Q, D], ent [N, D] and weights [2] expected")
-    sub_emb, rel_emb, ent, weights, target = f32c(sub_emb), f32c(rel_emb), f32c(ent), f32c(weights.reshape(2)), target.int().contiguous()
+    nw = 2 if hidden is None else 3
+    if (sub_emb.dim() != 2 or sub_emb.shape != rel_emb.shape or ent.dim() != 2 or ent.shape[1] != sub_emb.shape[1] or weights.numel() != nw
+            or (hidden is not None and hidden.shape != sub_emb.shape)):
+        raise ValueError("mix_ranks: sub_emb / rel_emb [Q, D], ent [N, D] and weights [2], or hidden [Q, D] and weights [3], expected")
+    if hidden is not None and not hidden.is_cuda:
+        raise MrgnasError("mix_ranks runs on a HIP device (no CPU fallback)")
+    sub_emb, rel_emb, ent, weights, target = f32c(sub_emb), f32c(rel_emb), f32c(ent), f32c(weights.reshape(nw)), target.int().contiguous()
     require_hip(sub_emb, rel_emb, ent, weights, target)
     (Q, D), N = sub_emb.shape, ent.shape[0]
     if target.numel() != Q:
@@ -299,38 +304,58 @@ def mix_ranks(sub_emb, rel_emb, ent, weights, gamma, target, known_side=None, wh
     with torch.no_grad():
         obj, qd = K.compose("add", sub_emb, rel_emb), K.compose("mult", sub_emb, rel_emb)
     ranks = torch.empty(Q, dtype=torch.int64, device=ent.device)
-    nbytes = load().mrg_sfmix_rank_workspace_bytes(Q, N, D)
+    name = "mrg_sfmix_rank" if hidden is None else "mrg_sfmix3_rank"
+    nbytes = getattr(load(), name + "_workspace_bytes")(Q, N, D)
     if nbytes < 0:
-        check(int(nbytes), "mrg_sfmix_rank")
+        check(int(nbytes), name)
     ws = torch.empty(max(int(nbytes), 1), dtype=torch.uint8, device=ent.device)
-    call("mrg_sfmix_rank", (ptr(obj), ptr(qd), ptr(ent), ptr(weights), float(gamma), ptr(target), *(ptr(t) for t in side[:6]), side[6],
-                            Q, N, D, ptr(ranks), ptr(ws), int(nbytes), stream_of(ent)),
-         nbytes=4 * (2 * Q + N) * D, flops=5 * Q * N * D)
+    tail = (ptr(ent), ptr(weights), float(gamma), ptr(target), *(ptr(t) for t in side[:6]), side[6], Q, N, D, ptr(ranks), ptr(ws), int(nbytes),
+            stream_of(ent))
+    if hidden is None:
+        call(name, (ptr(obj), ptr(qd), *tail), nbytes=4 * (2 * Q + N) * D, flops=5 * Q * N * D)
+    else:
+        qh = f32c(hidden.detach())
+        require_hip(qh)
+        call(name, (ptr(obj), ptr(qd), ptr(qh), *tail), nbytes=4 * (3 * Q + N) * D, flops=7 * Q * N * D)
     return ranks
 
 
-def predict_mix(loader, ent, rel_emb, weights, gamma, label_index, device):
+def predict_mix(loader, ent, rel_emb, weights, gamma, label_index, device, conve=None):
     """predict_1n's loop and result dictionary under the mixed score, on embeddings the caller already holds (a supernet's forward):
     per batch of (s, r, o) triples the ranks come from mix_ranks with label_index as the filter and when = -1, the batch's mean BCE
-    from mrg_sfmix_bce_fwd on the unsmoothed labels.  Returns (results, summed loss) after ONE device -> host copy."""
+    from mrg_sfmix_bce_fwd on the unsmoothed labels.  conve: the sf_ConvE_op of a three-way MixedOp_SF (weights [3]); it is put in
+    eval mode for the pass (and back afterwards) and forms the batch's hidden rows.  Returns (results, summed loss) after ONE
+    device -> host copy."""
     from . import functional as K
     if torch.device(device).type != "cuda" or not (ent.is_cuda and rel_emb.is_cuda and weights.is_cuda):
         raise MrgnasError("predict_mix runs on a HIP device (no CPU fallback); got " + str(device))
     side = _LabelSide(label_index)
     v_zero, v_one = label_index.label_values(0.0)
     ks, acc = _stats_begin(device)
-    with torch.no_grad():
-        ent, rel_emb, weights = f32c(ent), f32c(rel_emb), f32c(weights.reshape(2))
-        for batch in loader:
-            triplets = (batch[0] if isinstance(batch, (tuple, list)) else batch).to(device)
-            s, r, o = (triplets[:, i].int().contiguous() for i in range(3))
-            sub_e, rel_e = K.gather_rows(ent, s), K.gather_rows(rel_emb, r)
-            when = torch.full((s.numel(),), -1, dtype=torch.int32, device=device)
-            qkey = (s.long() * side.num_rels + r.long()).contiguous()
-            ranks = mix_ranks(sub_e, rel_e, ent, weights, gamma, o, side, when, qkey).double()
-            loss = K.sf_mix_bce_mean(K.compose("add", sub_e, rel_e), K.compose("mult", sub_e, rel_e), ent, weights, gamma, label_index, qkey,
-                                     v_zero, v_one)
-            acc += _batch_stats(ranks, loss, ks)
+    was_training = conve is not None and conve.training
+    if conve is not None:
+        conve.eval()
+    try:
+        with torch.no_grad():
+            ent, rel_emb, weights = f32c(ent), f32c(rel_emb), f32c(weights.reshape(2 if conve is None else 3))
+            for batch in loader:
+                triplets = (batch[0] if isinstance(batch, (tuple, list)) else batch).to(device)
+                s, r, o = (triplets[:, i].int().contiguous() for i in range(3))
+                sub_e, rel_e = K.gather_rows(ent, s), K.gather_rows(rel_emb, r)
+                when = torch.full((s.numel(),), -1, dtype=torch.int32, device=device)
+                qkey = (s.long() * side.num_rels + r.long()).contiguous()
+                obj, qd = K.compose("add", sub_e, rel_e), K.compose("mult", sub_e, rel_e)
+                if conve is None:
+                    ranks = mix_ranks(sub_e, rel_e, ent, weights, gamma, o, side, when, qkey).double()
+                    loss = K.sf_mix_bce_mean(obj, qd, ent, weights, gamma, label_index, qkey, v_zero, v_one)
+                else:
+                    hidden = conve.query(sub_e, rel_e)
+                    ranks = mix_ranks(sub_e, rel_e, ent, weights, gamma, o, side, when, qkey, hidden=hidden).double()
+                    loss = K.sf_mix3_bce_mean(obj, qd, hidden, ent, weights, gamma, label_index, qkey, v_zero, v_one)
+                acc += _batch_stats(ranks, loss, ks)
+    finally:
+        if was_training:
+            conve.train()
     return _stats_end(acc)
 
 

@@ -140,10 +140,11 @@ def transe_bce_dlogit(obj, ent, gamma, label_index, qkey, v_zero, v_one, c0, c1,
     return _bce_dlogit("l1", gamma, obj, ent, label_index, qkey, v_zero, v_one, c0, c1, gscale, out)
 
 
-def _dot_chunk_bwd(q, ent, dl, c0, nc, g_q, g_ent, pre, st):
+def _dot_chunk_bwd(q, ent, dl, c0, nc, g_q, g_ent, pre, st, ent_dst=None):
     """One column chunk of the "dot" backward: the two gradient GEMMs of `linear` on dl [B, nc]: g_q += dl ent[c0:c1]
     (mrg_linear_bwd_input, accumulating) and g_ent[c0:c1] = dl^T q (mrg_linear_fwd on the transposed operands).  pre: (q^T, the row
-    GEMM's workspace) when g_ent is wanted."""
+    GEMM's workspace) when g_ent is wanted.  ent_dst: a [>= nc, D] scratch that receives dl^T q in place of g_ent[c0:c1] (a second "dot"
+    leg on the same entities, which its caller adds)."""
     (B, D), esz = q.shape, ent.element_size()
     need_q, need_ent = g_q is not None, g_ent is not None
     work = dict(nbytes=4 * B * (D + nc) + 4 * D * nc, flops=2 * B * D * nc)
@@ -168,8 +169,8 @@ def _dot_chunk_bwd(q, ent, dl, c0, nc, g_q, g_ent, pre, st):
         # kernel keeps all of gW's row tiles in registers: it does not cover thousands of output rows, nor a chunk whose
         # width is no multiple of 4)
         qT, gws = pre
-        call("mrg_linear_fwd", (ptr(dlT), ptr(qT), None, ctypes.c_void_p(g_ent.data_ptr() + c0 * D * esz), ptr(gws), nc, B, D, 0, st),
-             **work)
+        dst = ctypes.c_void_p(g_ent.data_ptr() + c0 * D * esz) if ent_dst is None else ptr(ent_dst)
+        call("mrg_linear_fwd", (ptr(dlT), ptr(qT), None, dst, ptr(gws), nc, B, D, 0, st), **work)
 
 
 def _l1_chunk_bwd(obj, ent, dl, c0, nc, g_obj, g_ent, pre, st):

@@ -312,15 +312,23 @@ class ScoreSearchNetwork(SearchNetwork):
     data: int tensor [B, >= 2] of (subj, rel) in the step graph's node ids.  labels: a ``sampler.LabelIndex`` over the step graph's
     nodes -- no [B, N] tensor is formed (cell_lp.MixedOp_SF.loss_1n, csrc/sf_mix_1n.hip) -- or a dense float [B, N] tensor, which runs
     the literal Cell_SF forward and BCELoss (also the path of CPU tensors, with a scorer registry that computes on the CPU).
-    ``score_func`` has neither parameters nor buffers: the state_dict keys are SearchNetwork's."""
+    With the default scorers ``score_func`` has neither parameters nor buffers: the state_dict keys are SearchNetwork's."""
 
-    def __init__(self, *args, sf_registry=None, **kwargs):
+    def __init__(self, *args, sf_registry=None, sf_ops=None, sf_args=None, **kwargs):
+        """sf_ops: the scorers searched over (default operations_lp.SF_OPS); ['sf_TransE', 'sf_DisMult', 'sf_ConvE'] adds the scorer the
+        reference's published genotype ends in (csrc/sf_mix3_1n.hip), whose sizes and dropouts come in sf_args (embed_dim, k_h, k_w,
+        num_filt, ker_sz, conve_hid_drop, feat_drop; embed_dim = k_h * k_w = the feature width).  Then the fifth architecture parameter
+        is [1, len(sf_ops)] and score_func carries sf_ConvE's parameters and buffers.  With the defaults nothing differs: the same
+        state_dict keys, the same random draws."""
         super().__init__(*args, **kwargs)
-        self.score_func = _cell_lp.Cell_SF(self.gamma, sf_registry)
+        self.sf_ops = list(OPS.SF_OPS if sf_ops is None else sf_ops)
+        self.score_func = _cell_lp.Cell_SF(self.gamma, sf_registry, self.sf_ops, sf_args)
+        if len(self.sf_ops) != len(OPS.SF_OPS):
+            self._arch_parameters[4] = (1e-3 * torch.randn(1, len(self.sf_ops), device=self._device)).requires_grad_(True)
         self.label_smooth = 0.0
 
     def score_weights(self):
-        """W_final of the reference (models/model_search_lp.py:158): softmax of the score-function alpha, [1, len(SF_OPS)]."""
+        """W_final of the reference (models/model_search_lp.py:158): softmax of the score-function alpha, [1, len(sf_ops)]."""
         return F.softmax(self._arch_parameters[4], dim=1)
 
     def get_loss(self, g_train, ent, rel, data, labels):
@@ -340,7 +348,7 @@ class ScoreSearchNetwork(SearchNetwork):
         gt = super().show_genotype(l)
         if l != self._layers - 1:
             return gt
-        return gt._replace(score_func=OPS.SF_OPS[int(self.score_weights().detach()[0].argmax())])
+        return gt._replace(score_func=self.sf_ops[int(self.score_weights().detach()[0].argmax())])
 
 
 # ---------------------------------------------------------------------------
