@@ -34,7 +34,7 @@
 extern "C" {
 #endif
 
-#define MRG_ABI_VERSION 23   /* 23 (addition, no bump): mrg_linear_bwd_input_acc2, mrg_linear_bwd_input3_acc2, mrg_linear_bwd_input3_pair_acc2, mrg_segmax_bwd_input_chain, mrg_gate_row_bwd_acc (the gradient fan-in chain: a reader adds the running sum of the other readers' gradients in its own last store); 23 (addition, no bump): mrg_rows_rank, mrg_transe_bce_fwd / _dlogit / _workspace_bytes, mrg_transe_dist_bwd, mrg_transe_rank / _workspace_bytes (1-N loss and ranks of ConvE and TransE without [B, N] tensors); 23 (addition, no bump: nothing existing changed, and tests pin the number): mrg_distmult_rank, mrg_distmult_rank_workspace_bytes (raw / filtered DistMult ranks as a row GEMM with a counting epilogue); 23: mrg_gemm_set_epilogue removed (the row-order and transposed-accumulator store orders of the split-core row GEMM, measured slower, left the library; accumulator-order stores remain), mrg_gemm_set_wide8 and mrg_gemm_set_small take 0 or 1 only; 22: mrg_cand_linear_fwd, mrg_cand_linear_bwd_input, mrg_cand_linear_colsum_blocks, mrg_cand_linear_workspace_bytes (the candidate Linears of one node-classification MixedOp in one launch, BatchNorm sums included); 21: mrg_adam_step (multi-tensor Adam over the pointer tables of mrg_clip_sgd_step, two launches; per-tensor step counts and lr in device memory); 20: BatchNorm sums formed by a candidate's producer: mrg_gated_branch.given / given_n / given_stride (mrg_mix_stats_coef skips the sweep over such a candidate), mrg_dense_filter3_colsum_blocks, mrg_dense_filter_fwd3_colsum, mrg_gate_row_colsum_blocks, mrg_gate_row_fwd_colsum; 19: mrg_seg_std_workspace_bytes, mrg_seg_std_fwd, mrg_seg_std_bwd (a_std, the standard-deviation aggregator of the node-classification task); 18: mrg_conve_* (the ConvE feature path: BN0 statistics, conv, BN1, split-K fc and their gradients, stacked or interleaved image layout); 17: mrg_ccorr_rows, mrg_ccorr_matrix, mrg_ccorr_matrix_grad (standalone circular correlation: per-row kernel, and the circulant of a shared row with its gradient fold for the row GEMM); 16: mrg_set_stream_blocks, mrg_gate_collapse and mrg_gate_param_grad removed (the streaming grid bound is fixed; the three-segment forms remain); 15: mrg_gated_branch.valid_rows and the valid_rows argument of mrg_mix_finalize_bwd / mrg_zero_* except colstats (the device row count of a static step graph, passed per call instead of the process-wide registry of 13), mrg_linear_bwd_weight_share (the weight gradient of one range of a grouped launch, instead of the process-wide setter of 14); 14: mrg_clip_sgd_step, mrg_optim_chunk (clip_grad_norm_ + SGD with momentum over every parameter tensor in three launches), mrg_gated_branch.act (tanh behind the BatchNorm: CompGraphConv's tail on the epilogue kernels), mrg_gemm_set_small (few-row products on two-tile column blocks), a weight-gradient share setter, mrg_segmax_bwd_input (a_max's input gradient without a dense product); 13: a registry of device-side row counts (the sampled search step as one replayable HIP graph), mrg_seg_reduce_bwd_ordered (aggregator backward walked in destination order), mrg_gemm_set_q (the 16 x 16 x 32 row GEMM at three workgroups per CU for 129..224 output columns); 12: mrg_act_grad_transpose (the [B, N] scorer's output gradient, activation folded in, as [N, B] rows); 11: mrg_gemm_set_wide8 (eight-tile column block for D = 256); 10: mrg_gemm_set_epilogue(2) (transposed accumulators: a tested comparison point); 9: mrg_gated_branch (the MixedOp epilogue recomputes f_dense_comp's output from its gate and f_sparse_comp's from its row factor), mrg_gate_row_fwd / _bwd, mrg_sum_rows_gather, mrg_wgrad_set_variant, mrg_dense_filter_fwd3 out == NULL; 8: mrg_zero_* (cell-zero MixedOp recomputed from the tables), mrg_linear_bwd_input3_pair, mrg_sample_edge_neighborhood; 7: mrg_gemm_set_epilogue (row-order stores of the split-core row GEMM), mrg_set_stream_blocks, mrg_gemm_set_mode(2); 6: fused a_mean (run-sum epilogue, heads reducer, bit-mask backward), mrg_mix_stats_coef; 5: three-segment dense filter entry points; 4: mrg_linear_relu_segmax_fwd (fused a_max); 3: device graph / plan builders, samplers, [B, N] scorers, ranking; 2: GEMM workspaces, span_gcs ext_scal */
+#define MRG_ABI_VERSION 23   /* 23 (addition, no bump): mrg_rows_bias_bce_fwd / _dlogit, mrg_rows_bias_rank, mrg_rows_bias_topk, mrg_cols_sum (the "dot" sweeps under a per-entity score bias: CompGCN_ConvE without a [B, N] tensor); 23 (addition, no bump): mrg_linear_bwd_input_acc2, mrg_linear_bwd_input3_acc2, mrg_linear_bwd_input3_pair_acc2, mrg_segmax_bwd_input_chain, mrg_gate_row_bwd_acc (the gradient fan-in chain: a reader adds the running sum of the other readers' gradients in its own last store); 23 (addition, no bump): mrg_rows_rank, mrg_transe_bce_fwd / _dlogit / _workspace_bytes, mrg_transe_dist_bwd, mrg_transe_rank / _workspace_bytes (1-N loss and ranks of ConvE and TransE without [B, N] tensors); 23 (addition, no bump: nothing existing changed, and tests pin the number): mrg_distmult_rank, mrg_distmult_rank_workspace_bytes (raw / filtered DistMult ranks as a row GEMM with a counting epilogue); 23: mrg_gemm_set_epilogue removed (the row-order and transposed-accumulator store orders of the split-core row GEMM, measured slower, left the library; accumulator-order stores remain), mrg_gemm_set_wide8 and mrg_gemm_set_small take 0 or 1 only; 22: mrg_cand_linear_fwd, mrg_cand_linear_bwd_input, mrg_cand_linear_colsum_blocks, mrg_cand_linear_workspace_bytes (the candidate Linears of one node-classification MixedOp in one launch, BatchNorm sums included); 21: mrg_adam_step (multi-tensor Adam over the pointer tables of mrg_clip_sgd_step, two launches; per-tensor step counts and lr in device memory); 20: BatchNorm sums formed by a candidate's producer: mrg_gated_branch.given / given_n / given_stride (mrg_mix_stats_coef skips the sweep over such a candidate), mrg_dense_filter3_colsum_blocks, mrg_dense_filter_fwd3_colsum, mrg_gate_row_colsum_blocks, mrg_gate_row_fwd_colsum; 19: mrg_seg_std_workspace_bytes, mrg_seg_std_fwd, mrg_seg_std_bwd (a_std, the standard-deviation aggregator of the node-classification task); 18: mrg_conve_* (the ConvE feature path: BN0 statistics, conv, BN1, split-K fc and their gradients, stacked or interleaved image layout); 17: mrg_ccorr_rows, mrg_ccorr_matrix, mrg_ccorr_matrix_grad (standalone circular correlation: per-row kernel, and the circulant of a shared row with its gradient fold for the row GEMM); 16: mrg_set_stream_blocks, mrg_gate_collapse and mrg_gate_param_grad removed (the streaming grid bound is fixed; the three-segment forms remain); 15: mrg_gated_branch.valid_rows and the valid_rows argument of mrg_mix_finalize_bwd / mrg_zero_* except colstats (the device row count of a static step graph, passed per call instead of the process-wide registry of 13), mrg_linear_bwd_weight_share (the weight gradient of one range of a grouped launch, instead of the process-wide setter of 14); 14: mrg_clip_sgd_step, mrg_optim_chunk (clip_grad_norm_ + SGD with momentum over every parameter tensor in three launches), mrg_gated_branch.act (tanh behind the BatchNorm: CompGraphConv's tail on the epilogue kernels), mrg_gemm_set_small (few-row products on two-tile column blocks), a weight-gradient share setter, mrg_segmax_bwd_input (a_max's input gradient without a dense product); 13: a registry of device-side row counts (the sampled search step as one replayable HIP graph), mrg_seg_reduce_bwd_ordered (aggregator backward walked in destination order), mrg_gemm_set_q (the 16 x 16 x 32 row GEMM at three workgroups per CU for 129..224 output columns); 12: mrg_act_grad_transpose (the [B, N] scorer's output gradient, activation folded in, as [N, B] rows); 11: mrg_gemm_set_wide8 (eight-tile column block for D = 256); 10: mrg_gemm_set_epilogue(2) (transposed accumulators: a tested comparison point); 9: mrg_gated_branch (the MixedOp epilogue recomputes f_dense_comp's output from its gate and f_sparse_comp's from its row factor), mrg_gate_row_fwd / _bwd, mrg_sum_rows_gather, mrg_wgrad_set_variant, mrg_dense_filter_fwd3 out == NULL; 8: mrg_zero_* (cell-zero MixedOp recomputed from the tables), mrg_linear_bwd_input3_pair, mrg_sample_edge_neighborhood; 7: mrg_gemm_set_epilogue (row-order stores of the split-core row GEMM), mrg_set_stream_blocks, mrg_gemm_set_mode(2); 6: fused a_mean (run-sum epilogue, heads reducer, bit-mask backward), mrg_mix_stats_coef; 5: three-segment dense filter entry points; 4: mrg_linear_relu_segmax_fwd (fused a_max); 3: device graph / plan builders, samplers, [B, N] scorers, ranking; 2: GEMM workspaces, span_gcs ext_scal */
 
 #define MRG_OK            0
 #define MRG_E_NULLPTR    -1   /* a required pointer is NULL */
@@ -844,6 +844,31 @@ int64_t mrg_transe_topk_workspace_bytes(int64_t Q, int64_t N, int D, int k);
 int mrg_transe_topk(const float *obj, const float *ent, const int64_t *qkey, const int32_t *when, const int64_t *keys,
                     const int32_t *rowptr, const int32_t *members, const int32_t *gone_at, int64_t U, int64_t Q, int64_t N, int D, int k,
                     int32_t *ids, float *vals, void *ws, int64_t ws_bytes, void *stream);
+/* The "dot" sweeps under a per-entity score bias, x[b, e] = sum_c q[b, c] * ent[e, c] + bias[e] -- the logit of the reference's baseline
+ * model CompGCN_ConvE (models/compgcn.py:188-269) -- without a [B, N] tensor (csrc/bce.hip, rank.hip, topk.hip).  Additive: ABI 23.
+ * Each entry point is its unbiased twin (mrg_distmult_bce_fwd, mrg_distmult_bce_dlogit, mrg_rows_rank, mrg_rows_topk) with bias [N]
+ * float32 after ent: same arguments, same labels / filter, same cores, same errors, and the SAME workspace query
+ * (mrg_distmult_bce_workspace_bytes, mrg_distmult_rank_workspace_bytes, mrg_rows_topk_workspace_bytes).  bias is required (NULL:
+ * MRG_E_NULLPTR).  The bias joins the float32 accumulator by one float32 add before the sigmoid and loss term, the logit gradient,
+ * the rank comparison and the top-k selection see it; kernel instances of their own, so a call without a bias runs the code it ran.
+ * The rank's target score is the diagonal accumulator plus bias[t_idx[i]], the float32 add the sweep forms for the target's column: a
+ * duplicate entity row with an equal bias ties exactly.  mrg_rows_bias_topk's vals are the biased logits mrg_rows_bias_rank compares.
+ * mrg_cols_sum: out[c] = sum_r x[r][c] for x [rows][cols] with leading dimension ld >= cols (rows == 0: zeros) -- the bias gradient of a
+ *   slice of mrg_rows_bias_bce_dlogit.  float64 accumulation in a fixed order (a wave adds every eighth row ascending, eight waves are
+ *   added in wave order), stored as float32; no atomics: bitwise repeatable. */
+int mrg_rows_bias_bce_fwd(const float *q, const float *ent, const float *bias, const int64_t *qkey, const int64_t *keys,
+                          const int32_t *rowptr, const int32_t *objs, int64_t U, float v_zero, float v_one, int64_t B, int64_t N, int D,
+                          float *loss, void *ws, int64_t ws_bytes, void *stream);
+int mrg_rows_bias_bce_dlogit(const float *q, const float *ent, const float *bias, const int64_t *qkey, const int64_t *keys,
+                             const int32_t *rowptr, const int32_t *objs, int64_t U, float v_zero, float v_one, int64_t B, int64_t N, int D,
+                             int64_t c0, int64_t c1, const float *gscale, float *dl, void *ws, int64_t ws_bytes, void *stream);
+int mrg_rows_bias_rank(const float *q, const float *ent, const float *bias, const int32_t *t_idx, const int64_t *qkey,
+                       const int32_t *when, const int64_t *keys, const int32_t *rowptr, const int32_t *members, const int32_t *gone_at,
+                       int64_t U, int64_t Q, int64_t N, int D, int64_t *ranks, void *ws, int64_t ws_bytes, void *stream);
+int mrg_rows_bias_topk(const float *q, const float *ent, const float *bias, const int64_t *qkey, const int32_t *when,
+                       const int64_t *keys, const int32_t *rowptr, const int32_t *members, const int32_t *gone_at, int64_t U, int64_t Q,
+                       int64_t N, int D, int k, int32_t *ids, float *vals, void *ws, int64_t ws_bytes, void *stream);
+int mrg_cols_sum(const float *x, int64_t rows, int64_t cols, int64_t ld, float *out, void *stream);
 /* The score-function search leg without a [B, N] tensor (csrc/sf_mix_1n.hip): the 1-N loss, its gradients and the filtered ranks under
  * the mixed score of MixedOp_SF over SF_OPS = [sf_TransE, sf_DisMult] (reference models/cell_lp.py:36-50, 71-86, 191-200; the
  * supernet's score_f, models/model_search_lp.py:160-161).  Additive: ABI 23.

@@ -141,6 +141,11 @@ SIGNATURES = {
     "mrg_transe_rank": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _L, _L, _L, _I, _P, _P, _L, _P]),
     "mrg_rows_topk_workspace_bytes": (_L, [_L, _L, _I, _I]),
     "mrg_rows_topk": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _L, _L, _L, _I, _I, _P, _P, _P, _L, _P]),
+    "mrg_rows_bias_bce_fwd": (_I, [_P, _P, _P, _P, _P, _P, _P, _L, _F, _F, _L, _L, _I, _P, _P, _L, _P]),
+    "mrg_rows_bias_bce_dlogit": (_I, [_P, _P, _P, _P, _P, _P, _P, _L, _F, _F, _L, _L, _I, _L, _L, _P, _P, _P, _L, _P]),
+    "mrg_rows_bias_rank": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _L, _L, _L, _I, _P, _P, _L, _P]),
+    "mrg_rows_bias_topk": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _L, _L, _L, _I, _I, _P, _P, _P, _L, _P]),
+    "mrg_cols_sum": (_I, [_P, _L, _L, _L, _P, _P]),
     "mrg_transe_topk_workspace_bytes": (_L, [_L, _L, _I, _I]),
     "mrg_transe_topk": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _L, _L, _L, _I, _I, _P, _P, _P, _L, _P]),
     "mrg_sfmix_bce_workspace_bytes": (_L, [_L, _L, _I]),

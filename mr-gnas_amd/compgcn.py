@@ -9,7 +9,9 @@ Same constructors, same ``forward`` signatures and return values, same parameter
 the MixedOp epilogue kernels and the [B, N] product on the row GEMM; autocast, forward hooks on a scorer submodule, or a
 BatchNorm without running statistics or with momentum=None run the reference's torch formulation instead.  Unlike the
 reference, it raises a ValueError when ``k_w * k_h != layer_size[-1]`` (the reference's reshape then silently makes several
-images per row and returns more score rows than queries).
+images per row and returns more score rows than queries).  It also follows the scorer protocol of operations_lp.py
+(``embed``, ``query``, ``score_kind``, ``score_bias``, ``score_func`` = the model itself) and has ``loss_1n``: the training loss and, through
+``evaluation.predict_1n`` / ``predict_topk``, the evaluation without a [B, N] tensor, the per-entity bias riding in the sweeps' epilogues.
 ``g`` is a ``RelGraph`` carrying ``edata['etype'|'norm'|'in_edges_mask'|'out_edges_mask']``.
 
 What changes is the schedule: W_O and W_I are linear and applied before a *sum*, so they
@@ -23,6 +25,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from . import functional as K
+from ._lib import MrgnasError
 from .graph import cached_on
 
 
@@ -155,17 +158,66 @@ class CompGCN_ConvE(nn.Module):
         stack_inp = torch.cat([e1_embed, rel_embed], 1)
         return torch.transpose(stack_inp, 2, 1).reshape((-1, 1, 2 * self.k_w, self.k_h))
 
-    def forward(self, graph, sub, rel):
+    # ---- the scorer protocol of the paths that keep no [B, N] tensor (operations_lp: query / score_kind / score_bias), with the model
+    # as its own scorer, so that evaluation.predict_1n and evaluation.predict_topk take it unchanged.  No parameters, no buffers.
+    score_kind = "dot"
+
+    @property
+    def score_func(self):
+        return self
+
+    @property
+    def score_bias(self):
+        return self.bias
+
+    def _check_image(self):
         if self.k_w * self.k_h != self.embed_dim:
             raise ValueError(f"CompGCN_ConvE: k_w * k_h = {self.k_w} * {self.k_h} must equal the embedding width layer_size[-1] = "
                              f"{self.embed_dim} (one 2 k_w x k_h image per query)")
-        n_feats, r_feats = self.compGCN_Model(graph)
+
+    def _hip_ok(self, tensors):
+        mods = (self.bn0, self.m_conv1, self.bn1, self.feature_drop, self.fc, self.hidden_drop, self.bn2)
+        return K.conve.hip_path_ok(mods, (self.bn0, self.bn1, self.bn2), tensors)
+
+    def embed(self, graph):
+        """(n_feats, r_feats): the CompGCN stack's entity and relation embeddings, the operands of ``query``."""
+        return self.compGCN_Model(graph)
+
+    def query(self, sub_emb, rel_emb):
+        """The hidden vector after bn2 + ReLU [B, D], the row every entity is scored against (logit = query . entity + bias[entity]):
+        forward without its last product, bias and sigmoid.  Like forward it draws the dropout masks and, in train mode, updates the
+        BatchNorm statistics: one call per step.  HIP operands only (``_hip_ok``)."""
+        self._check_image()
+        if not self._hip_ok((sub_emb, rel_emb)):
+            raise MrgnasError("CompGCN_ConvE.query runs the ConvE kernels: float32 HIP operands, no autocast, no forward hooks on the "
+                              "scorer's submodules, BatchNorms that track running statistics (no CPU or torch fallback)")
+        return K.conve_query(sub_emb, rel_emb, K.conve.INTERLEAVED, (2 * self.k_w, self.k_h), self.bn0, self.m_conv1, self.bn1,
+                             self.feature_drop, self.fc, self.hidden_drop, self.bn2, self._one)
+
+    def loss_1n(self, graph, sub, rel, label_index, label_smooth=0.0, col_chunk=None):
+        """BCELoss(forward(graph, sub, rel), label_index.labels(sub, rel, label_smooth)) -- the reference's training loss -- as a float32
+        scalar with no [B, N] tensor: one embed, one query, then the fused 1-N loss with the entity bias in its epilogue
+        (functional.rows_bce_all(..., bias=self.bias)).  label_index: sampler.LabelIndex on the same device.  No host synchronisation;
+        no CPU or torch fallback (MrgnasError)."""
+        self._check_image()
+        if not (self.bias.is_cuda and sub.is_cuda and rel.is_cuda):
+            raise MrgnasError("CompGCN_ConvE.loss_1n runs on a HIP device (no CPU or torch fallback); got the model on "
+                              f"{self.bias.device} and the batch on {sub.device}")
+        n_feats, r_feats = self.embed(graph)
+        sub_emb, rel_emb = n_feats[sub, :], r_feats[rel, :]
+        if not self._hip_ok((n_feats, sub_emb, rel_emb)):
+            raise MrgnasError("CompGCN_ConvE.loss_1n runs on a HIP device in float32 without autocast or forward hooks on the scorer's "
+                              "submodules (no CPU or torch fallback); use forward and F.binary_cross_entropy otherwise")
+        return K.rows_bce_all("dot", None, n_feats, self.query(sub_emb, rel_emb), label_index, sub, rel, label_smooth, col_chunk,
+                              _what="CompGCN_ConvE.loss_1n", bias=self.bias)
+
+    def forward(self, graph, sub, rel):
+        self._check_image()
+        n_feats, r_feats = self.embed(graph)
         sub_emb = n_feats[sub, :]
         rel_emb = r_feats[rel, :]
-        mods = (self.bn0, self.m_conv1, self.bn1, self.feature_drop, self.fc, self.hidden_drop, self.bn2)
-        if K.conve.hip_path_ok(mods, (self.bn0, self.bn1, self.bn2), (n_feats, sub_emb, rel_emb)):
-            return K.conve_scores(sub_emb, rel_emb, K.conve.INTERLEAVED, (2 * self.k_w, self.k_h), self.bn0, self.m_conv1, self.bn1,
-                                  self.feature_drop, self.fc, self.hidden_drop, self.bn2, self._one, n_feats, self.bias)
+        if self._hip_ok((n_feats, sub_emb, rel_emb)):
+            return K.linear(self.query(sub_emb, rel_emb), n_feats, self.bias, "sigmoid")        # the [B, N] product on the row GEMM
         x = self.bn0(self.concat(sub_emb, rel_emb))
         x = self.feature_drop(F.relu(self.bn1(self.m_conv1(x))))
         x = self.fc(x.view(-1, self.flat_sz))

@@ -53,6 +53,15 @@ constexpr bool epi_accum(int epi) { return epi == EPI_ACCUM || epi == EPI_ACCUM2
 // The selecting epilogue of mrg_rows_topk (topk.hip defines gemm_epilogue_topk and what it reads): rows are queries, columns are
 // entities, every (row, workgroup) leaves its k best unfiltered (value, id) pairs.  Kernel instances of their own.
 enum { EPI_TOPK = 13 };
+// The sweep epilogues under a per-entity score bias (CompGCN_ConvE: logit = acc + bias[column], GemmArgs::bias = the bias of the
+// launch's column 0): gemm_add_col_bias puts the bias into the accumulators, one float32 add per element, and the unbiased kind's
+// epilogue (epi_unbiased) runs on them -- nothing else changes.  Kernel instances of their own, so that the unbiased ones stay what
+// they are.  The rank's target score needs no instance: rank.hip adds bias[target] to the diagonal's result (rank_bias_tscore_k).
+enum { EPI_BCE_BIAS = 14, EPI_BCE_GRAD_BIAS = 15, EPI_RANK_BIAS = 16, EPI_TOPK_BIAS = 17 };
+constexpr bool epi_col_bias(int epi) { return epi >= EPI_BCE_BIAS && epi <= EPI_TOPK_BIAS; }
+constexpr int epi_unbiased(int epi) {
+  return epi == EPI_BCE_BIAS ? EPI_BCE : (epi == EPI_BCE_GRAD_BIAS ? EPI_BCE_GRAD : (epi == EPI_RANK_BIAS ? EPI_RANK : (epi == EPI_TOPK_BIAS ? EPI_TOPK : epi)));
+}
 struct GemmArgs;
 template <int NT>
 __device__ __forceinline__ void gemm_epilogue_topk(const GemmArgs& a, f32x16 (&acc)[NT], int64_t rowbase, int col0, int li, int lh);
@@ -143,6 +152,23 @@ inline void gemm_set_rank(GemmArgs& a, const RankEpi& r) {
 }
 __device__ __forceinline__ RankEpi gemm_rank(const GemmArgs& a) {
   return RankEpi{a.S, a.aux, a.row_seg, reinterpret_cast<const int32_t*>(a.Cin), reinterpret_cast<const int32_t*>(a.rowscale), a.relu_bits};
+}
+
+// acc[n][r] += bias[col0 + n * 32 + li]: the logit of a "dot" sweep with a per-entity bias (epi_col_bias kinds), formed before the
+// epilogue looks at the accumulators.  A column beyond N is not read: its lane re-reads the last valid column and adds 0.
+template <int NT>
+__device__ __forceinline__ void gemm_add_col_bias(const GemmArgs& a, f32x16 (&acc)[NT], int col0, int li) {
+  float bv[NT];
+#pragma unroll
+  for (int n = 0; n < NT; ++n) {
+    const int col = col0 + n * 32 + li;
+    const float b = a.bias[col < a.N ? col : a.N - 1];
+    bv[n] = col < a.N ? b : 0.f;
+  }
+#pragma unroll
+  for (int n = 0; n < NT; ++n)
+#pragma unroll
+    for (int r = 0; r < 16; ++r) acc[n][r] += bv[n];
 }
 
 // ---- DistMult ranking: "how many columns beat this row's target" as the GEMM's epilogue (reference utils/utils_rgcn.py:212-380) --
@@ -773,7 +799,12 @@ __global__ __launch_bounds__(MRG_BLOCK, (MT == 1 ? 2 : 1)) void rowgemm_k(GemmAr
   }
 
   // ---- epilogue
-  if constexpr (EPI == EPI_BCE) {
+  constexpr int EPU = epi_unbiased(EPI);
+  if constexpr (epi_col_bias(EPI)) {
+#pragma unroll
+    for (int m = 0; m < MT; ++m) gemm_add_col_bias<NT>(a, acc[m], col0, li);
+  }
+  if constexpr (EPU == EPI_BCE) {
     double s = 0.0;
 #pragma unroll
     for (int m = 0; m < MT; ++m) s += gemm_epilogue_bce<NT>(a, acc[m], row0 + wave * 32 * MT + m * 32, col0, li, lh);
@@ -782,10 +813,10 @@ __global__ __launch_bounds__(MRG_BLOCK, (MT == 1 ? 2 : 1)) void rowgemm_k(GemmAr
   }
 #pragma unroll
   for (int m = 0; m < MT; ++m) {
-    if constexpr (EPI == EPI_BCE_GRAD) gemm_epilogue_bce_grad<NT>(a, acc[m], row0 + wave * 32 * MT + m * 32, col0, li, lh, row0 + GBM <= a.rows);
-    else if constexpr (EPI == EPI_RANK) gemm_epilogue_rank<NT>(a, acc[m], row0 + wave * 32 * MT + m * 32, col0, li, lh);
-    else if constexpr (EPI == EPI_RANK_DIAG) gemm_epilogue_rank_diag<NT>(a, acc[m], row0 + wave * 32 * MT + m * 32, wave, li, lh);
-    else if constexpr (EPI == EPI_TOPK) gemm_epilogue_topk<NT>(a, acc[m], row0 + wave * 32 * MT + m * 32, col0, li, lh);
+    if constexpr (EPU == EPI_BCE_GRAD) gemm_epilogue_bce_grad<NT>(a, acc[m], row0 + wave * 32 * MT + m * 32, col0, li, lh, row0 + GBM <= a.rows);
+    else if constexpr (EPU == EPI_RANK) gemm_epilogue_rank<NT>(a, acc[m], row0 + wave * 32 * MT + m * 32, col0, li, lh);
+    else if constexpr (EPU == EPI_RANK_DIAG) gemm_epilogue_rank_diag<NT>(a, acc[m], row0 + wave * 32 * MT + m * 32, wave, li, lh);
+    else if constexpr (EPU == EPI_TOPK) gemm_epilogue_topk<NT>(a, acc[m], row0 + wave * 32 * MT + m * 32, col0, li, lh);
     else gemm_epilogue<NT, EPI>(a, acc[m], row0 + wave * 32 * MT + m * 32, col0, li, lh, row0 + GBM <= a.rows);
   }
 }

@@ -151,6 +151,8 @@ __global__ __launch_bounds__(256, 2) void rowgemm_x3s_k(GemmArgs a, const char* 
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");            // the tail's unused A fills: their registers must stay until they land
   asm volatile("" :: "v"(xr[0][0]), "v"(xr[0][1]), "v"(xr[1][0]), "v"(xr[1][1]), "v"(xr[2][0]), "v"(xr[2][1]));
 
+  constexpr int EPU = epi_unbiased(EPI);
+  if constexpr (epi_col_bias(EPI)) gemm_add_col_bias<NT>(a, acc, col0, li);     // the sweeps under a per-entity score bias
   if constexpr (epi_sums(EPI)) {
     // the weight slabs are done with: once every wave has read its last fragments, LDS holds the waves' sums
     // ([4 waves][2 lane halves][2][NT * 32] doubles: 28 KB of the 63 for seven tiles)
@@ -162,11 +164,11 @@ __global__ __launch_bounds__(256, 2) void rowgemm_x3s_k(GemmArgs a, const char* 
   }
   else if constexpr (EPI == EPI_SEGMAX) gemm_epilogue_segmax<NT>(a, acc, roww, col0, li, lh);
   else if constexpr (EPI == EPI_SEGSUM) gemm_epilogue_segsum<NT>(a, acc, roww, col0, li, lh);
-  else if constexpr (EPI == EPI_RANK) gemm_epilogue_rank<NT>(a, acc, roww, col0, li, lh);
-  else if constexpr (EPI == EPI_RANK_DIAG) gemm_epilogue_rank_diag<NT>(a, acc, roww, wave, li, lh);
-  else if constexpr (EPI == EPI_TOPK) gemm_epilogue_topk<NT>(a, acc, roww, col0, li, lh);
-  else if constexpr (EPI == EPI_BCE) gemm_bce_flush(a, gemm_epilogue_bce<NT>(a, acc, roww, col0, li, lh), reinterpret_cast<double*>(smem_b));
-  else if constexpr (EPI == EPI_BCE_GRAD) gemm_epilogue_bce_grad<NT>(a, acc, roww, col0, li, lh, row0 + GBM <= a.rows);
+  else if constexpr (EPU == EPI_RANK) gemm_epilogue_rank<NT>(a, acc, roww, col0, li, lh);
+  else if constexpr (EPU == EPI_RANK_DIAG) gemm_epilogue_rank_diag<NT>(a, acc, roww, wave, li, lh);
+  else if constexpr (EPU == EPI_TOPK) gemm_epilogue_topk<NT>(a, acc, roww, col0, li, lh);
+  else if constexpr (EPU == EPI_BCE) gemm_bce_flush(a, gemm_epilogue_bce<NT>(a, acc, roww, col0, li, lh), reinterpret_cast<double*>(smem_b));
+  else if constexpr (EPU == EPI_BCE_GRAD) gemm_epilogue_bce_grad<NT>(a, acc, roww, col0, li, lh, row0 + GBM <= a.rows);
   else gemm_epilogue<NT, EPI>(a, acc, roww, col0, li, lh, row0 + GBM <= a.rows);
 }
 

@@ -13,6 +13,10 @@
 // mrg_rows_rank is the same body for query rows the caller already holds (ConvE's hidden vector, any "dot" scorer): step 1 gathers
 // the target rows only.  rank_prep_k / rank_finish_k live in sweep_prep.hpp and the host code around them in
 // sweep_host.hpp, shared with the L1 sweeps of transe_1n.hip.
+// mrg_rows_bias_rank is mrg_rows_rank under a per-entity score bias, x_e = q . ent[e] + bias[e] (CompGCN_ConvE): the sweep runs as
+// EPI_RANK_BIAS (gemm.hpp: the bias joins the accumulators, then EPI_RANK's epilogue), and between steps 2 and 3 rank_bias_tscore_k
+// adds bias[t_i] to the target scores -- the float32 add on the same two values that the sweep forms for the target's column, so a
+// duplicate entity row with an equal bias still ties bit for bit.
 #include "gemm_dispatch.hpp"
 #include "sweep_host.hpp"      // the launch bounds, the workspace's rounding and base, the checks; rank_prep_k, rank_finish_k
 
@@ -35,7 +39,19 @@ inline RankPlan rank_plan(int64_t Q, int64_t N, int D) {
   return p;
 }
 
-// one chunk: target scores, then the sweep.  g: A1 / K1 / rows and the rank pointers of the chunk are set
+// tscore[i] += bias[target of query i] (qinfo[i][0]): the target's logit under a score bias, after EPI_RANK_DIAG and before the sweep
+static __global__ void rank_bias_tscore_k(const float* __restrict__ bias, const int32_t* __restrict__ qinfo, float* __restrict__ tscore, int64_t rows) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < rows) tscore[i] = tscore[i] + bias[qinfo[i * 4]];
+}
+// g: a chunk's arguments, gemm_set_rank done (qinfo travels in row_seg, tscore_out in aux).  g.bias == NULL: nothing to do
+static int rank_bias_tscore(const GemmArgs& g, hipStream_t st) {
+  if (!g.bias) return MRG_OK;
+  return sweep_launch_rows(rank_bias_tscore_k, g.rows, st, g.bias, g.row_seg, g.aux, g.rows);
+}
+
+// one chunk: target scores, then the sweep.  g: A1 / K1 / rows and the rank pointers of the chunk are set; g.bias: [N] or NULL
+template <int EPI>
 inline int rank_chunk_split(GemmArgs g, const float* T, void* t_split, const void* ent_split, int64_t N, int D, hipStream_t st) {
   GemmArgs d = g;
   d.N = (int)g.rows;
@@ -43,20 +59,24 @@ inline int rank_chunk_split(GemmArgs g, const float* T, void* t_split, const voi
   int rc = launch_kernel(rowgemm_x3s_k<4, EPI_RANK_DIAG, false>, dim3((unsigned)((g.rows + 127) / 128), 1), dim3(256), (size_t)3 * 4 * 3 * 1024, st,
                          d, (const char*)t_split, x3_tiles(d.N, 4));
   if (rc != MRG_OK) return rc;
+  rc = rank_bias_tscore(g, st);
+  if (rc != MRG_OK) return rc;
   g.N = (int)N;
   const int ntile = x3_tiles(g.N, RANK_NT);
-  return launch_kernel(rowgemm_x3s_k<RANK_NT, EPI_RANK, false>, dim3((unsigned)((g.rows + 127) / 128), (unsigned)(ntile / RANK_NT)), dim3(256),
+  return launch_kernel(rowgemm_x3s_k<RANK_NT, EPI, false>, dim3((unsigned)((g.rows + 127) / 128), (unsigned)(ntile / RANK_NT)), dim3(256),
                        (size_t)3 * RANK_NT * 3 * 1024, st, g, (const char*)ent_split, ntile);
 }
 
-template <bool VEC4>
+template <int EPI, bool VEC4>
 inline int rank_chunk_exact(GemmArgs g, const float* T, const float* ent, int64_t N, int D, hipStream_t st) {
   GemmArgs d = g;
   d.N = (int)g.rows; d.B = T; d.ldb = D;
   int rc = launch_kernel(rowgemm_k<4, 1, 16, EPI_RANK_DIAG, VEC4>, dim3((unsigned)((g.rows + 127) / 128), 1), dim3(MRG_BLOCK), gemm_lds_bytes(4, 1, 16), st, d);
   if (rc != MRG_OK) return rc;
+  rc = rank_bias_tscore(g, st);
+  if (rc != MRG_OK) return rc;
   g.N = (int)N; g.B = ent; g.ldb = D;
-  return launch_kernel(rowgemm_k<RANK_NT, 1, 16, EPI_RANK, VEC4>, dim3((unsigned)((g.rows + 127) / 128), (unsigned)((N + RANK_NT * 32 - 1) / (RANK_NT * 32))),
+  return launch_kernel(rowgemm_k<RANK_NT, 1, 16, EPI, VEC4>, dim3((unsigned)((g.rows + 127) / 128), (unsigned)((N + RANK_NT * 32 - 1) / (RANK_NT * 32))),
                        dim3(MRG_BLOCK), gemm_lds_bytes(RANK_NT, 1, 16), st, g);
 }
 
@@ -69,9 +89,9 @@ extern "C" int64_t mrg_distmult_rank_workspace_bytes(int64_t Q, int64_t N, int D
   return (int64_t)rank_plan(Q, N, D).total;
 }
 
-// The body of both entry points.  rows_q == NULL: the chunk's query rows are ent[a] * rel[r] (mrg_distmult_rank); else they are the
-// caller's rows_q + q0 * D (mrg_rows_rank).  The target rows are gathered in both.
-static int rank_run(const float* rows_q, const float* ent, const float* rel, const int32_t* a_idx, const int32_t* r_idx, const int32_t* t_idx,
+// The body of the three entry points.  rows_q == NULL: the chunk's query rows are ent[a] * rel[r] (mrg_distmult_rank); else they are the
+// caller's rows_q + q0 * D (mrg_rows_rank; bias != NULL: mrg_rows_bias_rank).  The target rows are gathered in all.
+static int rank_run(const float* rows_q, const float* ent, const float* bias, const float* rel, const int32_t* a_idx, const int32_t* r_idx, const int32_t* t_idx,
                     const int64_t* qkey, const int32_t* when, const int64_t* keys, const int32_t* rowptr, const int32_t* members,
                     const int32_t* gone_at, int64_t U, int64_t Q, int64_t N, int D, int64_t* ranks, void* ws, int64_t ws_bytes, void* stream) {
   if (!sweep_labels_ok(U, qkey, when, keys, rowptr, members, gone_at)) return MRG_E_NULLPTR;
@@ -100,11 +120,16 @@ static int rank_run(const float* rows_q, const float* ent, const float* rel, con
     rc = mrg_gather_compose_fwd(-1, ent, rel, t_idx + q0, rows_q ? nullptr : r_idx + q0, T, rows, D, stream);
     if (rc != MRG_OK) return rc;
     GemmArgs g{};
-    g.A1 = Aq; g.A2 = Aq; g.K1 = D; g.K2 = 0; g.rows = rows;
+    g.A1 = Aq; g.A2 = Aq; g.K1 = D; g.K2 = 0; g.rows = rows; g.bias = bias;      // (the sweep covers all N columns: column 0 is entity 0)
     gemm_set_rank(g, RankEpi{tscore + q0, tscore + q0, qinfo + q0 * 4, members, gone_at, counts + q0});
-    if (split) rc = rank_chunk_split(g, T, w + p.t_split, w + p.ent_split, N, D, st);
-    else if (vec) rc = rank_chunk_exact<true>(g, T, ent, N, D, st);
-    else rc = rank_chunk_exact<false>(g, T, ent, N, D, st);
+    if (bias) {
+      if (split) rc = rank_chunk_split<EPI_RANK_BIAS>(g, T, w + p.t_split, w + p.ent_split, N, D, st);
+      else if (vec) rc = rank_chunk_exact<EPI_RANK_BIAS, true>(g, T, ent, N, D, st);
+      else rc = rank_chunk_exact<EPI_RANK_BIAS, false>(g, T, ent, N, D, st);
+    }
+    else if (split) rc = rank_chunk_split<EPI_RANK>(g, T, w + p.t_split, w + p.ent_split, N, D, st);
+    else if (vec) rc = rank_chunk_exact<EPI_RANK, true>(g, T, ent, N, D, st);
+    else rc = rank_chunk_exact<EPI_RANK, false>(g, T, ent, N, D, st);
     if (rc != MRG_OK) return rc;
   }
   return sweep_launch_rows(rank_finish_k, Q, st, counts, ranks, Q);
@@ -117,7 +142,7 @@ extern "C" int mrg_distmult_rank(const float* ent, const float* rel, const int32
   if (U < 0 || !sweep_shape_ok(Q, N, D, true)) return MRG_E_SHAPE;
   if (Q == 0) return MRG_OK;
   if (!ent || !rel || !a_idx || !r_idx || !t_idx || !ranks) return MRG_E_NULLPTR;
-  return rank_run(nullptr, ent, rel, a_idx, r_idx, t_idx, qkey, when, keys, rowptr, members, gone_at, U, Q, N, D, ranks, ws, ws_bytes, stream);
+  return rank_run(nullptr, ent, nullptr, rel, a_idx, r_idx, t_idx, qkey, when, keys, rowptr, members, gone_at, U, Q, N, D, ranks, ws, ws_bytes, stream);
 }
 
 extern "C" int mrg_rows_rank(const float* q, const float* ent, const int32_t* t_idx, const int64_t* qkey, const int32_t* when, const int64_t* keys,
@@ -126,5 +151,15 @@ extern "C" int mrg_rows_rank(const float* q, const float* ent, const int32_t* t_
   if (U < 0 || !sweep_shape_ok(Q, N, D, true)) return MRG_E_SHAPE;
   if (Q == 0) return MRG_OK;
   if (!q || !ent || !t_idx || !ranks) return MRG_E_NULLPTR;
-  return rank_run(q, ent, nullptr, nullptr, nullptr, t_idx, qkey, when, keys, rowptr, members, gone_at, U, Q, N, D, ranks, ws, ws_bytes, stream);
+  return rank_run(q, ent, nullptr, nullptr, nullptr, nullptr, t_idx, qkey, when, keys, rowptr, members, gone_at, U, Q, N, D, ranks, ws, ws_bytes, stream);
+}
+
+extern "C" int mrg_rows_bias_rank(const float* q, const float* ent, const float* bias, const int32_t* t_idx, const int64_t* qkey,
+                                  const int32_t* when, const int64_t* keys, const int32_t* rowptr, const int32_t* members,
+                                  const int32_t* gone_at, int64_t U, int64_t Q, int64_t N, int D, int64_t* ranks, void* ws, int64_t ws_bytes,
+                                  void* stream) {
+  if (U < 0 || !sweep_shape_ok(Q, N, D, true)) return MRG_E_SHAPE;
+  if (Q == 0) return MRG_OK;
+  if (!q || !ent || !bias || !t_idx || !ranks) return MRG_E_NULLPTR;
+  return rank_run(q, ent, bias, nullptr, nullptr, nullptr, t_idx, qkey, when, keys, rowptr, members, gone_at, U, Q, N, D, ranks, ws, ws_bytes, stream);
 }

@@ -8,6 +8,9 @@
 // Core selection is mrg_rows_rank's -- split-bf16 (rowgemm_x3s_k) for D > 48, D % 4 == 0 and 16-byte aligned rows, else exact f32
 // (rowgemm_k) -- and a column's accumulator does not depend on how the columns are cut into blocks, so the values returned are the
 // ones mrg_rows_rank compares, bit for bit.
+// mrg_rows_bias_topk is the same sweep under a per-entity score bias, x_e = q . ent[e] + bias[e] (CompGCN_ConvE): EPI_TOPK_BIAS adds the
+// bias to the accumulators (gemm.hpp: gemm_add_col_bias; a column block that starts at entity c gets bias + c) and selects on them,
+// so the values are the ones mrg_rows_bias_rank compares.
 #include "gemm_dispatch.hpp"
 #include "topk_parts.hpp"
 
@@ -109,12 +112,11 @@ extern "C" int64_t mrg_rows_topk_workspace_bytes(int64_t Q, int64_t N, int D, in
   return (int64_t)topk_rows_plan(Q, N, D, k).total;
 }
 
-extern "C" int mrg_rows_topk(const float* q, const float* ent, const int64_t* qkey, const int32_t* when, const int64_t* keys,
-                             const int32_t* rowptr, const int32_t* members, const int32_t* gone_at, int64_t U, int64_t Q, int64_t N, int D,
-                             int k, int32_t* ids, float* vals, void* ws, int64_t ws_bytes, void* stream) {
-  if (U < 0 || !sweep_shape_ok(Q, N, D, true) || !topk_k_ok(k)) return MRG_E_SHAPE;
-  if (Q == 0) return MRG_OK;
-  if (!q || !ent || !ids || !vals) return MRG_E_NULLPTR;
+// The body of both entry points; bias == NULL: mrg_rows_topk, else mrg_rows_bias_topk.
+template <int EPI>
+static int topk_rows_run(const float* q, const float* ent, const float* bias, const int64_t* qkey, const int32_t* when, const int64_t* keys,
+                         const int32_t* rowptr, const int32_t* members, const int32_t* gone_at, int64_t U, int64_t Q, int64_t N, int D,
+                         int k, int32_t* ids, float* vals, void* ws, int64_t ws_bytes, void* stream) {
   if (!sweep_labels_ok(U, qkey, when, keys, rowptr, members, gone_at)) return MRG_E_NULLPTR;
   const TopkPlan p = topk_rows_plan(Q, N, D, k);
   if (!ws || ws_bytes < (int64_t)p.total) return MRG_E_WORKSPACE;
@@ -133,20 +135,39 @@ extern "C" int mrg_rows_topk(const float* q, const float* ent, const int64_t* qk
     GemmArgs g{};
     g.A1 = q + q0 * D; g.A2 = g.A1; g.K1 = D; g.K2 = 0; g.rows = rows; g.N = (int)nc;
     gemm_set_topk(g, TopkEpi{qinfo + q0 * 4, members, gone_at, part, k, (int)c, vals + q0 * k, ids + q0 * k});
+    if (epi_col_bias(EPI)) g.bias = bias + c;
     const dim3 grid(sg.row_tiles(rows), sg.col_tiles(nc));
     const float* ent_c = ent + c * D;
     int rc2;
     // (the split of a column block is redone per row chunk: the launches of one block share the buffer in stream order)
     if (split) {
       launch_bsplit(ent_c, D, 1, g.N, D, RANK_NT, ent_split, st);
-      rc2 = launch_kernel(rowgemm_x3s_k<RANK_NT, EPI_TOPK, false>, grid, dim3(256), (size_t)3 * RANK_NT * 3 * 1024, st, g, (const char*)ent_split,
+      rc2 = launch_kernel(rowgemm_x3s_k<RANK_NT, EPI, false>, grid, dim3(256), (size_t)3 * RANK_NT * 3 * 1024, st, g, (const char*)ent_split,
                           x3_tiles(g.N, RANK_NT));
     } else {
       g.B = ent_c; g.ldb = D;
-      if (vec) rc2 = launch_kernel(rowgemm_k<RANK_NT, 1, 16, EPI_TOPK, true>, grid, dim3(MRG_BLOCK), gemm_lds_bytes(RANK_NT, 1, 16), st, g);
-      else rc2 = launch_kernel(rowgemm_k<RANK_NT, 1, 16, EPI_TOPK, false>, grid, dim3(MRG_BLOCK), gemm_lds_bytes(RANK_NT, 1, 16), st, g);
+      if (vec) rc2 = launch_kernel(rowgemm_k<RANK_NT, 1, 16, EPI, true>, grid, dim3(MRG_BLOCK), gemm_lds_bytes(RANK_NT, 1, 16), st, g);
+      else rc2 = launch_kernel(rowgemm_k<RANK_NT, 1, 16, EPI, false>, grid, dim3(MRG_BLOCK), gemm_lds_bytes(RANK_NT, 1, 16), st, g);
     }
     if (rc2 != MRG_OK) return rc2;
     return topk_merge_launch<true>(part, (int)grid.y, k, rows, ids + q0 * k, vals + q0 * k, st);
   });
+}
+
+extern "C" int mrg_rows_topk(const float* q, const float* ent, const int64_t* qkey, const int32_t* when, const int64_t* keys,
+                             const int32_t* rowptr, const int32_t* members, const int32_t* gone_at, int64_t U, int64_t Q, int64_t N, int D,
+                             int k, int32_t* ids, float* vals, void* ws, int64_t ws_bytes, void* stream) {
+  if (U < 0 || !sweep_shape_ok(Q, N, D, true) || !topk_k_ok(k)) return MRG_E_SHAPE;
+  if (Q == 0) return MRG_OK;
+  if (!q || !ent || !ids || !vals) return MRG_E_NULLPTR;
+  return topk_rows_run<EPI_TOPK>(q, ent, nullptr, qkey, when, keys, rowptr, members, gone_at, U, Q, N, D, k, ids, vals, ws, ws_bytes, stream);
+}
+
+extern "C" int mrg_rows_bias_topk(const float* q, const float* ent, const float* bias, const int64_t* qkey, const int32_t* when,
+                                  const int64_t* keys, const int32_t* rowptr, const int32_t* members, const int32_t* gone_at, int64_t U,
+                                  int64_t Q, int64_t N, int D, int k, int32_t* ids, float* vals, void* ws, int64_t ws_bytes, void* stream) {
+  if (U < 0 || !sweep_shape_ok(Q, N, D, true) || !topk_k_ok(k)) return MRG_E_SHAPE;
+  if (Q == 0) return MRG_OK;
+  if (!q || !ent || !bias || !ids || !vals) return MRG_E_NULLPTR;
+  return topk_rows_run<EPI_TOPK_BIAS>(q, ent, bias, qkey, when, keys, rowptr, members, gone_at, U, Q, N, D, k, ids, vals, ws, ws_bytes, stream);
 }

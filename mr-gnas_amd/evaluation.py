@@ -109,7 +109,8 @@ def predict_fused(val_test_loader, g, model, label_index, device):
 
 def predict_1n(val_test_loader, g, model, label_index, device):
     """predict_fused for every scorer that follows the scorer protocol (operations_lp: ``query`` and ``score_kind``): DistMult, ConvE
-    ("dot") and TransE ("l1").  Per batch one model.embed(g) and one score_func.query(ent[s], rel_emb[r]); the ranks come from
+    ("dot"), TransE ("l1") and a "dot" scorer with a ``score_bias`` (compgcn.CompGCN_ConvE, its own scorer: the bias goes to the ranks
+    and to the loss).  Per batch one model.embed(g) and one score_func.query(ent[s], rel_emb[r]); the ranks come from
     query_ranks with label_index as the filter and when = -1, the batch's mean BCE from mrg_distmult_bce_fwd / mrg_transe_bce_fwd on the
     unsmoothed labels.  "dot" ranks are taken on the logits, "l1" ranks on the distances: where predict's float32 sigmoid ties
     different logits -- with gamma = 40 and realistic L1 distances it saturates to exactly 0 and ties whole rows -- the value
@@ -123,6 +124,7 @@ def predict_1n(val_test_loader, g, model, label_index, device):
         raise MrgnasError(f"predict_1n needs a scorer with query() and a score_kind of 'dot' or 'l1'; this network scores with {type(sf).__name__}")
     side = _LabelSide(label_index)
     v_zero, v_one = label_index.label_values(0.0)
+    bias = getattr(sf, "score_bias", None)                  # a "dot" scorer's optional per-entity bias (CompGCN_ConvE)
     ks, acc = _stats_begin(device)
     with torch.no_grad():
         model.eval()
@@ -134,11 +136,11 @@ def predict_1n(val_test_loader, g, model, label_index, device):
             q = f32c(sf.query(K.gather_rows(ent, s), K.gather_rows(f32c(rel_emb), r)))
             when = torch.full((s.numel(),), -1, dtype=torch.int32, device=device)
             qkey = (s.long() * side.num_rels + r.long()).contiguous()
-            ranks = query_ranks(q, ent, o, side, when, qkey, kind).double()
+            ranks = query_ranks(q, ent, o, side, when, qkey, kind, bias=bias).double()
             if kind == "l1":
                 loss = K.transe_bce_mean(q, ent, sf.gamma, label_index, qkey, v_zero, v_one)
             else:
-                loss = K.distmult_bce_mean(q, ent, label_index, qkey, v_zero, v_one)
+                loss = K.distmult_bce_mean(q, ent, label_index, qkey, v_zero, v_one, bias=bias)
             acc += _batch_stats(ranks, loss, ks)
     return _stats_end(acc)
 
@@ -233,6 +235,15 @@ def _filter_side(msg, known_side, when, qkey, Q):
     return qkey, when, k.keys, k.rowptr, k.members, k.gone_at, k.keys.numel()
 
 
+def _score_bias(what, bias, kind, N):
+    """An optional per-entity score bias of a "dot" sweep, checked before any device check (functional.score_bias_arg): float32 [N]."""
+    from .functional.scoring import score_bias_arg
+    bias = score_bias_arg(what, bias, kind, N)
+    if bias is not None and not bias.is_cuda:
+        raise MrgnasError(f"{what} runs on a HIP device (no CPU fallback)")
+    return None if bias is None else bias.detach()
+
+
 def _rank_call(name, ws_name, ws_err, head, side, Q, N, D, like):
     """ranks [Q] of entry point `name`(*head, *side, Q, N, D, ranks, workspace, stream): the workspace queried (ws_name; an error code is
     raised under ws_err) and allocated beside `like`."""
@@ -261,13 +272,15 @@ def distmult_ranks(embedding, w, a, r, target, known_side=None, when=None):
                       (embedding, w, a, r, target), side, Q, N, D, embedding)
 
 
-def query_ranks(q, ent, target, known_side=None, when=None, qkey=None, kind="dot"):
+def query_ranks(q, ent, target, known_side=None, when=None, qkey=None, kind="dot", bias=None):
     """ranks [Q] int64 (1-based) of `target` among all entities for query rows q [Q, D] the caller holds (a scorer's ``query``).
     kind "dot": the score is q . ent[e] (mrg_rows_rank: distmult_ranks from the point where the rows exist); kind "l1": the score is
     -||q - ent[e]||_1, compared on the distance itself (mrg_transe_rank).  known_side / when as in distmult_ranks, with qkey [Q] int64
-    the queries' keys into known_side (fixed entity * num_rels + relation); None for raw ranks."""
+    the queries' keys into known_side (fixed entity * num_rels + relation); None for raw ranks.  bias [N] (kind "dot" only, else
+    ValueError): the score is q . ent[e] + bias[e] (mrg_rows_bias_rank)."""
     if kind not in ("dot", "l1"):
         raise ValueError("query_ranks: kind is 'dot' or 'l1'")
+    bias = _score_bias("query_ranks", bias, kind, ent.shape[0])
     if not (q.is_cuda and ent.is_cuda and target.is_cuda):
         raise MrgnasError("query_ranks runs on a HIP device (no CPU fallback)")
     q, ent, target = f32c(q), f32c(ent), target.int().contiguous()
@@ -277,6 +290,9 @@ def query_ranks(q, ent, target, known_side=None, when=None, qkey=None, kind="dot
         raise ValueError("query_ranks: q [Q, D], ent [N, D] and target [Q] expected")
     side = _filter_side("query_ranks: a filtered call needs when [Q] and qkey [Q]", known_side, when, qkey, Q)
     name, ws_name = ("mrg_rows_rank", "mrg_distmult_rank_workspace_bytes") if kind == "dot" else ("mrg_transe_rank", "mrg_transe_rank_workspace_bytes")
+    if bias is not None:
+        require_hip(bias)
+        return _rank_call("mrg_rows_bias_rank", ws_name, "mrg_rows_bias_rank", (q, ent, bias, target), side, Q, N, D, q)
     return _rank_call(name, ws_name, name, (q, ent, target), side, Q, N, D, q)
 
 
@@ -362,15 +378,17 @@ def predict_mix(loader, ent, rel_emb, weights, gamma, label_index, device, conve
 _TOPK_MAX = 64
 
 
-def query_topk(q, ent, k, known_side=None, when=None, qkey=None, kind="dot"):
+def query_topk(q, ent, k, known_side=None, when=None, qkey=None, kind="dot", bias=None):
     """(ids [Q, k] int64, values [Q, k] float32): per query row of q [Q, D] the k best unfiltered entities, best first, without a
     [Q, N] tensor -- the twin of query_ranks.  kind "dot": the largest logits q . ent[e] (mrg_rows_topk); kind "l1": the smallest
     distances ||q - ent[e]||_1 (mrg_transe_topk).  Equal values: the lower entity id first.  known_side / when / qkey as in
     query_ranks; there is no target, so every member with gone_at > when is excluded.  values are the float32 accumulators the rank
     sweeps compare, so query_ranks(q, ent, ids[:, j], ...) == j + 1.  Where fewer than k candidates remain the tail is id -1 with
-    value -inf ("dot") / +inf ("l1")."""
+    value -inf ("dot") / +inf ("l1").  bias [N] (kind "dot" only, else ValueError): the logits, and the values returned, are
+    q . ent[e] + bias[e] (mrg_rows_bias_topk), the numbers query_ranks(..., bias=bias) compares."""
     if kind not in ("dot", "l1"):
         raise ValueError("query_topk: kind is 'dot' or 'l1'")
+    bias = _score_bias("query_topk", bias, kind, ent.shape[0])
     k = int(k)
     if not 1 <= k <= _TOPK_MAX:
         raise ValueError(f"query_topk: 1 <= k <= {_TOPK_MAX} (got {k}); for a longer list run the dense forward, model(g, subj, rel), "
@@ -384,13 +402,18 @@ def query_topk(q, ent, k, known_side=None, when=None, qkey=None, kind="dot"):
     (Q, D), N = q.shape, ent.shape[0]
     side = _filter_side("query_topk: a filtered call needs when [Q] and qkey [Q]", known_side, when, qkey, Q)
     name = "mrg_rows_topk" if kind == "dot" else "mrg_transe_topk"
+    ws_name = name + "_workspace_bytes"
+    head = (ptr(q), ptr(ent))
+    if bias is not None:
+        require_hip(bias)
+        name, head = "mrg_rows_bias_topk", (ptr(q), ptr(ent), ptr(bias))               # (same workspace)
     ids = torch.empty(Q, k, dtype=torch.int32, device=q.device)
     vals = torch.empty(Q, k, dtype=torch.float32, device=q.device)
-    nbytes = getattr(load(), name + "_workspace_bytes")(Q, N, D, k)
+    nbytes = getattr(load(), ws_name)(Q, N, D, k)
     if nbytes < 0:
         check(int(nbytes), name)
     ws = torch.empty(max(int(nbytes), 1), dtype=torch.uint8, device=q.device)
-    call(name, (ptr(q), ptr(ent), *(ptr(t) for t in side[:6]), side[6], Q, N, D, k, ptr(ids), ptr(vals), ptr(ws), int(nbytes), stream_of(q)),
+    call(name, (*head, *(ptr(t) for t in side[:6]), side[6], Q, N, D, k, ptr(ids), ptr(vals), ptr(ws), int(nbytes), stream_of(q)),
          nbytes=4 * (Q + N) * D, flops=2 * Q * N * D)
     return ids.long(), vals
 
@@ -418,13 +441,14 @@ def predict_topk(model, g, subj, rel, k, label_index=None):
         ent, rel_emb = model.embed(g)
         ent = f32c(ent)
         q = f32c(sf.query(K.gather_rows(ent, s), K.gather_rows(f32c(rel_emb), r)))
+        bias = getattr(sf, "score_bias", None)
         if label_index is None:
-            ids, vals = query_topk(q, ent, k, kind=kind)
+            ids, vals = query_topk(q, ent, k, kind=kind, bias=bias)
         else:
             side = _LabelSide(label_index)
             when = torch.full((s.numel(),), -1, dtype=torch.int32, device=q.device)
             qkey = (s.long() * side.num_rels + r.long()).contiguous()
-            ids, vals = query_topk(q, ent, k, side, when, qkey, kind)
+            ids, vals = query_topk(q, ent, k, side, when, qkey, kind, bias=bias)
         prob = torch.sigmoid(sf.gamma - vals) if kind == "l1" else torch.sigmoid(vals)
         return ids, torch.where(ids >= 0, prob, torch.zeros_like(prob))
 

@@ -69,7 +69,7 @@ from .cell_zero import (  # noqa: F401
 from .scoring import (  # noqa: F401
     ScorePlan, _DistMult, distmult_score, distmult_scores_all, _TransE, transe_scores_all,
     _BCE1N, rows_bce_all, dot_bce_all, distmult_bce_all, distmult_bce_mean, distmult_bce_dlogit, bce_default_col_chunk,
-    transe_bce_all, transe_bce_mean, transe_bce_dlogit,
+    transe_bce_all, transe_bce_mean, transe_bce_dlogit, cols_sum, score_bias_arg,
 )
 from .sf_mix import (  # noqa: F401
     _MixBCE1N, sf_mix_bce_all, sf_mix_bce_mean, sf_mix_bce_grad,

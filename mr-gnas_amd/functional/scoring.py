@@ -84,6 +84,25 @@ def bce_default_col_chunk(B):
 # csrc/transe_1n.hip).  The "l1" calls take gamma in front of v_zero; everything else is the same argument list.
 _BCE_ENTRY = {"dot": ("mrg_distmult_bce_workspace_bytes", "mrg_distmult_bce_fwd", "mrg_distmult_bce_dlogit"),
               "l1": ("mrg_transe_bce_workspace_bytes", "mrg_transe_bce_fwd", "mrg_transe_bce_dlogit")}
+# The "dot" calls with a per-entity score bias (logit = q . entity + bias[entity]: CompGCN_ConvE): the bias pointer follows ent; same
+# workspace.  Kernel instances of their own: a call without a bias runs what it always ran.
+_BCE_BIAS_ENTRY = ("mrg_distmult_bce_workspace_bytes", "mrg_rows_bias_bce_fwd", "mrg_rows_bias_bce_dlogit")
+
+
+def _bce_entry(kind, bias):
+    return _BCE_ENTRY[kind] if bias is None else _BCE_BIAS_ENTRY         # (score_bias_arg has refused a bias with kind "l1")
+
+
+def score_bias_arg(what, bias, kind, N):
+    """The checks of an optional per-entity score bias, before any device check: None stays None; else kind must be "dot" and the
+    bias [N].  Returns it float32 and contiguous."""
+    if bias is None:
+        return None
+    if kind != "dot":
+        raise ValueError(f"{what}: a score bias is defined for \"dot\" scorers only (logit = q . entity + bias[entity]); kind \"{kind}\" has none")
+    if bias.dim() != 1 or int(bias.numel()) != int(N):
+        raise ValueError(f"{what}: bias [num_ent] = [{int(N)}] expected, got {list(bias.shape)}")
+    return f32c(bias)
 
 
 def _checked_ws(name, B, cols, D, like):
@@ -93,34 +112,39 @@ def _checked_ws(name, B, cols, D, like):
     return _ws(nbytes, like), int(nbytes)
 
 
-def _bce_mean(kind, gamma, q, ent, li, qkey, v_zero, v_one):
-    ws_name, fwd, _ = _BCE_ENTRY[kind]
+def _bce_mean(kind, gamma, q, ent, li, qkey, v_zero, v_one, bias=None):
+    ws_name, fwd, _ = _bce_entry(kind, bias)
     (B, D), N = q.shape, ent.shape[0]
     loss = torch.empty((), dtype=torch.float32, device=q.device)
     ws, nbytes = _checked_ws(ws_name, B, N, D, q)
     values = (float(gamma), v_zero, v_one) if kind == "l1" else (v_zero, v_one)
-    call(fwd, (ptr(q), ptr(ent), ptr(qkey), ptr(li.keys), ptr(li.rowptr), ptr(li.objs), int(li.keys.numel()), *values, B, N, D,
+    head = (ptr(q), ptr(ent)) if bias is None else (ptr(q), ptr(ent), ptr(bias))
+    call(fwd, (*head, ptr(qkey), ptr(li.keys), ptr(li.rowptr), ptr(li.objs), int(li.keys.numel()), *values, B, N, D,
                ptr(loss), ptr(ws), nbytes, stream_of(q)),
          nbytes=4 * (B + N) * D, flops=2 * B * N * D)
     return loss
 
 
-def _bce_dlogit(kind, gamma, q, ent, li, qkey, v_zero, v_one, c0, c1, gscale, out):
-    ws_name, _, dlogit = _BCE_ENTRY[kind]
+def _bce_dlogit(kind, gamma, q, ent, li, qkey, v_zero, v_one, c0, c1, gscale, out, bias=None):
+    ws_name, _, dlogit = _bce_entry(kind, bias)
     (B, D), N, nc = q.shape, ent.shape[0], c1 - c0
     if out is None:
         out = torch.empty(B * nc, dtype=torch.float32, device=q.device)
     ws, nbytes = _checked_ws(ws_name, B, nc, D, q)
     values = (float(gamma), v_zero, v_one) if kind == "l1" else (v_zero, v_one)
-    call(dlogit, (ptr(q), ptr(ent), ptr(qkey), ptr(li.keys), ptr(li.rowptr), ptr(li.objs), int(li.keys.numel()), *values, B, N, D,
+    head = (ptr(q), ptr(ent)) if bias is None else (ptr(q), ptr(ent), ptr(bias))
+    call(dlogit, (*head, ptr(qkey), ptr(li.keys), ptr(li.rowptr), ptr(li.objs), int(li.keys.numel()), *values, B, N, D,
                   c0, c1, ptr(gscale), ptr(out), ptr(ws), nbytes, stream_of(q)),
          nbytes=4 * (B + nc) * D + 4 * B * nc, flops=2 * B * nc * D)
     return out[:B * nc].view(B, nc)
 
 
-def distmult_bce_mean(q, ent, label_index, qkey, v_zero, v_one):
-    """mrg_distmult_bce_fwd, no autograd: mean over [B, N] of BCE(sigmoid(q ent^T), labels) as a float32 device scalar."""
-    return _bce_mean("dot", None, q, ent, label_index, qkey, v_zero, v_one)
+def distmult_bce_mean(q, ent, label_index, qkey, v_zero, v_one, bias=None):
+    """mrg_distmult_bce_fwd, no autograd: mean over [B, N] of BCE(sigmoid(q ent^T), labels) as a float32 device scalar.  bias [N]:
+    the logits are q ent^T + bias (mrg_rows_bias_bce_fwd)."""
+    bias = score_bias_arg("distmult_bce_mean", bias, "dot", ent.shape[0])
+    require_hip(bias)
+    return _bce_mean("dot", None, q, ent, label_index, qkey, v_zero, v_one, bias)
 
 
 def transe_bce_mean(obj, ent, gamma, label_index, qkey, v_zero, v_one):
@@ -128,10 +152,23 @@ def transe_bce_mean(obj, ent, gamma, label_index, qkey, v_zero, v_one):
     return _bce_mean("l1", gamma, obj, ent, label_index, qkey, v_zero, v_one)
 
 
-def distmult_bce_dlogit(q, ent, label_index, qkey, v_zero, v_one, c0, c1, gscale, out=None):
+def distmult_bce_dlogit(q, ent, label_index, qkey, v_zero, v_one, c0, c1, gscale, out=None, bias=None):
     """mrg_distmult_bce_dlogit, no autograd: the loss gradient with respect to the logits of the entities [c0, c1) as [B, c1 - c0],
-    written into the first B * (c1 - c0) floats of `out` when given.  gscale: float32 [1] on the device (upstream gradient / (B N))."""
-    return _bce_dlogit("dot", None, q, ent, label_index, qkey, v_zero, v_one, c0, c1, gscale, out)
+    written into the first B * (c1 - c0) floats of `out` when given.  gscale: float32 [1] on the device (upstream gradient / (B N)).
+    bias [N]: the logits are q ent^T + bias (mrg_rows_bias_bce_dlogit)."""
+    bias = score_bias_arg("distmult_bce_dlogit", bias, "dot", ent.shape[0])
+    require_hip(bias)
+    return _bce_dlogit("dot", None, q, ent, label_index, qkey, v_zero, v_one, c0, c1, gscale, out, bias)
+
+
+def cols_sum(x, out=None):
+    """mrg_cols_sum, no autograd: the column sums of x [rows, cols] float32 as [cols] float32 (into `out` when given), accumulated in
+    float64 in a fixed order -- no float atomics, the same bits on every call.  The bias gradient of a logit-gradient slice."""
+    rows, cols = x.shape
+    if out is None:
+        out = torch.empty(cols, dtype=torch.float32, device=x.device)
+    call("mrg_cols_sum", (ptr(x), rows, cols, cols, ptr(out), stream_of(x)), nbytes=4 * (rows + 1) * cols)
+    return out
 
 
 def transe_bce_dlogit(obj, ent, gamma, label_index, qkey, v_zero, v_one, c0, c1, gscale, out=None):
@@ -190,22 +227,24 @@ class _BCE1N(torch.autograd.Function):
     kind's work on it (_dot_chunk_bwd / _l1_chunk_bwd)."""
 
     @staticmethod
-    def forward(ctx, kind, gamma, q, ent, label_index, qkey, v_zero, v_one, col_chunk):
+    def forward(ctx, kind, gamma, q, ent, label_index, qkey, v_zero, v_one, col_chunk, bias=None):
         q, ent = f32c(q), f32c(ent)
         li = label_index
-        require_hip(q, ent, qkey, li.keys, li.rowptr, li.objs)
+        bias = score_bias_arg("the 1-N loss", bias, kind, ent.shape[0])
+        require_hip(q, ent, qkey, li.keys, li.rowptr, li.objs, bias)
         ctx.kind, ctx.gamma = kind, None if gamma is None else float(gamma)
         ctx.li, ctx.v, ctx.col_chunk = li, (v_zero, v_one), col_chunk
-        ctx.save_for_backward(q, ent, qkey)
-        return _bce_mean(kind, gamma, q, ent, li, qkey, v_zero, v_one)
+        ctx.save_for_backward(q, ent, qkey, bias)
+        return _bce_mean(kind, gamma, q, ent, li, qkey, v_zero, v_one, bias)
 
     @staticmethod
     def backward(ctx, g):
-        q, ent, qkey = ctx.saved_tensors
+        q, ent, qkey, bias = ctx.saved_tensors
         kind, li, (v_zero, v_one), step = ctx.kind, ctx.li, ctx.v, ctx.col_chunk
         (B, D), N, st = q.shape, ent.shape[0], stream_of(q)
         step = min(step, N)
         need_q, need_ent = ctx.needs_input_grad[2], ctx.needs_input_grad[3]
+        g_bias = torch.empty_like(bias) if bias is not None and ctx.needs_input_grad[9] else None
         gscale = (g.detach().float().reshape(1) / float(B * N)).contiguous()          # stays on the device: no host synchronisation
         dl = torch.empty(B * step, dtype=torch.float32, device=q.device)               # ONE slice, reused by every chunk
         g_q = torch.empty_like(q) if need_q else None
@@ -216,9 +255,11 @@ class _BCE1N(torch.autograd.Function):
         chunk_bwd = _dot_chunk_bwd if kind == "dot" else _l1_chunk_bwd
         for c0 in range(0, N, step):
             c1 = min(N, c0 + step)
-            _bce_dlogit(kind, ctx.gamma, q, ent, li, qkey, v_zero, v_one, c0, c1, gscale, dl)
+            dl_c = _bce_dlogit(kind, ctx.gamma, q, ent, li, qkey, v_zero, v_one, c0, c1, gscale, dl, bias)
+            if g_bias is not None:                                                     # g_bias[c0:c1] = the slice's column sums
+                cols_sum(dl_c, g_bias[c0:c1])
             chunk_bwd(q, ent, dl, c0, c1 - c0, g_q, g_ent, pre, st)
-        return None, None, g_q, g_ent, None, None, None, None, None
+        return None, None, g_q, g_ent, None, None, None, None, None, g_bias
 
 
 def _require_cuda(what, tensors):
@@ -242,21 +283,24 @@ def _bce_all_args(what, tensors, B, N, label_index, subj, rel, label_smooth, col
     return qkey, v_zero, v_one, col_chunk
 
 
-def rows_bce_all(kind, gamma, all_ent, q, label_index, subj, rel, label_smooth=0.0, col_chunk=None, _what="rows_bce_all"):
+def rows_bce_all(kind, gamma, all_ent, q, label_index, subj, rel, label_smooth=0.0, col_chunk=None, _what="rows_bce_all", bias=None):
     """The 1-N losses from the point where the query rows exist (the scorers' ``query``): the mean over [B, N] of BCELoss(sigmoid(x),
     label_index.labels(subj, rel, label_smooth)) for rows q [B, D] the caller formed, with x = q all_ent^T for kind "dot" (DistMult's
     sub * rel, ConvE's hidden vector after BN2 + ReLU; gamma unused) and x = gamma - ||q - all_ent||_1 for kind "l1" (TransE's
-    sub + rel).  No [B, N] tensor, no host synchronisation."""
+    sub + rel).  bias [num_ent] (kind "dot" only, else ValueError): a per-entity score bias, x = q all_ent^T + bias, with its gradient
+    (CompGCN_ConvE's).  No [B, N] tensor, no host synchronisation."""
     if q.dim() != 2 or all_ent.dim() != 2 or q.shape[1] != all_ent.shape[1]:
         raise ValueError(f"{_what}: all_ent [num_ent, D] and query rows [B, D] expected")
     B, N = int(q.shape[0]), int(all_ent.shape[0])
-    qkey, v_zero, v_one, col_chunk = _bce_all_args(_what, (all_ent, q, subj, rel), B, N, label_index, subj, rel, label_smooth, col_chunk)
-    return _BCE1N.apply(kind, gamma, q, all_ent, label_index, qkey, v_zero, v_one, col_chunk)
+    score_bias_arg(_what, bias, kind, N)                       # (before any device check)
+    tensors = (all_ent, q, subj, rel) if bias is None else (all_ent, q, subj, rel, bias)
+    qkey, v_zero, v_one, col_chunk = _bce_all_args(_what, tensors, B, N, label_index, subj, rel, label_smooth, col_chunk)
+    return _BCE1N.apply(kind, gamma, q, all_ent, label_index, qkey, v_zero, v_one, col_chunk, bias)
 
 
-def dot_bce_all(all_ent, q, label_index, subj, rel, label_smooth=0.0, col_chunk=None, _what="dot_bce_all"):
+def dot_bce_all(all_ent, q, label_index, subj, rel, label_smooth=0.0, col_chunk=None, _what="dot_bce_all", bias=None):
     """distmult_bce_all from the point where the query rows exist: rows_bce_all for the "dot" scorers.  Same kernels, same memory."""
-    return rows_bce_all("dot", None, all_ent, q, label_index, subj, rel, label_smooth, col_chunk, _what=_what)
+    return rows_bce_all("dot", None, all_ent, q, label_index, subj, rel, label_smooth, col_chunk, _what=_what, bias=bias)
 
 
 def distmult_bce_all(all_ent, sub_emb, rel_emb, label_index, subj, rel, label_smooth=0.0, col_chunk=None):

@@ -281,7 +281,9 @@ class a_sum_op(_Operator):
 # ---- score functions (the step after the path): HIP kernels as well (compose + MFMA GEMM with a sigmoid epilogue; L1 kernel) ----
 # The scorer protocol of the paths that keep no [B, N] tensor (FixedNetwork.loss_1n, evaluation.predict_1n): ``query(sub_emb, rel_emb)``
 # returns the [B, D] row every entity is scored against, and ``score_kind`` says how: "dot" (logit = query . entity: DistMult, ConvE)
-# or "l1" (logit = gamma - ||query - entity||_1: TransE).  forward is sigmoid of that logit over all entities.
+# or "l1" (logit = gamma - ||query - entity||_1: TransE).  forward is sigmoid of that logit over all entities.  A "dot" scorer may also
+# carry ``score_bias``, a [num_ent] float32 tensor added to the logits (logit = query . entity + score_bias[entity]: compgcn.CompGCN_ConvE);
+# predict_1n / predict_topk read it with getattr(sf, "score_bias", None) and pass it to the ranks, the evaluation loss and the top-k.
 class sf_TransE_op(nn.Module):
     score_kind = "l1"
 
