@@ -739,6 +739,34 @@ int64_t mrg_block_relabel_workspace_bytes(int64_t E);
 int mrg_block_relabel(const int32_t *gsrc, const int64_t *dst_nodes, int64_t n_dst, int64_t N, int64_t E, int32_t *local,
                       int32_t *firstpos, int64_t *src_nodes, int64_t *lsrc, int32_t *n_new, void *ws, int64_t ws_bytes, void *stream);
 
+/* The same blocks with one fan-out PER EDGE TYPE (csrc/blocks_rel.hip; sampler.NeighborSampler with a per-relation layer).  A run
+ * (v, r) is the in-edges of destination v with type r in ascending edge id.  The resident index: rel_eid [E_graph] int32 = the edge
+ * ids in stable (destination, type, edge id) order; run_ptr [N + 1] = the number of runs before every destination; run_start
+ * [n_runs + 1] = every run's first position in rel_eid, then E_graph; run_type [n_runs]; src_of / type_of [E_graph] int32 = the
+ * graph's sources and types by edge id (type_of may be NULL with etype NULL).
+ * The specification comes twice and the two must agree: fan_host [R] in HOST memory (checked before any launch) and spec [2 R] on
+ * the device = the same R entries, then every type's first column in a row of u.  An entry is -1 (every in-edge of the type), 0
+ * (none) or 1..64 (another value: MRG_E_SHAPE); K = the sum of the entries >= 1 (another K: MRG_E_SHAPE); u [n_dst][K] float64 in
+ * [0, 1) (may be NULL when K == 0).  Of a run of length d with entry f a destination keeps nothing (f == 0), all of it (f == -1 or
+ * d <= f) or the f positions of the run that Floyd's algorithm (mrg_block_emit) picks from u[i][col_r .. col_r + f).
+ *   mrg_block_rel_sizes: first [n_dst + 1] = exclusive sums of the kept edges per destination; first[n_dst] = E.
+ *     ws: mrg_block_rel_sizes_workspace_bytes(n_dst) (the scan's temporary storage and the n_dst + 1 counts).
+ *   mrg_block_rel_emit: the block's E edges with mrg_block_emit's outputs and conventions -- grouped by destination, edge ids
+ *     ascending inside one ACROSS the types -- and the layer entered into local / firstpos; mrg_block_relabel follows, unchanged.
+ *     ws: mrg_block_rel_emit_workspace_bytes(E) (two key buffers and the temporary storage of a key sort over E items).
+ * No launch, memset or work item of these entry points grows with N or E_graph.  n_dst == 0 or E == 0: MRG_OK, nothing launched.
+ * Integer atomics only; deterministic.  MRG_E_NULLPTR, MRG_E_SHAPE (a negative size, R < 1, a bad entry or K), MRG_E_WORKSPACE. */
+int64_t mrg_block_rel_sizes_workspace_bytes(int64_t n_dst);
+int mrg_block_rel_sizes(const int32_t *run_ptr, const int32_t *run_start, const int32_t *run_type, const int64_t *dst_nodes,
+                        int64_t n_dst, int64_t N, const int32_t *fan_host, const int32_t *spec, int R, int32_t *first, void *ws,
+                        int64_t ws_bytes, void *stream);
+int64_t mrg_block_rel_emit_workspace_bytes(int64_t E);
+int mrg_block_rel_emit(const int32_t *run_ptr, const int32_t *run_start, const int32_t *run_type, const int32_t *rel_eid,
+                       const int32_t *src_of, const int32_t *type_of, int64_t E_graph, const int64_t *dst_nodes,
+                       const int32_t *first, int64_t n_dst, int64_t N, const int32_t *fan_host, const int32_t *spec, int R,
+                       const double *u, int64_t K, int64_t E, int64_t *eid, int64_t *etype, int64_t *ldst, int32_t *gsrc,
+                       int32_t *local, int32_t *firstpos, void *ws, int64_t ws_bytes, void *stream);
+
 /* ---- f3: filtered ranking and the [B, N] score functions ---------------------------------------------
  * predict(), reference train/mr_lp_train.py:290-299: entries with a non-zero label are pushed to -1e7, the target keeps
  * its score; ranks[b] = 1 + #(greater) + #(equal at a lower index)  (the position in a stable descending sort). */

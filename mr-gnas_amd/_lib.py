@@ -182,6 +182,10 @@ SIGNATURES = {
     "mrg_block_emit": (_I, [_P, _P, _P, _P, _P, _P, _L, _L, _I, _P, _L, _P, _P, _P, _P, _P, _P, _P]),
     "mrg_block_relabel_workspace_bytes": (_L, [_L]),
     "mrg_block_relabel": (_I, [_P, _P, _L, _L, _L, _P, _P, _P, _P, _P, _P, _L, _P]),
+    "mrg_block_rel_sizes_workspace_bytes": (_L, [_L]),
+    "mrg_block_rel_sizes": (_I, [_P, _P, _P, _P, _L, _L, _P, _P, _I, _P, _P, _L, _P]),
+    "mrg_block_rel_emit_workspace_bytes": (_L, [_L]),
+    "mrg_block_rel_emit": (_I, [_P, _P, _P, _P, _P, _P, _L, _P, _P, _L, _L, _P, _P, _I, _P, _L, _L, _P, _P, _P, _P, _P, _P, _P, _L, _P]),
 }
 
 _lib = None

@@ -7,18 +7,9 @@
 //   mrg_block_relabel   local source indices in first-appearance order, the source-node list, and the tables restored
 // The two tables (local: -1 everywhere, firstpos: INT32_MAX everywhere between calls) are only ever touched at the block's own
 // nodes.  Integer atomics only (atomicMin: order-independent); every output is a pure function of the inputs.
-#include <climits>
-#include <hip/hip_runtime.h>
-#include <rocprim/device/device_scan.hpp>
-#include <rocprim/iterator/counting_iterator.hpp>
-#include <rocprim/iterator/transform_iterator.hpp>
-#include "common.hpp"
+#include "blocks_parts.hpp"
 
 namespace mrg {
-
-constexpr int BLOCKS_MAX_FANOUT = 64;       // one lane of a wave per pick
-
-static inline size_t up256(size_t b) { return (b + 255) & ~(size_t)255; }
 
 // cnt[i] as the scan reads it; index n_dst (one past the end) is 0, so that the exclusive scan leaves the total in first[n_dst].
 // A destination id outside [0, N) has no edges (and is never used as an index).
@@ -49,21 +40,6 @@ struct block_fresh_fn {
 
 typedef rocprim::transform_iterator<rocprim::counting_iterator<int32_t>, block_count_fn, int32_t> count_iter;
 typedef rocprim::transform_iterator<rocprim::counting_iterator<int32_t>, block_fresh_fn, int32_t> fresh_iter;
-
-// Temporary storage of an int32 scan over n items as the workspace queries size it: a HOST formula (the queries answer without a
-// device), 16 bytes per 64 items + 4 KiB -- several times what rocprim's look-back scan takes (8 bytes of state per workgroup of
-// >= 256 items, and a fixed part).  scan_into checks it against rocprim's own figure before it launches.
-static size_t scan_temp_bound(int64_t n) { return up256(4096 + 16 * (size_t)((n + 63) / 64)); }
-
-template <typename It>
-static int scan_into(void* temp, It in, int32_t* out, int64_t n, hipStream_t st) {
-  size_t need = 0, have = scan_temp_bound(n);
-  hipError_t e = rocprim::exclusive_scan(nullptr, need, in, out, 0, (size_t)n, rocprim::plus<int32_t>(), st);
-  if (e != hipSuccess) return (int)e;
-  if (need > have) return MRG_E_WORKSPACE;
-  e = rocprim::exclusive_scan(temp, have, in, out, 0, (size_t)n, rocprim::plus<int32_t>(), st);
-  return e != hipSuccess ? (int)e : MRG_OK;
-}
 
 struct EmitOut {
   int64_t* eid;        // [E] edge ids in the graph
@@ -126,11 +102,9 @@ __global__ __launch_bounds__(MRG_BLOCK) void block_emit_k(const int32_t* __restr
     for (int s = 0; s < k; ++s) {
       const double us = __shfl(ul, s, MRG_WAVE);
       const int32_t j = d - k + s;
-      long long t = (long long)(us * (double)((int64_t)j + 1));   // floor: the product is >= 0
-      if (!(t >= 0)) t = 0;
-      if (t > j) t = j;
-      const bool taken = __ballot(lane < s && pick == (int32_t)t) != 0;
-      if (lane == s) pick = taken ? j : (int32_t)t;
+      const int32_t t = floyd_candidate(us, j);
+      const bool taken = __ballot(lane < s && pick == t) != 0;
+      if (lane == s) pick = taken ? j : t;
     }
     int32_t rank = 0;
     for (int m = 0; m < k; ++m) rank += __shfl(pick, m, MRG_WAVE) < pick ? 1 : 0;

@@ -14,8 +14,11 @@ reference for the same draws -- that is what the tests replay.  The neighbourhoo
 launch of one persistent workgroup (``mrg_sample_edge_neighborhood``) over an adjacency CSR in the reference's append order.
 
 Node classification: ``full_neighbor_blocks`` (torch ops, every in-edge) and ``NeighborSampler`` (per-layer fan-outs over a resident
-in-edge index; the kernels of ``csrc/blocks.hip``) build the blocks of a minibatch.
+in-edge index, over all in-edges or per edge type; the kernels of ``csrc/blocks.hip`` and ``csrc/blocks_rel.hip``) build the blocks of
+a minibatch.
 """
+import ctypes
+
 import numpy as np
 import torch
 
@@ -306,6 +309,61 @@ def _check_fanout(f):
     return f
 
 
+
+def _check_rel_fanout(f):
+    """An entry of a per-relation specification: None (every in-edge of the type; -1 says the same), 0 (none) or 1..MAX_FANOUT."""
+    if f is None:
+        return None
+    if isinstance(f, bool) or not isinstance(f, (int, np.integer)):
+        raise ValueError(f"a per-relation fan-out is None, -1, 0 or an integer in 1..{MAX_FANOUT}, got {f!r}")
+    f = int(f)
+    if f == -1:
+        return None
+    if not 0 <= f <= MAX_FANOUT:
+        raise ValueError(f"a per-relation fan-out is None, -1, 0 or an integer in 1..{MAX_FANOUT} (the limit is {MAX_FANOUT}), got {f}")
+    return f
+
+
+class _RelSpec:
+    """One per-relation layer: ``f[r]`` per edge type (None = every in-edge of the type), ``K`` = the width of its uniforms (the sum
+    of the integer entries >= 1; type r reads the columns ``[off_r, off_r + f_r)``, off_r = the sum over the lower types), and the two
+    copies csrc/blocks_rel.hip takes: ``fan_host`` (a host int32 array, -1 for None) and ``spec`` (int32 [2 R] on the sampler's
+    device: the same entries, then the offsets)."""
+
+    def __init__(self, f, device):
+        self.f = tuple(f)
+        self.R = len(self.f)
+        fan = [-1 if x is None else x for x in self.f]
+        off = [sum(max(x, 0) for x in fan[:r]) for r in range(self.R)]
+        self.K = sum(max(x, 0) for x in fan)
+        self.fan_host = (ctypes.c_int32 * self.R)(*fan)
+        self.spec = torch.tensor(fan + off, dtype=torch.int32, device=device)
+
+    def __repr__(self):
+        return f"per-relation{list(self.f)}"
+
+
+def _rel_entries(f, R):
+    """The R entries of a per-relation layer given as a dict {etype: f} or a 1-D sequence / integer tensor of length R."""
+    if isinstance(f, dict):
+        for key in f:
+            if isinstance(key, bool) or not isinstance(key, (int, np.integer)) or not 0 <= int(key) < R:
+                raise ValueError(f"a per-relation fan-out names the edge types 0..{R - 1}, got the key {key!r}")
+        given = {int(key): v for key, v in f.items()}
+        missing = [r for r in range(R) if r not in given]
+        if missing:
+            raise ValueError(f"a per-relation fan-out names every edge type 0..{R - 1}; missing {missing[:8]}")
+        return [_check_rel_fanout(given[r]) for r in range(R)]
+    if torch.is_tensor(f) or isinstance(f, np.ndarray):
+        if f.ndim != 1 or (f.dtype.is_floating_point or f.dtype == torch.bool if torch.is_tensor(f) else f.dtype.kind not in "iu"):
+            raise ValueError(f"a per-relation fan-out tensor is 1-D and integer, got {f.dtype} with {f.ndim} dimensions")
+        f = [int(x) for x in f.tolist()]
+    f = list(f)
+    if len(f) != R:
+        raise ValueError(f"a per-relation fan-out has one entry per edge type ({R}), got {len(f)}")
+    return [_check_rel_fanout(x) for x in f]
+
+
 class NeighborSampler:
     """DGL's ``MultiLayerNeighborSampler(fanouts, return_eids=True)`` (reference search/mr_nc_search.py:39-44, 231: ``--fanout``)
     over a resident in-edge index of ``graph``: ``sample(seeds)`` returns the blocks of a minibatch, outermost first, with the
@@ -325,11 +383,37 @@ class NeighborSampler:
     are built once, on ``graph.device``.  On a HIP graph a layer is three entry points of csrc/blocks.hip (mrg_block_sizes,
     mrg_block_emit, mrg_block_relabel) and two host reads of sizes; nothing per call grows with the graph.  CPU graphs run the torch
     formulation of the same function.  Preconditions: ``seeds`` are unique node ids.  The scratch tables are shared by all calls:
-    a sampler object is used from ONE stream at a time."""
+    a sampler object is used from ONE stream at a time.
 
-    def __init__(self, graph, fanouts):
-        self.fanouts = [_check_fanout(f) for f in fanouts]
+    Per-relation layers (DGL's fan-out per edge type; ``sample_etype_neighbors`` on a homogenised graph).  With R edge types
+    (``num_etypes``, else 1 + the largest type of the graph, read once here) ``fanouts[j]`` may also be a dict ``{etype: f}`` naming
+    every type or a 1-D sequence / integer tensor of length R; every ``f`` is None / -1 (every in-edge of the type), 0 (none) or an
+    integer 1..64.  ``per_relation=True`` reads an integer entry k as ``[k] * R`` (None keeps its meaning).  A run (v, r) is the
+    in-edges of destination v with type r in ascending edge id, d_vr its length: v keeps nothing of it when f_r = 0, all of it when
+    f_r is None or d_vr <= f_r, else the f_r positions of the run that Floyd's recurrence above picks with d = d_vr, k = f_r.  The
+    block keeps every convention above; edge ids ascend inside a destination ACROSS the types.  Such a layer draws ONE
+    ``torch.rand((n_dst, K), dtype=float64)``, K = the sum of its integer entries >= 1, of which type r reads the columns
+    ``[off_r, off_r + f_r)``, off_r = the sum of the integer entries of the lower types (columns of absent or short runs are drawn
+    and ignored); K = 0 draws nothing.  Its index -- the in-edges in stable (destination, type, edge id) order and the table of
+    runs -- is built here only when some layer is per-relation; on a HIP graph the layer is mrg_block_rel_sizes, mrg_block_rel_emit
+    (csrc/blocks_rel.hip) and mrg_block_relabel, again with two host reads."""
+
+    def __init__(self, graph, fanouts, num_etypes=None, per_relation=False):
         dev = self.device = graph.device
+        etype = _edge_types(graph)
+        fanouts = list(fanouts)
+        scalar = lambda f: f is None or (isinstance(f, (int, np.integer)) and not isinstance(f, bool)) or isinstance(f, (float, str, bytes))
+        rel = [not scalar(f) or (per_relation and _check_fanout(f) is not None) for f in fanouts]
+        R = self.num_etypes = None
+        if any(rel):
+            if etype is None:
+                raise ValueError("a per-relation fan-out needs a graph with edge types")
+            R = int(num_etypes) if num_etypes is not None else (int(etype.max()) + 1 if etype.numel() else 1)
+            if R < 1 or (etype.numel() and not (0 <= int(etype.min()) and int(etype.max()) < R)):
+                raise ValueError(f"NeighborSampler: an edge type lies outside [0, {R})")
+            self.num_etypes = R
+        self.fanouts = [(_RelSpec(_rel_entries([f] * R if scalar(f) else f, R), dev) if is_rel else _check_fanout(f))
+                        for f, is_rel in zip(fanouts, rel)]
         N = self.N = graph.number_of_nodes()
         gsrc, gdst = graph.edges()
         gsrc, gdst = gsrc.long(), gdst.long()
@@ -348,6 +432,18 @@ class NeighborSampler:
         self.in_type = i32(etype[order]) if etype is not None else None
         self.local = torch.full((N,), -1, dtype=torch.int32, device=dev)            # -1 everywhere between calls
         self.firstpos = torch.full((N,), _I32_MAX, dtype=torch.int32, device=dev)   # INT32_MAX everywhere between calls
+        if any(rel):                                                     # the runs (destination, type), edge ids ascending inside one
+            by_type = torch.argsort(etype.long(), stable=True)
+            order = by_type[torch.argsort(gdst[by_type], stable=True)]
+            d_s, t_s = gdst[order], etype.long()[order]
+            head = torch.ones(E, dtype=torch.bool, device=dev)
+            head[1:] = (d_s[1:] != d_s[:-1]) | (t_s[1:] != t_s[:-1])
+            start = torch.nonzero(head).reshape(-1)
+            run_ptr = torch.zeros(N + 1, dtype=torch.long, device=dev)
+            run_ptr[1:] = torch.cumsum(torch.bincount(d_s[start], minlength=N), 0)
+            self.rel_eid, self.run_ptr, self.run_type = i32(order), i32(run_ptr), i32(t_s[start])
+            self.run_start = i32(torch.cat((start, torch.tensor([E], device=dev))))
+            self.src_of, self.type_of = i32(gsrc), i32(etype)
         self._hip = G._hip_ready(gsrc)
         G.settle(dev)
 
@@ -357,21 +453,24 @@ class NeighborSampler:
             raise ValueError(f"draws needs one entry per fan-out ({L}), got {len(draws)}")
         dst_nodes = torch.as_tensor(seeds, device=dev).long().reshape(-1).contiguous()
         layer = self._layer_hip if self._hip else self._layer_torch
+        rel_layer = self._layer_rel_hip if self._hip else self._layer_rel_torch
         blocks = []
         for j in reversed(range(L)):
             k, n_dst, u = self.fanouts[j], int(dst_nodes.numel()), None
-            if k is not None and draws is None:
-                u = torch.rand((n_dst, k), dtype=torch.float64, device=dev, generator=generator)
-            elif k is not None:
+            rel = isinstance(k, _RelSpec)
+            width = k.K if rel else (k or 0)                                  # the uniforms of a row; 0: the layer draws nothing
+            if width and draws is None:
+                u = torch.rand((n_dst, width), dtype=torch.float64, device=dev, generator=generator)
+            elif width:
                 u = draws[j]
-                if not torch.is_tensor(u) or u.dtype != torch.float64 or tuple(u.shape) != (n_dst, k):
-                    raise ValueError(f"draws[{j}] must be a float64 tensor of shape ({n_dst}, {k}), got "
+                if not torch.is_tensor(u) or u.dtype != torch.float64 or tuple(u.shape) != (n_dst, width):
+                    raise ValueError(f"draws[{j}] must be a float64 tensor of shape ({n_dst}, {width}), got "
                                      + (f"{u.dtype} {tuple(u.shape)}" if torch.is_tensor(u) else repr(type(u))))
                 u = u.to(dev).contiguous()
             elif draws is not None and draws[j] is not None:
-                raise ValueError(f"draws[{j}] must be None: layer {j} takes every in-edge")
+                raise ValueError(f"draws[{j}] must be None: layer {j} draws no uniforms")
             try:
-                blk = layer(dst_nodes, k, u)
+                blk = (rel_layer if rel else layer)(dst_nodes, k, u)
             except Exception:
                 self.local.fill_(-1)                                          # a failed layer may have left its entries behind
                 self.firstpos.fill_(_I32_MAX)
@@ -435,9 +534,83 @@ class NeighborSampler:
             keep = torch.arange(k, device=dev)[None, :] < d.clamp(max=k)[:, None]
             ldst = torch.arange(n_dst, device=dev)[:, None].expand(n_dst, k)[keep]
             pos = (r0[:, None] + pick)[keep]
-        E = int(pos.numel())
-        eid, s = self.in_eid[pos].long(), self.in_src[pos].long()
         etype = self.in_type[pos].long() if self.in_type is not None else None
+        return self._relabel_torch(dst_nodes, ldst, self.in_eid[pos].long(), self.in_src[pos].long(), etype)
+
+    def _layer_rel_hip(self, dst_nodes, spec, u):
+        dev, N, n_dst, R = self.device, self.N, int(dst_nodes.numel()), spec.R
+        lib, st = load(), stream_of(dst_nodes)
+        i64 = lambda n: torch.empty(int(n), dtype=torch.int64, device=dev)
+        runs = (ptr(self.run_ptr), ptr(self.run_start), ptr(self.run_type))
+        E = 0
+        if n_dst:
+            first = torch.empty(n_dst + 1, dtype=torch.int32, device=dev)
+            nb = lib.mrg_block_rel_sizes_workspace_bytes(n_dst)
+            ws = torch.empty(max(nb, 16), dtype=torch.uint8, device=dev)
+            call("mrg_block_rel_sizes", runs + (ptr(dst_nodes), n_dst, N, spec.fan_host, ptr(spec.spec), R, ptr(first), ptr(ws), nb, st))
+            E = int(first[n_dst])                                             # host read 1
+            if E < 0:
+                raise ValueError("NeighborSampler: the block has more than 2^31 - 1 edges (are the seeds unique?)")
+        eid, ldst, lsrc, etype = i64(E), i64(E), i64(E), i64(E)
+        if E == 0:
+            return G.Block(dst_nodes, dst_nodes, lsrc, ldst, eid, etype)
+        gsrc = torch.empty(E, dtype=torch.int32, device=dev)
+        src_nodes = i64(n_dst + E)
+        n_new = torch.empty(1, dtype=torch.int32, device=dev)
+        nb = lib.mrg_block_rel_emit_workspace_bytes(E)
+        ws = torch.empty(max(nb, 16), dtype=torch.uint8, device=dev)
+        call("mrg_block_rel_emit", runs + (ptr(self.rel_eid), ptr(self.src_of), ptr(self.type_of), int(self.rel_eid.numel()), ptr(dst_nodes),
+                                           ptr(first), n_dst, N, spec.fan_host, ptr(spec.spec), R, ptr(u), spec.K, E, ptr(eid), ptr(etype),
+                                           ptr(ldst), ptr(gsrc), ptr(self.local), ptr(self.firstpos), ptr(ws), nb, st))
+        nb = lib.mrg_block_relabel_workspace_bytes(E)
+        ws = torch.empty(max(nb, 16), dtype=torch.uint8, device=dev)
+        call("mrg_block_relabel", (ptr(gsrc), ptr(dst_nodes), n_dst, N, E, ptr(self.local), ptr(self.firstpos), ptr(src_nodes), ptr(lsrc),
+                                   ptr(n_new), ptr(ws), nb, st))
+        src_nodes = src_nodes[: n_dst + int(n_new)]                            # host read 2
+        return G.Block(src_nodes, dst_nodes, lsrc, ldst, eid, etype)
+
+    def _layer_rel_torch(self, dst_nodes, spec, u):
+        """A per-relation layer in torch ops: the runs of every destination, Floyd's picks of all cut runs at once, then the block's
+        edges sorted by (destination, edge id)."""
+        dev, n_dst, R = self.device, int(dst_nodes.numel()), spec.R
+        if n_dst and not (0 <= int(dst_nodes.min()) and int(dst_nodes.max()) < self.N):
+            raise ValueError("NeighborSampler: a seed lies outside [0, number_of_nodes())")
+        ar = lambda n: torch.arange(n, device=dev)
+        fan, col = spec.spec[:R].long(), spec.spec[R:].long()
+        q0 = self.run_ptr[dst_nodes].long()
+        nr = self.run_ptr[dst_nodes + 1].long() - q0
+        n_runs = int(nr.sum())
+        rdst = torch.repeat_interleave(ar(n_dst), nr, output_size=n_runs)       # the destination of every run of the layer
+        q = ar(n_runs) - (torch.cumsum(nr, 0) - nr)[rdst] + q0[rdst]
+        s0 = self.run_start[q].long()
+        d, r = self.run_start[q + 1].long() - s0, self.run_type[q].long()
+        f = fan[r]
+        kept = torch.where((f < 0) | (d <= f), d, f)
+        E = int(kept.sum())
+        run = torch.repeat_interleave(ar(n_runs), kept, output_size=E)          # the run of every kept edge, type by type
+        within = ar(E) - (torch.cumsum(kept, 0) - kept)[run]                    # kept whole: positions 0..d-1 of the run
+        big = (f >= 1) & (d > f)
+        if bool(big.any()):                                                     # Floyd's f picks, every cut run at once
+            db, fb, row, cb = d[big], f[big], rdst[big], col[r[big]]
+            P = torch.full((int(db.numel()), int(fb.max())), _I32_MAX, dtype=torch.long, device=dev)
+            for i in range(P.shape[1]):
+                j = db - fb + i
+                ui = u[row, (cb + i).clamp(max=spec.K - 1)]
+                t = torch.minimum(torch.floor(ui * (j + 1).double()).long(), j)
+                P[:, i] = torch.where(i < fb, torch.where((P[:, :i] == t[:, None]).any(1), j, t), P[:, i])
+            P = P.sort(1).values                                                # a run's picks ascending, then the unused columns
+            slot = torch.zeros(n_runs, dtype=torch.long, device=dev)
+            slot[big] = ar(int(db.numel()))
+            cut = big[run]
+            within[cut] = P[slot[run[cut]], within[cut]]
+        eid, ldst = self.rel_eid[s0[run] + within].long(), rdst[run]
+        order = torch.argsort(ldst * max(int(self.rel_eid.numel()), 1) + eid)   # edge ids ascending inside a destination, across types
+        eid, ldst = eid[order], ldst[order]
+        return self._relabel_torch(dst_nodes, ldst, eid, self.src_of[eid].long(), self.type_of[eid].long())
+
+    def _relabel_torch(self, dst_nodes, ldst, eid, s, etype):
+        """Local source indices and the source list of a layer's edges; touches the two tables at the block's nodes only."""
+        dev, n_dst, E = self.device, int(dst_nodes.numel()), int(eid.numel())
         ar = torch.arange(E, dtype=torch.int32, device=dev)
         self.local[dst_nodes] = torch.arange(n_dst, dtype=torch.int32, device=dev)
         self.firstpos.scatter_reduce_(0, s, ar, reduce="amin")

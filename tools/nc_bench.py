@@ -12,7 +12,9 @@
                classes), built with synth.py.  A new batch of seeds every repeat (its blocks are built outside the step's timing).
                Next to it the same step on blocks of sampler.NeighborSampler with fan-outs [4, 4], and the block-build leg
                (DESIGN.md section 9.9): full_neighbor_blocks against NeighborSampler with [None, None] and with [4, 4], the three
-               builders alternating on the same seeds in one process.
+               builders alternating on the same seeds in one process.  With them the per-relation sampler,
+               NeighborSampler with [1] * R per layer: its build in the same alternation, the step on its blocks, and per builder
+               the number of distinct edge types that reach the seeds' block.
 
 HIP events, a warm-up, the median of the repeats.  Prints one JSON line at the end.
 Usage on the GPU box:  python tools/nc_bench.py [--reps 20] [--only a_std|train_step]"""
@@ -153,21 +155,40 @@ def bench_train(reps):
         res["step_4_4_ms"] = round(timeit(step, reps, before=build44), 3)
         res["edges_per_block_4_4_median"] = [int(v) for v in np.median(np.array(edges44[3:reps + 3]), 0)]
 
-        # the block-build leg: the three builders alternate on the same seeds
+        # the same step on per-relation blocks, one in-edge of every type per destination
+        per_rel = SM.NeighborSampler(g, [1, 1], num_etypes=R, per_relation=True)
+        edges_rel = []
+
+        def build_rel():
+            seeds = batches[state["i"] % len(batches)]
+            state["i"] += 1
+            state["blocks"] = per_rel.sample(seeds, generator=gen44)
+            state["seeds"] = seeds
+            edges_rel.append([b.num_edges() for b in state["blocks"]])
+
+        state["i"] = 0
+        res["step_rel_1_ms"] = round(timeit(step, reps, before=build_rel), 3)
+        res["edges_per_block_rel_1_median"] = [int(v) for v in np.median(np.array(edges_rel[3:reps + 3]), 0)]
+
+        # the block-build leg: the four builders alternate on the same seeds; next to the time, how many distinct edge types reach the
+        # seeds' block (counted outside the timing)
         full = SM.NeighborSampler(g, [None, None])
         builders = {"full_neighbor_blocks": lambda sd: SM.full_neighbor_blocks(g, sd, 2), "sampler_none_none": full.sample,
-                    "sampler_4_4": lambda sd: sampled.sample(sd, generator=gen44)}
-        times = {k: [] for k in builders}
+                    "sampler_4_4": lambda sd: sampled.sample(sd, generator=gen44), "sampler_rel_1": lambda sd: per_rel.sample(sd, generator=gen44)}
+        times, reached = {k: [] for k in builders}, {k: [] for k in builders}
         for r in range(reps + 3):
             for k, f in builders.items():
                 a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
                 a.record()
-                f(batches[r])
+                blocks = f(batches[r])
                 b.record()
                 torch.cuda.synchronize()
                 if r >= 3:
                     times[k].append(a.elapsed_time(b))
+                    reached[k].append(int(blocks[-1].edata[G.ETYPE].unique().numel()))
         res["blocks_build_ms"] = {k: round(float(np.median(v)), 3) for k, v in times.items()}
+        res["blocks_build_quartiles_ms"] = {k: [round(float(q), 3) for q in np.percentile(v, [25, 75])] for k, v in times.items()}
+        res["seed_block_edge_types_median"] = {k: int(np.median(v)) for k, v in reached.items()}
         out[name] = res
         print(name, json.dumps(res), flush=True)
         del net, opt, g, tri, trip_index
