@@ -34,7 +34,7 @@
 extern "C" {
 #endif
 
-#define MRG_ABI_VERSION 23   /* 23 (addition, no bump): mrg_rows_bias_bce_fwd / _dlogit, mrg_rows_bias_rank, mrg_rows_bias_topk, mrg_cols_sum (the "dot" sweeps under a per-entity score bias: CompGCN_ConvE without a [B, N] tensor); 23 (addition, no bump): mrg_linear_bwd_input_acc2, mrg_linear_bwd_input3_acc2, mrg_linear_bwd_input3_pair_acc2, mrg_segmax_bwd_input_chain, mrg_gate_row_bwd_acc (the gradient fan-in chain: a reader adds the running sum of the other readers' gradients in its own last store); 23 (addition, no bump): mrg_rows_rank, mrg_transe_bce_fwd / _dlogit / _workspace_bytes, mrg_transe_dist_bwd, mrg_transe_rank / _workspace_bytes (1-N loss and ranks of ConvE and TransE without [B, N] tensors); 23 (addition, no bump: nothing existing changed, and tests pin the number): mrg_distmult_rank, mrg_distmult_rank_workspace_bytes (raw / filtered DistMult ranks as a row GEMM with a counting epilogue); 23: mrg_gemm_set_epilogue removed (the row-order and transposed-accumulator store orders of the split-core row GEMM, measured slower, left the library; accumulator-order stores remain), mrg_gemm_set_wide8 and mrg_gemm_set_small take 0 or 1 only; 22: mrg_cand_linear_fwd, mrg_cand_linear_bwd_input, mrg_cand_linear_colsum_blocks, mrg_cand_linear_workspace_bytes (the candidate Linears of one node-classification MixedOp in one launch, BatchNorm sums included); 21: mrg_adam_step (multi-tensor Adam over the pointer tables of mrg_clip_sgd_step, two launches; per-tensor step counts and lr in device memory); 20: BatchNorm sums formed by a candidate's producer: mrg_gated_branch.given / given_n / given_stride (mrg_mix_stats_coef skips the sweep over such a candidate), mrg_dense_filter3_colsum_blocks, mrg_dense_filter_fwd3_colsum, mrg_gate_row_colsum_blocks, mrg_gate_row_fwd_colsum; 19: mrg_seg_std_workspace_bytes, mrg_seg_std_fwd, mrg_seg_std_bwd (a_std, the standard-deviation aggregator of the node-classification task); 18: mrg_conve_* (the ConvE feature path: BN0 statistics, conv, BN1, split-K fc and their gradients, stacked or interleaved image layout); 17: mrg_ccorr_rows, mrg_ccorr_matrix, mrg_ccorr_matrix_grad (standalone circular correlation: per-row kernel, and the circulant of a shared row with its gradient fold for the row GEMM); 16: mrg_set_stream_blocks, mrg_gate_collapse and mrg_gate_param_grad removed (the streaming grid bound is fixed; the three-segment forms remain); 15: mrg_gated_branch.valid_rows and the valid_rows argument of mrg_mix_finalize_bwd / mrg_zero_* except colstats (the device row count of a static step graph, passed per call instead of the process-wide registry of 13), mrg_linear_bwd_weight_share (the weight gradient of one range of a grouped launch, instead of the process-wide setter of 14); 14: mrg_clip_sgd_step, mrg_optim_chunk (clip_grad_norm_ + SGD with momentum over every parameter tensor in three launches), mrg_gated_branch.act (tanh behind the BatchNorm: CompGraphConv's tail on the epilogue kernels), mrg_gemm_set_small (few-row products on two-tile column blocks), a weight-gradient share setter, mrg_segmax_bwd_input (a_max's input gradient without a dense product); 13: a registry of device-side row counts (the sampled search step as one replayable HIP graph), mrg_seg_reduce_bwd_ordered (aggregator backward walked in destination order), mrg_gemm_set_q (the 16 x 16 x 32 row GEMM at three workgroups per CU for 129..224 output columns); 12: mrg_act_grad_transpose (the [B, N] scorer's output gradient, activation folded in, as [N, B] rows); 11: mrg_gemm_set_wide8 (eight-tile column block for D = 256); 10: mrg_gemm_set_epilogue(2) (transposed accumulators: a tested comparison point); 9: mrg_gated_branch (the MixedOp epilogue recomputes f_dense_comp's output from its gate and f_sparse_comp's from its row factor), mrg_gate_row_fwd / _bwd, mrg_sum_rows_gather, mrg_wgrad_set_variant, mrg_dense_filter_fwd3 out == NULL; 8: mrg_zero_* (cell-zero MixedOp recomputed from the tables), mrg_linear_bwd_input3_pair, mrg_sample_edge_neighborhood; 7: mrg_gemm_set_epilogue (row-order stores of the split-core row GEMM), mrg_set_stream_blocks, mrg_gemm_set_mode(2); 6: fused a_mean (run-sum epilogue, heads reducer, bit-mask backward), mrg_mix_stats_coef; 5: three-segment dense filter entry points; 4: mrg_linear_relu_segmax_fwd (fused a_max); 3: device graph / plan builders, samplers, [B, N] scorers, ranking; 2: GEMM workspaces, span_gcs ext_scal */
+#define MRG_ABI_VERSION 23   /* 23 (addition, no bump): mrg_unrolled_virtual_step, mrg_unrolled_radius, mrg_unrolled_shift, mrg_unrolled_alpha_grad (the parameter passes of the second-order DARTS architect step over the pointer tables of mrg_clip_sgd_step); 23 (addition, no bump): mrg_rows_bias_bce_fwd / _dlogit, mrg_rows_bias_rank, mrg_rows_bias_topk, mrg_cols_sum (the "dot" sweeps under a per-entity score bias: CompGCN_ConvE without a [B, N] tensor); 23 (addition, no bump): mrg_linear_bwd_input_acc2, mrg_linear_bwd_input3_acc2, mrg_linear_bwd_input3_pair_acc2, mrg_segmax_bwd_input_chain, mrg_gate_row_bwd_acc (the gradient fan-in chain: a reader adds the running sum of the other readers' gradients in its own last store); 23 (addition, no bump): mrg_rows_rank, mrg_transe_bce_fwd / _dlogit / _workspace_bytes, mrg_transe_dist_bwd, mrg_transe_rank / _workspace_bytes (1-N loss and ranks of ConvE and TransE without [B, N] tensors); 23 (addition, no bump: nothing existing changed, and tests pin the number): mrg_distmult_rank, mrg_distmult_rank_workspace_bytes (raw / filtered DistMult ranks as a row GEMM with a counting epilogue); 23: mrg_gemm_set_epilogue removed (the row-order and transposed-accumulator store orders of the split-core row GEMM, measured slower, left the library; accumulator-order stores remain), mrg_gemm_set_wide8 and mrg_gemm_set_small take 0 or 1 only; 22: mrg_cand_linear_fwd, mrg_cand_linear_bwd_input, mrg_cand_linear_colsum_blocks, mrg_cand_linear_workspace_bytes (the candidate Linears of one node-classification MixedOp in one launch, BatchNorm sums included); 21: mrg_adam_step (multi-tensor Adam over the pointer tables of mrg_clip_sgd_step, two launches; per-tensor step counts and lr in device memory); 20: BatchNorm sums formed by a candidate's producer: mrg_gated_branch.given / given_n / given_stride (mrg_mix_stats_coef skips the sweep over such a candidate), mrg_dense_filter3_colsum_blocks, mrg_dense_filter_fwd3_colsum, mrg_gate_row_colsum_blocks, mrg_gate_row_fwd_colsum; 19: mrg_seg_std_workspace_bytes, mrg_seg_std_fwd, mrg_seg_std_bwd (a_std, the standard-deviation aggregator of the node-classification task); 18: mrg_conve_* (the ConvE feature path: BN0 statistics, conv, BN1, split-K fc and their gradients, stacked or interleaved image layout); 17: mrg_ccorr_rows, mrg_ccorr_matrix, mrg_ccorr_matrix_grad (standalone circular correlation: per-row kernel, and the circulant of a shared row with its gradient fold for the row GEMM); 16: mrg_set_stream_blocks, mrg_gate_collapse and mrg_gate_param_grad removed (the streaming grid bound is fixed; the three-segment forms remain); 15: mrg_gated_branch.valid_rows and the valid_rows argument of mrg_mix_finalize_bwd / mrg_zero_* except colstats (the device row count of a static step graph, passed per call instead of the process-wide registry of 13), mrg_linear_bwd_weight_share (the weight gradient of one range of a grouped launch, instead of the process-wide setter of 14); 14: mrg_clip_sgd_step, mrg_optim_chunk (clip_grad_norm_ + SGD with momentum over every parameter tensor in three launches), mrg_gated_branch.act (tanh behind the BatchNorm: CompGraphConv's tail on the epilogue kernels), mrg_gemm_set_small (few-row products on two-tile column blocks), a weight-gradient share setter, mrg_segmax_bwd_input (a_max's input gradient without a dense product); 13: a registry of device-side row counts (the sampled search step as one replayable HIP graph), mrg_seg_reduce_bwd_ordered (aggregator backward walked in destination order), mrg_gemm_set_q (the 16 x 16 x 32 row GEMM at three workgroups per CU for 129..224 output columns); 12: mrg_act_grad_transpose (the [B, N] scorer's output gradient, activation folded in, as [N, B] rows); 11: mrg_gemm_set_wide8 (eight-tile column block for D = 256); 10: mrg_gemm_set_epilogue(2) (transposed accumulators: a tested comparison point); 9: mrg_gated_branch (the MixedOp epilogue recomputes f_dense_comp's output from its gate and f_sparse_comp's from its row factor), mrg_gate_row_fwd / _bwd, mrg_sum_rows_gather, mrg_wgrad_set_variant, mrg_dense_filter_fwd3 out == NULL; 8: mrg_zero_* (cell-zero MixedOp recomputed from the tables), mrg_linear_bwd_input3_pair, mrg_sample_edge_neighborhood; 7: mrg_gemm_set_epilogue (row-order stores of the split-core row GEMM), mrg_set_stream_blocks, mrg_gemm_set_mode(2); 6: fused a_mean (run-sum epilogue, heads reducer, bit-mask backward), mrg_mix_stats_coef; 5: three-segment dense filter entry points; 4: mrg_linear_relu_segmax_fwd (fused a_max); 3: device graph / plan builders, samplers, [B, N] scorers, ranking; 2: GEMM workspaces, span_gcs ext_scal */
 
 #define MRG_OK            0
 #define MRG_E_NULLPTR    -1   /* a required pointer is NULL */
@@ -342,6 +342,36 @@ int mrg_clip_sgd_step(void *const *params, const void *const *grads, void *const
 int mrg_adam_step(void *const *params, const void *const *grads, void *const *exp_avg, void *const *exp_avg_sq, int64_t n_tensors,
                   const int32_t *chunk_tensor, const int64_t *chunk_off, const int32_t *chunk_len, int64_t n_chunks, float *step,
                   float *scal, const float *lr, double beta1, double beta2, float eps, float weight_decay, void *stream);
+/* ABI 23 (addition).  The parameter passes of the second-order (unrolled) DARTS architect step (reference models/architect_lp.py:26-35
+ * and :88-103, models/architect.py:23-32 and :84-99) over the pointer tables and chunks of mrg_clip_sgd_step.  One launch each (the
+ * radius: two); the sweeps run on at most 2048 workgroups that stride over the chunks.  eta [1] float32 and scal [3] float32 are DEVICE
+ * memory: nothing here needs a host value of the learning rate or of the norm.  Deterministic.  A chunk whose addresses are all 16-byte
+ * aligned moves 16 bytes per lane, any other chunk (a gradient may be a contiguous view inside a larger buffer) 4 bytes per lane.
+ *   mrg_unrolled_virtual_step   backup = p;  p = p - eta * (momentum * buf + (g + weight_decay * p))   -- the reference's order,
+ *        `moment + dtheta`; NOT clipped (the reference's virtual step is not, even where the real step is).  bufs == NULL or a null
+ *        entry: a zero moment (the reference's `except:` branch); a null gradient entry: a zero gradient.
+ *   mrg_unrolled_radius         partial[b] = sum of squares of chunk b of the tensor list vecs (double; a null entry counts as zero);
+ *        one workgroup folds them in fixed order:  scal = { |v|, R = r / |v|, 1 / (2 R) }.  DEPARTS from the reference, which divides
+ *        by zero when |v| == 0: then R = 0 and 1 / (2 R) is stored as 0, so that the implicit term comes out as zero.  partial: n_chunks
+ *        doubles.  r > 0 (MRG_E_SHAPE otherwise).
+ *   mrg_unrolled_shift          p = backup + sign * R * v, R = scal[1], sign in {+1, -1, 0} (MRG_E_ENUM otherwise): always formed from
+ *        backup, never accumulated; sign 0 is a plain copy (vecs and scal may be NULL), so the parameters come back bit for bit.  A
+ *        null entry of vecs: p = backup.
+ *   mrg_unrolled_alpha_grad     ig = (gp - gn) * scal[2];  out = dalpha - eta * ig   over the architecture parameters' own tables.  A
+ *        null gp / gn entry (an alpha without a gradient) leaves out and ig untouched; a null dalpha entry counts as zero; ig may be
+ *        NULL.
+ * Nothing to do (n_chunks <= 0): MRG_OK (mrg_unrolled_radius still writes scal = {0, 0, 0}).  MRG_E_NULLPTR for a missing table,
+ * MRG_E_SHAPE for more than 2^31 - 1 chunks. */
+int mrg_unrolled_virtual_step(void *const *params, const void *const *grads, const void *const *bufs, void *const *backup,
+                              const int32_t *chunk_tensor, const int64_t *chunk_off, const int32_t *chunk_len, int64_t n_chunks,
+                              const float *eta, float momentum, float weight_decay, void *stream);
+int mrg_unrolled_radius(const void *const *vecs, const int32_t *chunk_tensor, const int64_t *chunk_off, const int32_t *chunk_len,
+                        int64_t n_chunks, double *partial, float r, float *scal, void *stream);
+int mrg_unrolled_shift(void *const *params, const void *const *backup, const void *const *vecs, const int32_t *chunk_tensor,
+                       const int64_t *chunk_off, const int32_t *chunk_len, int64_t n_chunks, const float *scal, int sign, void *stream);
+int mrg_unrolled_alpha_grad(void *const *out, void *const *ig, const void *const *dalpha, const void *const *gp, const void *const *gn,
+                            const int32_t *chunk_tensor, const int64_t *chunk_off, const int32_t *chunk_len, int64_t n_chunks,
+                            const float *eta, const float *scal, void *stream);
 /* `gated` (HOST pointer, NULL or k < 0 = none) of the five entry points that read the candidates: candidate k is the gated
  * filter f_dense_op_comp (reference models/operations_lp.py:356-390) and is NOT stored -- y_host[k] holds its gate
  * sigmoid(W [s ; s_in] + b) (mrg_dense_filter_fwd3 with out == NULL) and its value is recomputed wherever it is read as

@@ -85,6 +85,10 @@ SIGNATURES = {
     "mrg_optim_chunk": (_I, []),
     "mrg_clip_sgd_step": (_I, [_P, _P, _P, _P, _P, _P, _L, _P, _P, _F, _F, _F, _F, _P]),
     "mrg_adam_step": (_I, [_P, _P, _P, _P, _L, _P, _P, _P, _L, _P, _P, _P, ctypes.c_double, ctypes.c_double, _F, _F, _P]),
+    "mrg_unrolled_virtual_step": (_I, [_P, _P, _P, _P, _P, _P, _P, _L, _P, _F, _F, _P]),
+    "mrg_unrolled_radius": (_I, [_P, _P, _P, _P, _L, _P, _F, _P, _P]),
+    "mrg_unrolled_shift": (_I, [_P, _P, _P, _P, _P, _P, _L, _P, _I, _P]),
+    "mrg_unrolled_alpha_grad": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _L, _P, _P, _P]),
     "mrg_act_grad_transpose": (_I, [_P, _P, _P, _L, _L, _I, _P]),
     "mrg_wgrad_set_variant": (_I, [_I]),
     "mrg_linear_fwd": (_I, [_P, _P, _P, _P, _P, _L, _I, _I, _I, _P]),

@@ -15,7 +15,8 @@ Two things the reference does, which a restatement from the DARTS paper would mi
   exception: there the fifth alpha is stepped like the other four.
 
 ``unrolled=True`` (the second-order step) cannot run in the reference -- it calls ``model.new()``, which models/model_search_lp.py has
-commented out -- and raises here.
+commented out -- and raises here.  ``architect_unrolled.SecondOrderArchitect`` extends this class with that step, restated without
+``new()``; ``search_epoch(..., unrolled=True, eta=lr)`` drives it.
 """
 import torch
 
@@ -63,7 +64,7 @@ class Architect(object):
             a.grad = g
 
 
-def search_epoch(model, architect, optimizer, train, val, epoch, warm_epochs, grad_norm=None):
+def search_epoch(model, architect, optimizer, train, val, epoch, warm_epochs, grad_norm=None, unrolled=False, eta=None):
     """One epoch of the reference's search loop between sampling and the scheduler (search/mr_lp_search.py:230-253): the architect
     step on `val` when epoch >= warm_epochs, then forward, loss and backward on `train`, gradient clipping, the weight step and
     ``optimizer.zero_grad()``.  train, val: tuples (g, node_id, src_in, edge_type, data, labels).
@@ -72,11 +73,16 @@ def search_epoch(model, architect, optimizer, train, val, epoch, warm_epochs, gr
     ``clip_grad_norm_(model.parameters(), grad_norm)`` runs before ``optimizer.step()`` (grad_norm=None: no clipping).
 
     Returns (loss, architect.loss) as tensors on their device: nothing here reads the device (the reference synchronises twice per
-    epoch with ``.item()``).  Sampling and the learning-rate scheduler stay with the caller."""
+    epoch with ``.item()``).  Sampling and the learning-rate scheduler stay with the caller.
+
+    unrolled=True: the second-order architect step (`architect`: an ``architect_unrolled.SecondOrderArchitect``) with `eta`, the
+    weights' learning rate (a float or a one-element device tensor; required), and `optimizer` for its momentum buffers."""
     from .optim import ClippedSGD
+    if unrolled and eta is None:
+        raise ValueError("search_epoch(unrolled=True) needs eta, the weights' learning rate")
     g, node_id, src_in, edge_type, data, labels = train
     if epoch >= warm_epochs:
-        architect.step(g, node_id, src_in, edge_type, data, labels, *val, None, optimizer, unrolled=False)
+        architect.step(g, node_id, src_in, edge_type, data, labels, *val, eta if unrolled else None, optimizer, unrolled=bool(unrolled))
     ent, rel = model(g, node_id, src_in, edge_type)
     loss = model.get_loss(g, ent, rel, data, labels)
     loss.backward()

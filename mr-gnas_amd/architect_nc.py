@@ -13,6 +13,8 @@ Where this loop differs from the link-prediction one (``architect.search_epoch``
 * no gradient clipping.
 
 ``unrolled=True`` (the second-order step) raises: it calls ``model.new()``, which cannot run in the reference either.
+``architect_unrolled.SecondOrderArchitectNC`` extends this class with that step, restated without ``new()``;
+``search_step(..., lr=lr, unrolled=True)`` drives it.
 """
 import torch
 
@@ -47,18 +49,23 @@ class Architect(object):
         self.loss.backward()
 
 
-def search_step(model, architect, optimizer, triple_g, train, val, labels, epoch, warm_epochs, criterion, lr=None):
+def search_step(model, architect, optimizer, triple_g, train, val, labels, epoch, warm_epochs, criterion, lr=None, unrolled=False):
     """One batch of the reference's search loop (search/mr_nc_search.py:162-182): the architect step on `val` when
     epoch > warm_epochs, ``optimizer.zero_grad()``, then forward, loss, backward and the weight step on `train`.
     train, val: (seeds, blocks) with the seeds already mapped to label indices; lr: the `eta` handed to the architect (unused by
     the first-order step).
 
     Returns (loss, architect.loss, logits) as detached tensors on their device: nothing here reads the device (the reference
-    synchronises with ``.item()`` three times per batch).  Sampling, accuracy bookkeeping and the scheduler stay with the caller."""
+    synchronises with ``.item()`` three times per batch).  Sampling, accuracy bookkeeping and the scheduler stay with the caller.
+
+    unrolled=True: the second-order architect step (`architect`: an ``architect_unrolled.SecondOrderArchitectNC``); `lr` (a float or
+    a one-element device tensor) is then required."""
+    if unrolled and lr is None:
+        raise ValueError("search_step(unrolled=True) needs lr, the weights' learning rate (the architect's eta)")
     seeds, blocks = train
     val_seeds, val_blocks = val
     if epoch > warm_epochs:
-        architect.step(triple_g, blocks, labels, seeds, val_blocks, val_seeds, lr, optimizer, unrolled=False)
+        architect.step(triple_g, blocks, labels, seeds, val_blocks, val_seeds, lr, optimizer, unrolled=bool(unrolled))
     optimizer.zero_grad()
     logits = model(triple_g, blocks)
     loss = criterion(logits, labels[seeds])

@@ -23,8 +23,10 @@ class _ParamTables:
     device table of parameter pointers, and the per-step table of gradient pointers -- staged through pinned memory, with pinned
     tables of their own for steps captured into HIP graphs."""
 
-    def __init__(self, who, params, capture_tables):
+    def __init__(self, who, params, capture_tables, width=1):
+        """width: how many tensor lists one stage() call may place side by side in g_ptrs (stage_grads() uses the first)."""
         self.who = who
+        self.width = int(width)
         self.params = [p for p in params]
         if not self.params:
             raise ValueError(f"{who}: no parameters")
@@ -48,22 +50,28 @@ class _ParamTables:
         self.p_ptrs = torch.tensor(self._p_ptr_host, dtype=torch.int64, device=dev)
         # pinned staging for the gradient pointers: two buffers used in turn, each guarded by the event of the copy that last read it
         # (the host may run a whole step ahead of the device)
-        self._g_host = [torch.zeros(len(self.params), dtype=torch.int64).pin_memory() for _ in range(2)]
+        self._g_host = [torch.zeros(self.width * len(self.params), dtype=torch.int64).pin_memory() for _ in range(2)]
         self._g_np = [h.numpy() for h in self._g_host]      # the same pinned memory: one vectorised write per step
         self._g_event = [None, None]
         self._turn = 0
         self._captured = []
         self._spare = [torch.zeros(len(self.params), dtype=torch.int64).pin_memory() for _ in range(capture_tables)]
-        self.g_ptrs = torch.zeros(len(self.params), dtype=torch.int64, device=dev)
+        self.g_ptrs = torch.zeros(self.width * len(self.params), dtype=torch.int64, device=dev)
 
-    def flat_state(self, pad=1):
+    def table(self, j):
+        """Device address of the j-th pointer table inside g_ptrs (what stage() filled with its j-th list)."""
+        import ctypes
+        return ctypes.c_void_p(self.g_ptrs.data_ptr() + 8 * j * len(self.params))
+
+    def flat_state(self, pad=1, zero=True):
         """One zeroed float32 allocation with a slot per parameter (each padded to a multiple of `pad` elements): the allocation, the
-        per-parameter views, and the device table of their pointers."""
+        per-parameter views, and the device table of their pointers.  zero=False: left as allocated, for a slot that is always
+        written before it is read."""
         offs, o = [], 0
         for n in self.sizes:
             offs.append(o)
             o += -(-n // pad) * pad
-        flat = torch.zeros(o, dtype=torch.float32, device=self.dev)
+        flat = torch.zeros(o, dtype=torch.float32, device=self.dev) if zero else torch.empty(o, dtype=torch.float32, device=self.dev)
         views = [flat[a:a + n].view_as(p) for a, n, p in zip(offs, self.sizes, self.params)]
         return flat, views, torch.tensor([v.data_ptr() for v in views], dtype=torch.int64, device=self.dev)
 
@@ -79,14 +87,46 @@ class _ParamTables:
             if g is not None and (g.dtype != torch.float32 or not g.is_contiguous()):
                 g = g.float().contiguous()
             grads.append(g)
-        ptrs = [0 if g is None else g.data_ptr() for g in grads]
+        self._copy_in([0 if g is None else g.data_ptr() for g in grads])
+        return grads
+
+    def stage(self, *lists):
+        """stage_grads() for GIVEN tensors (what ``torch.autograd.grad`` returned, an optimiser's momentum buffers): up to `width`
+        lists of one entry per parameter (a tensor or None; a whole list may be None), placed side by side in g_ptrs -- list j at
+        table(j) -- by ONE copy through the same pinned double buffer.  A tensor that is not contiguous float32 is made so.  Returns
+        the tensors as staged, list by list: the caller holds them until its launches are enqueued."""
+        n = len(self.params)
+        if not 1 <= len(lists) <= self.width:
+            raise ValueError(f"{self.who}: stage() takes 1..{self.width} tensor lists")
+        if torch.cuda.is_current_stream_capturing():
+            raise _lib.MrgnasError(f"{self.who}: stage() inside a graph capture is not supported")
+        held, ptrs = [], []
+        for ts in lists:
+            ts = [None] * n if ts is None else list(ts)
+            if len(ts) != n:
+                raise ValueError(f"{self.who}: stage(): a list of {len(ts)} tensors for {n} parameters")
+            for i, t in enumerate(ts):
+                if t is None:
+                    continue
+                if t.dtype != torch.float32 or not t.is_contiguous():
+                    t = ts[i] = t.float().contiguous()
+                if t.numel() != self.sizes[i] or t.device != self.dev:
+                    raise _lib.MrgnasError(f"{self.who}: stage(): tensor {i} does not match its parameter")
+            held.append(ts)
+            ptrs.extend(0 if t is None else t.data_ptr() for t in ts)
+        self._copy_in(ptrs)
+        return held
+
+    def _copy_in(self, ptrs):
+        """The first len(ptrs) entries of g_ptrs, in stream order."""
+        full = len(ptrs) == self.g_ptrs.numel()
         if torch.cuda.is_current_stream_capturing():
             # the captured copy node reads its host buffer again on every replay: a buffer of its own, never rewritten (the gradients
             # of a captured step live at fixed addresses of the graph's memory pool)
             if not self._spare:                              # (pinning allocates: not allowed while a capture is open)
                 raise _lib.MrgnasError(f"{self.who}: more captures than spare pinned pointer tables ({self.who}.CAPTURE_TABLES)")
             host = self._spare.pop()
-            host.numpy()[:] = ptrs
+            host.numpy()[:] = ptrs                           # (stage_grads() of a width-1 table: the only captured form)
             self._captured.append(host)
             self.g_ptrs.copy_(host, non_blocking=True)
         else:
@@ -96,10 +136,13 @@ class _ParamTables:
                 self._g_event[k].synchronize()              # normally long complete
             else:
                 self._g_event[k] = torch.cuda.Event()
-            self._g_np[k][:] = ptrs
-            self.g_ptrs.copy_(self._g_host[k], non_blocking=True)
+            if full:
+                self._g_np[k][:] = ptrs
+                self.g_ptrs.copy_(self._g_host[k], non_blocking=True)
+            else:
+                self._g_np[k][:len(ptrs)] = ptrs
+                self.g_ptrs[:len(ptrs)].copy_(self._g_host[k][:len(ptrs)], non_blocking=True)
             self._g_event[k].record()
-        return grads
 
 
 class ClippedSGD:

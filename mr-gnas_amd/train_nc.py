@@ -134,18 +134,26 @@ def infer_epoch(model, triple_g, loader, labels, inv_target=None, criterion=None
 
 
 def search_epoch(model, architect, optimizer, triple_g, loader, val_loader, labels, epoch, warm_epochs, inv_target=None, criterion=None,
-                 scheduler=None):
+                 scheduler=None, unrolled=False):
     """One epoch of the architecture search (reference search/mr_nc_search.py:152-199): per batch the first batch of `val_loader`
     (``next(iter(val_loader))``), ``architect_nc.search_step``, and the three meters.  Returns (acc, loss, arch_loss); arch_loss
-    averages ``architect.loss * n``, the stale 1.0 of the warm-up epochs included."""
+    averages ``architect.loss * n``, the stale 1.0 of the warm-up epochs included.
+
+    unrolled=True: the second-order architect step (`architect`: an ``architect_unrolled.SecondOrderArchitectNC``).  Its `eta` is the
+    reference's (search/mr_nc_search.py:154): ``scheduler.get_last_lr()[-1]`` at the start of the epoch, or without a scheduler the
+    optimiser's own learning rate."""
     model.train()
     criterion = model._criterion if criterion is None else criterion
     meters = Meters(labels.device)
+    lr = None
+    if unrolled:
+        lr = scheduler.get_last_lr()[-1] if scheduler is not None else (optimizer.lr if hasattr(optimizer, "lr") else optimizer.param_groups[0]["lr"])
     for _, seeds, blocks in loader:
         _, val_seeds, val_blocks = next(iter(val_loader))
         idx = _label_index(seeds, inv_target)
         loss, arch_loss, logits = search_step(model, architect, optimizer, triple_g, (idx, blocks),
-                                              (_label_index(val_seeds, inv_target), val_blocks), labels, epoch, warm_epochs, criterion)
+                                              (_label_index(val_seeds, inv_target), val_blocks), labels, epoch, warm_epochs, criterion,
+                                              lr, bool(unrolled))
         meters.update(loss, logits, labels[idx], arch_loss)
     if scheduler is not None:
         scheduler.step()

@@ -8,6 +8,12 @@
   architect  architect.Architect.step with weight_grads True (the reference's behaviour: the baseline) and False, alternately, at the
              fb15k237_supernet_300 and fb15k237_supernet_30k shapes of bench.py (the step's own sample serves as the validation sample).
 
+  unrolled   the second-order architect step (architect_unrolled.SecondOrderArchitect.step(unrolled=True), eta = 0.01, the step's
+             ClippedSGD for the momentum buffers) against the first-order step of the same object, alternately, on the D = 200 supernet
+             of fb15k237_supernet_300; and its parameter passes alone -- virtual step, radius, two shifts, restore: five mrg_unrolled_*
+             calls -- against the same arithmetic written with torch._foreach_* (eta a host float, R a 0-dim device tensor), on that
+             model's parameter list with fixed random g, v and momentum buffers.
+
 Times: HIP events around the call (they span the launch gaps of a launch-bound sequence) and a host clock around call + synchronise;
 median and the 10th / 90th percentile over the reps.  Launches: device events of a torch.profiler run of its own (kernels and copies
 counted apart), per step.  Prints one JSON line.  Usage on the GPU box:  python tools/optim_bench.py [--reps 50]"""
@@ -123,10 +129,78 @@ def architect_case(workload, reps):
     return out
 
 
+def unrolled_case(workload, reps, gen):
+    from mr_gnas_amd.architect_unrolled import SecondOrderArchitect, UnrolledEngine
+    saved = sys.argv
+    sys.argv = ["bench.py", "--workload", workload]
+    try:
+        args = bench.parse()
+    finally:
+        sys.argv = saved
+    dev = torch.device("cuda", 0)
+    step = bench.Step(args, dev, bench.build_step_inputs(args.workload, args.negative, args.seed))
+    a_args = types.SimpleNamespace(momentum=0.9, weight_decay=3e-4, arch_learning_rate=3e-4, arch_weight_decay=1e-3)
+    sample = (step.g, step.node_id, step.src_in, step.edge_type, step.samples, step.labels)
+    arch = SecondOrderArchitect(dev, step.model, a_args)
+    fns = {"first_order": lambda: arch.step(*sample, *sample, None, None, False),
+           "second_order": lambda: arch.step(*sample, *sample, 0.01, step.opt, True)}
+
+    def between():
+        for p in step.params:
+            p.grad = None
+
+    out = {"step": time_alternately(fns, reps, warm=3, between=between)}
+    for k, fn in fns.items():
+        out["step"][k].update(count_launches(fn, 2))
+        between()
+    # the parameter passes alone, on copies of the parameter list
+    eta, mom, wd, r = 0.01, 0.9, 3e-4, 1e-2
+    mine = [p.detach().clone() for p in step.params]
+    theirs = [p.detach().clone() for p in step.params]
+    g = [torch.randn(p.shape, device=dev, generator=gen) * 1e-2 for p in mine]
+    v = [torch.randn(p.shape, device=dev, generator=gen) * 1e-2 for p in mine]
+    bufs = [torch.randn(p.shape, device=dev, generator=gen) * 1e-2 for p in mine]
+    holder = types.SimpleNamespace(parameters=lambda: mine, arch_parameters=lambda: step.arch)
+    eng = UnrolledEngine(holder, mom, wd)
+    opt = types.SimpleNamespace(state={p: {"momentum_buffer": b} for p, b in zip(mine, bufs)})
+    eta_dev = eng._eta(eta)
+    backup = [torch.empty_like(p) for p in theirs]
+
+    def hip_passes():
+        eng._virtual(g, opt, eta_dev)
+        staged = eng._radius(v)
+        eng._shift(staged, +1)
+        eng._shift(staged, -1)
+        eng._shift(None, 0)
+
+    def foreach_passes():
+        torch._foreach_copy_(backup, theirs)
+        d = torch._foreach_add(g, theirs, alpha=wd)
+        m = torch._foreach_mul(bufs, mom)
+        torch._foreach_add_(m, d)
+        torch._foreach_add_(theirs, m, alpha=-eta)
+        R = r / torch.linalg.vector_norm(torch.stack(torch._foreach_norm(v)))
+        rv = torch._foreach_mul(v, R)
+        torch._foreach_copy_(theirs, backup)
+        torch._foreach_add_(theirs, rv)
+        torch._foreach_copy_(theirs, backup)
+        torch._foreach_sub_(theirs, rv)
+        torch._foreach_copy_(theirs, backup)
+
+    fns = {"hip": hip_passes, "foreach": foreach_passes}
+    out["passes"] = time_alternately(fns, reps)
+    for k, fn in fns.items():
+        out["passes"][k].update(count_launches(fn))
+    out["tensors"], out["elements"] = len(mine), int(sum(p.numel() for p in mine))
+    out["edges"], out["nodes"] = int(step.E), int(step.g.number_of_nodes())
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=50)
     ap.add_argument("--skip-architect", action="store_true")
+    ap.add_argument("--only-unrolled", action="store_true", help="the unrolled leg alone")
     a = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("optim_bench needs a HIP device: nothing here can be measured without one")
@@ -134,6 +208,10 @@ def main():
     dev = torch.device("cuda", 0)
     gen = torch.Generator(device=dev).manual_seed(0)
     res = {"tool": "optim_bench", "reps": a.reps}
+    if a.only_unrolled:
+        res["unrolled_fb15k237_supernet_300"] = unrolled_case("fb15k237_supernet_300", max(10, a.reps // 2), gen)
+        print(json.dumps(res))
+        return
     fixed = bench.FixedStep(types.SimpleNamespace(seed=0, hip_graph=False), dev)
     res["adam_fixedstep_params"] = adam_case(list(fixed.model.parameters()), a.reps, gen)
     del fixed
@@ -145,6 +223,7 @@ def main():
         for w in ("fb15k237_supernet_300", "fb15k237_supernet_30k"):
             res["architect_" + w] = architect_case(w, max(10, a.reps // 2))
             torch.cuda.empty_cache()
+        res["unrolled_fb15k237_supernet_300"] = unrolled_case("fb15k237_supernet_300", max(10, a.reps // 2), gen)
     print(json.dumps(res))
 
 
