@@ -965,7 +965,7 @@ int mrg_sfmix_rank(const float *obj, const float *qd, const float *ent, const fl
                    const int64_t *qkey, const int32_t *when, const int64_t *keys, const int32_t *rowptr, const int32_t *members,
                    const int32_t *gone_at, int64_t U, int64_t Q, int64_t N, int D, int64_t *ranks, void *ws, int64_t ws_bytes,
                    void *stream);
-/* The same leg over THREE scorers, [sf_TransE, sf_DisMult, sf_ConvE] (csrc/sf_mix3_1n.hip; reference models/operations_lp.py:26-30).
+/* The same leg over THREE scorers, [sf_TransE, sf_DisMult, sf_ConvE] (csrc/sf_mix_1n.hip; reference models/operations_lp.py:26-30).
  * Additive: ABI 23.  The two-way entry points argument for argument, with
  *   qh [B][D]: ConvE's hidden rows after BN2 + ReLU (float32, formed by the caller) after qd,  dot2[b, e] = sum_c qh[b, c] * ent[e, c]
  *   (one float32 fused multiply-add chain over c ascending),  p2 = sigmoid(dot2),

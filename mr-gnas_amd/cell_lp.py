@@ -270,7 +270,7 @@ class MixedOp_SF(nn.Module):
     def loss_1n(self, weights, all_ent, sub_emb, rel_emb, label_index, subj, rel, label_smooth=0.0, col_chunk=None):
         """BCELoss(forward(weights, all_ent, sub_emb, rel_emb), label_index.labels(subj, rel, label_smooth)) as a float32 scalar.  On the
         fused path (_fused_1n) neither the [B, N] scores, nor their weighted sum, nor the labels exist (functional.sf_mix_bce_all,
-        csrc/sf_mix_1n.hip; with sf_ConvE as the third scorer functional.sf_mix3_bce_all, csrc/sf_mix3_1n.hip, on ONE call of the ConvE
+        csrc/sf_mix_1n.hip; with sf_ConvE as the third scorer functional.sf_mix3_bce_all, the same file, on ONE call of the ConvE
         scorer's query: one BatchNorm update and one dropout draw per step, as forward has), and `weights` receives its gradient from
         the same sweep; otherwise the literal lines run."""
         width = self._fused_width(weights, all_ent, sub_emb, rel_emb)

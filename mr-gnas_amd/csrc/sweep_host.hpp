@@ -59,6 +59,31 @@ struct SweepGrid {
   }
 };
 
+// The workspace of a 1-N loss / gradient call of the register-tiled sweeps (transe_1n.hip, sf_mix_1n.hip): the queries' label lists
+// qlist [B][2] and nsums float64 partials per workgroup of the sweep's grid.
+struct SweepBcePlan { size_t qlist, partial, total; int64_t nparts; };
+inline SweepBcePlan sweep_bce_plan(const SweepGrid& grid, int64_t B, int nsums) {
+  SweepBcePlan p{};
+  p.nparts = grid.workgroups();
+  size_t off = 256;                                          // slack: the workspace pointer is rounded up to 256 bytes
+  p.qlist = off; off += sweep_up((size_t)B * 2 * sizeof(int32_t));
+  p.partial = off; off += sweep_up((size_t)p.nparts * nsums * sizeof(double));
+  p.total = off;
+  return p;
+}
+
+// ... of a rank call: qinfo [Q][4], the targets' values tval [Q] (a distance or a probability) and the counts [Q]
+struct SweepRankPlan { size_t qinfo, tval, counts, total; };
+inline SweepRankPlan sweep_rank_plan(int64_t Q) {
+  SweepRankPlan p{};
+  size_t off = 256;
+  p.qinfo = off; off += sweep_up((size_t)Q * 4 * sizeof(int32_t));
+  p.tval = off; off += sweep_up((size_t)Q * sizeof(float));
+  p.counts = off; off += sweep_up((size_t)Q * sizeof(unsigned));
+  p.total = off;
+  return p;
+}
+
 // kernel<<<ceil(n / 256), 256>>>(args...): the launch of sweep_prep.hpp's kernels, one thread per row (bce_finish_k: n = 1, its one
 // workgroup).  The kernels are `static`, so each translation unit launches its own copy.  MRG_OK or the HIP error.
 template <class... KARGS, class... ARGS>

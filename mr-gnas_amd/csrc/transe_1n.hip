@@ -17,14 +17,17 @@
 // No float atomics: the loss leaves one float64 partial per workgroup (lane sums in register order, butterfly per wave, the four waves
 // added in order), bce_finish_k adds the partials in a fixed order; counts are integer atomics, one per (row, workgroup).
 // Labels / filters of a tile: thread r < 64 walks the slice of tile row r's ascending list that falls into the tile's 64 entities
-// (binary search for its start, as gemm_bce_label_words does) and leaves a 64-bit mask in LDS.
-#include "sweep_host.hpp"      // the launch bounds, SweepGrid, the workspace's rounding and base, the checks; the prep / finish kernels
+// (binary search for its start, as gemm_bce_label_words does) and leaves a 64-bit mask in LDS.  The mask, the epilogues' edge set-up, the
+// rank count and the partial sums are sweep_tile.hpp's, shared with the mixed-score sweep (sf_mix_1n.hip); the two-operand staging
+// stays written out here (through the header's per-operand helpers the compiler encoded this kernel's compares differently).
+#include "sweep_host.hpp"      // the launch bounds, SweepGrid, the plans, the workspace's rounding and base, the checks; the prep / finish kernels
+#include "sweep_tile.hpp"      // the tile's staging, mask, rank count and partial sums
 #include "topk_parts.hpp"      // L1_TOPK: the order, the per-tile selection, the merge
 
 namespace mrg {
 
-constexpr int L1_T = 64;            // tile: 64 queries x 64 entities
-constexpr int L1_C = 32;            // columns per LDS slice
+constexpr int L1_T = SWT_T;         // tile: 64 queries x 64 entities
+constexpr int L1_C = SWT_C;         // columns per LDS slice
 enum { L1_LOSS = 0, L1_DLOGIT = 1, L1_RANK = 2, L1_TOPK = 3 };
 constexpr bool l1_filters(int epi) { return epi == L1_RANK || epi == L1_TOPK; }      // the tile's mask: filtered members, read through qinfo
 
@@ -70,41 +73,14 @@ __global__ __launch_bounds__(256) void l1_sweep_k(const L1Args a) {
   __shared__ __attribute__((aligned(16))) float se[L1_C][L1_T];
   __shared__ unsigned long long smask[L1_T];
   __shared__ unsigned scnt[L1_T];
-  __shared__ double sred[4];
+  __shared__ double sred[1][4];
   const int tid = threadIdx.x, tx = tid & 15, ty = tid >> 4;
   const int col0 = blockIdx.x * L1_T;
   const int64_t row0 = (int64_t)blockIdx.y * L1_T;
   const int D = a.D;
 
-  if (tid < L1_T) {                                          // the tile row's labels (filtered members) as bits
-    unsigned long long m = 0ull;
-    const int64_t row = row0 + tid;
-    if (row < a.rows) {
-      int lo, hi, when = 0;
-      if constexpr (l1_filters(EPI)) {
-        const int4 qi = *reinterpret_cast<const int4*>(a.qinfo + row * 4);
-        lo = qi.y; hi = qi.z; when = qi.w;
-      } else {
-        const int2 q = *reinterpret_cast<const int2*>(a.qlist + row * 2);
-        lo = q.x; hi = q.y;
-      }
-      if (lo < hi) {
-        const int cbeg = a.e0 + col0, cend = cbeg + L1_T;
-        int b = lo, e = hi;
-        while (b < e) {                                      // first member >= cbeg
-          const int mid = b + ((e - b) >> 1);
-          if (a.list[mid] < cbeg) b = mid + 1; else e = mid;
-        }
-        for (; b < hi; ++b) {
-          const int id = a.list[b];
-          if (id >= cend) break;
-          if constexpr (l1_filters(EPI)) { if (a.gone_at[b] > when) m |= 1ull << (id - cbeg); }
-          else m |= 1ull << (id - cbeg);
-        }
-      }
-    }
-    smask[tid] = m;
-  }
+  // the tile row's labels (filtered members) as bits
+  if (tid < L1_T) smask[tid] = sweep_tile_mask<l1_filters(EPI)>(a, row0 + tid, col0);
 
   // staging: thread (r = tid & 63, part = tid >> 6) carries row r of both operands; per slice 8 of its 32 columns
   const int r = tid & 63, part = tid >> 6;
@@ -171,30 +147,18 @@ __global__ __launch_bounds__(256) void l1_sweep_k(const L1Args a) {
   // ---- epilogues: element (i, j) of the thread is (row0 + ty * 4 + i, col0 + tx * 4 + j) ----
   unsigned long long mrow[4];
   bool rok[4], cok[4];
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    mrow[i] = smask[ty * 4 + i] >> (tx * 4);
-    rok[i] = row0 + ty * 4 + i < a.rows;
-    cok[i] = col0 + tx * 4 + i < a.ncols;
-  }
+  sweep_edges(smask, tx, ty, row0, col0, a.rows, a.ncols, mrow, rok, cok);
 
   if constexpr (EPI == L1_LOSS) {
-    double s = 0.0;
+    double s[1] = {0.0};
 #pragma unroll
     for (int i = 0; i < 4; ++i)
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
-        const float y = ((mrow[i] >> j) & 1ull) ? a.v_one : a.v_zero;
-        const float p = sigmoidf_fast(a.gamma - acc[i][j]);
-        const float lp = fmaxf(logf(p), -100.f), lq = fmaxf(log1pf(-p), -100.f);
-        const float t = (y - 1.f) * lq - y * lp;
-        s += (rok[i] && cok[j]) ? (double)t : 0.0;
+        const float t = sweep_bce_term(sigmoidf_fast(a.gamma - acc[i][j]), ((mrow[i] >> j) & 1ull) ? a.v_one : a.v_zero);
+        s[0] += (rok[i] && cok[j]) ? (double)t : 0.0;
       }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) s += __shfl_xor(s, off);
-    if ((tid & 63) == 0) sred[tid >> 6] = s;
-    __syncthreads();
-    if (tid == 0) a.partial[(int64_t)blockIdx.y * gridDim.x + blockIdx.x] = ((sred[0] + sred[1]) + sred[2]) + sred[3];
+    sweep_partials<1>(s, sred, tid, a.partial + ((int64_t)blockIdx.y * gridDim.x + blockIdx.x));
   } else if constexpr (EPI == L1_DLOGIT) {
     const float gs = a.gscale[0];
 #pragma unroll
@@ -226,26 +190,7 @@ __global__ __launch_bounds__(256) void l1_sweep_k(const L1Args a) {
       topk_select<false, 16, 4>(v, id, a.run_vals[kth], a.run_ids[kth], a.k, a.part + (row * gridDim.x + blockIdx.x) * a.k, rok[i]);
     }
   } else {
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      const int64_t row = row0 + ty * 4 + i;
-      const int64_t rc = rok[i] ? row : a.rows - 1;
-      const float td = a.tdist[rc];
-      const int tg = a.qinfo[rc * 4];
-      unsigned n = 0;
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        const int id = a.e0 + col0 + tx * 4 + j;
-        const float d = acc[i][j];
-        const bool hit = rok[i] && cok[j] && id != tg && !((mrow[i] >> j) & 1ull) && (d < td || (d == td && id < tg));
-        n += hit ? 1u : 0u;
-      }
-#pragma unroll
-      for (int off = 8; off > 0; off >>= 1) n += __shfl_xor(n, off);       // the 16 lanes tx of micro-tile row ty are consecutive
-      if (tx == 0) scnt[ty * 4 + i] = n;
-    }
-    __syncthreads();
-    if (tid < L1_T && row0 + tid < a.rows && scnt[tid]) atomicAdd(a.counts + row0 + tid, scnt[tid]);
+    sweep_rank_count<true>(mrow, rok, cok, tid, row0, a.rows, a.e0 + col0, a.tdist, a.qinfo, scnt, a.counts, [&](int i, int j) { return acc[i][j]; });
   }
 }
 
@@ -253,28 +198,8 @@ inline SweepGrid l1_grid(int64_t rows_all, int64_t c0, int64_t c1, int64_t row_c
   return SweepGrid{rows_all, c0, c1, L1_T, L1_T, row_chunk};
 }
 
-struct L1Plan { size_t qlist, partial, total; int64_t nparts; };
-// ncols: the columns a call sweeps (N for the forward, c1 - c0 for the logit gradient)
-inline L1Plan l1_bce_plan(int64_t B, int64_t ncols) {
-  L1Plan p{};
-  p.nparts = l1_grid(B, 0, ncols).workgroups();              // one float64 partial per workgroup of the sweep
-  size_t off = 256;                                          // slack: the workspace pointer is rounded up to 256 bytes
-  p.qlist = off; off += sweep_up((size_t)B * 2 * sizeof(int32_t));
-  p.partial = off; off += sweep_up((size_t)p.nparts * sizeof(double));
-  p.total = off;
-  return p;
-}
-
-struct L1RankPlan { size_t qinfo, tdist, counts, total; };
-inline L1RankPlan l1_rank_plan(int64_t Q) {
-  L1RankPlan p{};
-  size_t off = 256;
-  p.qinfo = off; off += sweep_up((size_t)Q * 4 * sizeof(int32_t));
-  p.tdist = off; off += sweep_up((size_t)Q * sizeof(float));
-  p.counts = off; off += sweep_up((size_t)Q * sizeof(unsigned));
-  p.total = off;
-  return p;
-}
+// ncols: the columns a call sweeps (N for the forward, c1 - c0 for the logit gradient); one float64 partial per workgroup
+inline SweepBcePlan l1_bce_plan(int64_t B, int64_t ncols) { return sweep_bce_plan(l1_grid(B, 0, ncols), B, 1); }
 
 // The sweep over the columns [c0, c1) of all rows on l1_grid: column blocks of BCE_COLS outermost, row chunks of RANK_CHUNK inside.  `all`
 // carries what does not change from launch to launch; L1_LOSS appends its launches' partials at all.partial.  L1_TOPK: every launch fills
@@ -319,7 +244,7 @@ static int l1_bce_run(const float* obj, const float* ent, const int64_t* qkey, c
                       int64_t U, float gamma, float v_zero, float v_one, int64_t B, int64_t N, int D, int64_t c0, int64_t c1, float* loss,
                       const float* gscale, float* dl, void* ws, int64_t ws_bytes, void* stream) {
   if (!sweep_labels_ok(U, qkey, keys, rowptr, objs)) return MRG_E_NULLPTR;
-  const L1Plan p = l1_bce_plan(B, c1 - c0);
+  const SweepBcePlan p = l1_bce_plan(B, c1 - c0);
   if (!ws || ws_bytes < (int64_t)p.total) return MRG_E_WORKSPACE;
   hipStream_t st = (hipStream_t)stream;
   char* w = sweep_ws_base(ws);
@@ -359,7 +284,7 @@ extern "C" int mrg_transe_bce_dlogit(const float* obj, const float* ent, const i
 
 extern "C" int64_t mrg_transe_rank_workspace_bytes(int64_t Q, int64_t N, int D) {
   if (!sweep_shape_ok(Q, N, D, false)) return MRG_E_SHAPE;
-  return (int64_t)l1_rank_plan(Q).total;
+  return (int64_t)sweep_rank_plan(Q).total;
 }
 
 extern "C" int mrg_transe_rank(const float* obj, const float* ent, const int32_t* t_idx, const int64_t* qkey, const int32_t* when,
@@ -369,12 +294,12 @@ extern "C" int mrg_transe_rank(const float* obj, const float* ent, const int32_t
   if (Q == 0) return MRG_OK;
   if (!obj || !ent || !t_idx || !ranks) return MRG_E_NULLPTR;
   if (!sweep_labels_ok(U, qkey, when, keys, rowptr, members, gone_at)) return MRG_E_NULLPTR;
-  const L1RankPlan p = l1_rank_plan(Q);
+  const SweepRankPlan p = sweep_rank_plan(Q);
   if (!ws || ws_bytes < (int64_t)p.total) return MRG_E_WORKSPACE;
   hipStream_t st = (hipStream_t)stream;
   char* w = sweep_ws_base(ws);
   int32_t* qinfo = (int32_t*)(w + p.qinfo);
-  float* tdist = (float*)(w + p.tdist);
+  float* tdist = (float*)(w + p.tval);
   unsigned* counts = (unsigned*)(w + p.counts);
   int rc = sweep_launch_rows(rank_prep_k, Q, st, t_idx, qkey, when, keys, rowptr, U, Q, qinfo, counts);
   if (rc != MRG_OK) return rc;

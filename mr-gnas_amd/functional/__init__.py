@@ -20,8 +20,8 @@ This package re-exports every name of its modules, so callers keep writing ``fro
   cell_zero   Cell zero: the MixedOp over the compose candidates, recomputed from the entity / relation tables (csrc/cell_zero.hip).
   scoring     The step after the path: DistMult triple scoring, the [B, N] score functions and the 1-N losses without [B, N] tensors
               (csrc/scoring.hip, bce.hip, transe_1n.hip).
-  sf_mix      The score-function search leg: the 1-N loss under the mixed TransE / DistMult score without [B, N] tensors (csrc/sf_mix_1n.hip),
-              and under the three-way TransE / DistMult / ConvE score (csrc/sf_mix3_1n.hip).
+  sf_mix      The score-function search leg: the 1-N loss under the mixed TransE / DistMult score without [B, N] tensors, and
+              under the three-way TransE / DistMult / ConvE score (csrc/sf_mix_1n.hip, one kernel template for both).
   ccorr       Standalone circular correlation ccorr(a, b): per-row kernel, or a shared row's circulant on the row GEMM (csrc/ccorr.hip).
   conve       ConvE feature path: BN0 -> conv -> BN1 -> ReLU -> fc of the (subject, relation) image, and the ConvE scorer (csrc/conve.hip).
   nc          Node-classification aggregators on a block: a_std (csrc/segstd.hip) and a_sum / a_mean / a_max without self rows.
@@ -73,7 +73,7 @@ from .scoring import (  # noqa: F401
 )
 from .sf_mix import (  # noqa: F401
     _MixBCE1N, sf_mix_bce_all, sf_mix_bce_mean, sf_mix_bce_grad,
-    _Mix3BCE1N, sf_mix3_bce_all, sf_mix3_bce_mean, sf_mix3_bce_grad,
+    sf_mix3_bce_all, sf_mix3_bce_mean, sf_mix3_bce_grad,
 )
 from .ccorr import (  # noqa: F401
     _CCorrRows, _Circulant, ccorr,

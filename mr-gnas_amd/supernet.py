@@ -316,7 +316,7 @@ class ScoreSearchNetwork(SearchNetwork):
 
     def __init__(self, *args, sf_registry=None, sf_ops=None, sf_args=None, **kwargs):
         """sf_ops: the scorers searched over (default operations_lp.SF_OPS); ['sf_TransE', 'sf_DisMult', 'sf_ConvE'] adds the scorer the
-        reference's published genotype ends in (csrc/sf_mix3_1n.hip), whose sizes and dropouts come in sf_args (embed_dim, k_h, k_w,
+        reference's published genotype ends in (csrc/sf_mix_1n.hip), whose sizes and dropouts come in sf_args (embed_dim, k_h, k_w,
         num_filt, ker_sz, conve_hid_drop, feat_drop; embed_dim = k_h * k_w = the feature width).  Then the fifth architecture parameter
         is [1, len(sf_ops)] and score_func carries sf_ConvE's parameters and buffers.  With the defaults nothing differs: the same
         state_dict keys, the same random draws."""

@@ -1,4 +1,4 @@
-"""Restatements for the three-way score-function search leg (csrc/sf_mix3_1n.hip, functional.sf_mix3_bce_all, cell_lp.MixedOp_SF.loss_1n
+"""Restatements for the three-way score-function search leg (csrc/sf_mix_1n.hip, functional.sf_mix3_bce_all, cell_lp.MixedOp_SF.loss_1n
 over ['sf_TransE', 'sf_DisMult', 'sf_ConvE'], evaluation.mix_ranks / predict_mix with a hidden operand), shared by test_sf_mix3_cpu.py and
 test_sf_mix3_gpu.py.  Plain torch on whatever device the operands live on; no kernel of the library is called here."""
 import torch

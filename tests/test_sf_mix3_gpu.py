@@ -1,4 +1,4 @@
-"""The three-way score-function search leg on the device: csrc/sf_mix3_1n.hip (the four-operand register-tiled sweep with its loss,
+"""The three-way score-function search leg on the device: csrc/sf_mix_1n.hip (the four-operand register-tiled sweep with its loss,
 gradient and counting epilogues), functional.sf_mix3_bce_all, cell_lp.MixedOp_SF.loss_1n over ['sf_TransE', 'sf_DisMult', 'sf_ConvE'],
 supernet.ScoreSearchNetwork(sf_ops=...) under architect.search_epoch, evaluation.mix_ranks / predict_mix with ConvE's hidden rows --
 against float64, against the two-way sweep (w2 = 0: bit for bit), against the fixed-genotype losses, against the dense literal

@@ -4,7 +4,7 @@ the relation rows, the mixing weights and the ConvE parameters -- in one process
 
   dense3  the literal formulation: cell_lp.MixedOp_SF(['sf_TransE', 'sf_DisMult', 'sf_ConvE']).forward (three [B, N] score matrices
           and their weighted sum) + LabelIndex.labels ([B, N] targets) + F.binary_cross_entropy
-  fused3  the same module's loss_1n: one sf_ConvE_op.query + functional.sf_mix3_bce_all (csrc/sf_mix3_1n.hip): no [B, N] tensor
+  fused3  the same module's loss_1n: one sf_ConvE_op.query + functional.sf_mix3_bce_all (csrc/sf_mix_1n.hip): no [B, N] tensor
   fused2  functional.sf_mix_bce_all (csrc/sf_mix_1n.hip), the two-way leg over SF_OPS.  NOT the same number: for scale.
 
 at FB15k-237's shape (N = 14 541, B = 256, D = 200; sf_ConvE_op's default 20 x 10 image, 200 filters of 7 x 7, train mode with its
